@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: rays/s of the full forward render (BASELINE.json `metric`).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: the contract fields, the roofline of the
+timed run and, at N > 1, every rank's statistics.  `--full` adds what takes runs or checks of its own: the ray
+generation timing, the CPU baseline, the other configurations under `also` and, at N > 1, the single-GPU render
+of the same image with the check of the gathered image on every rank.
+`--dump-outputs DIR` writes what the last timed step returned (image, depth, weights_sum of every ray; the
+gathered image at N > 1) as DIR/<name>.npy in float32; the inputs are seeded, so runs with the same arguments
+compare output for output.
 
 `--gpus N` is honoured either way: under `torch.distributed.run` (WORLD_SIZE set; must equal N) or
 stand-alone, in which case this script re-launches itself as N ranks (one per GPU, RCCL) and fails
@@ -13,7 +21,7 @@ Workload, random-init (hash-generated) weights, synthetic orbit camera, rays res
                    --schedule ref     = [128,64,32] with both proposal grids (the reference's default).
   N > 1 (default)  BASELINE configs[3], STRONG scaling: one fixed 1600x1600 image, contiguous row bands
                    (dist.shard_rows), ONE RCCL all-gather of rgb|depth|weights_sum per frame; value = 2.56e6 rays
-                   / step time.  The same image rendered by one GPU is measured in the same run
+                   / step time.  With `--full`, the same image rendered by one GPU is measured in the same run
                    (`single_gpu_same_image`), which is the base of the speed-up.  `--scaling weak` keeps the
                    round-1 behaviour (an 800 x 800*N image).  `--scaling strong --gpus 1` renders config 4 on one GPU.
 One "step" = one whole-image render of this rank's band (+ at N>1 the all-gather; the gather of frame k
@@ -25,7 +33,8 @@ Prints ONE JSON line (rank 0): the contract fields plus
                  ceilings that bind: the gather address rate of the texture addressers at the
                  shader clock measured in the kernel, the fabric-side traffic from the committed PMC passes;
                  the SURVEY 8(d) algorithmic figure is kept, labelled as cache-absorbed
-  cpu_baseline — the CPU oracle (a port, oracle/) on a bounded sample of the same rays, N = 1 only
+  cpu_baseline — `--full`, N = 1 only: the CPU oracle (a port, oracle/) on a bounded sample of the same rays
+  also         — `--full`, N = 1 only: the other configurations (null otherwise)
 """
 import argparse
 import ctypes as C
@@ -63,10 +72,15 @@ def parse_args():
     ap.add_argument("--tables", choices=["f32", "f16"], default="f16",
                     help="hash-table storage: f16 = what BASELINE configs[1] names (the reference's fp16 mode keeps its tables in half), f32 = the "
                          "model's own parameters; arithmetic is fp32 either way")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: ray generation, CPU baseline, the `also` configurations, and at "
+                         "N > 1 the single-GPU render of the same image with the image check on every rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (image, depth, weights_sum) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--force-dist", action="store_true", help="world size 1 only: still go through RCCL (init, all-gather pipeline, barriers)")
-    ap.add_argument("--primary-only", action="store_true", help="skip the extra configurations reported under `also`")
+    ap.add_argument("--primary-only", action="store_true", help="with --full: skip the extra configurations reported under `also`")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="N > 1: nccl (= RCCL over xGMI, the product) or gloo (device tensors staged through the host: lets the N > 1 branch run where "
                          "RCCL cannot, e.g. several ranks on one GPU)")
@@ -188,6 +202,29 @@ def source_fingerprint():
     return h.hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 64_000_000 - 4096      # 64 MB in all: 4096 bytes are left for the .npy headers (128 bytes per file, at most 4 files)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: every array (one row per ray) as DIR/<name>.npy in float32.  Beyond DUMP_LIMIT_BYTES in all, the same fixed,
+    seeded sample of rows is taken from every array, and the sampled row numbers are written as rows.npy (float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(4 * (t[0].numel() if t.dim() > 1 else 1) for t in arrays.values())
+    rows = None
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(1234).choice(n, size=k, replace=False))
+    for name, t in arrays.items():
+        if rows is not None:
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(t.detach().float().cpu().numpy()))
+    if rows is not None:
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+
+
 def main():
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -256,16 +293,18 @@ def main():
     total_rays = H * W
     models = {}
 
-    # ---- ray generation (a1; SURVEY 8(d): reported as its own term, not inside `value`) ----
+    # ---- ray generation (a1; SURVEY 8(d): reported as its own term, not inside `value`; timed with --full) ----
     rays_o, rays_d = rm.generate_rays(pose, intr, H, W, device=dev, row_begin=b, row_end=e)
-    torch.cuda.synchronize()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    for _ in range(10):
-        rm.generate_rays(pose, intr, H, W, device=dev, row_begin=b, row_end=e)
-    ev[1].record()
-    torch.cuda.synchronize()
-    raygen_ms = ev[0].elapsed_time(ev[1]) / 10
+    raygen_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(10):
+            rm.generate_rays(pose, intr, H, W, device=dev, row_begin=b, row_end=e)
+        ev[1].record()
+        torch.cuda.synchronize()
+        raygen_ms = ev[0].elapsed_time(ev[1]) / 10
     n_local = rays_o.shape[0]
 
     def measure(schedule, tables, n_steps, n_warm, rays=None, gather=multi, compact=False, aabb=None, gain=None):
@@ -352,8 +391,15 @@ def main():
     m = measure(args.schedule, args.tables, args.steps, args.warmup)
     steps, params, out = m["steps"], m["params"], m["out"]
     value, ms_per_step, s_bytes, final_ms = m["value"], m["ms_per_step"], m["s_bytes"], m["final_ms"]
+    if args.dump_outputs and rank == 0:
+        beat("dump outputs")
+        if m["image"] is not None:      # N > 1: the gathered image (rgb | depth | weights_sum) every rank received in the last step
+            img = m["image"]
+            dump_outputs(args.dump_outputs, {"image": img[:, :3], "depth": img[:, 3], "weights_sum": img[:, 4]})
+        else:
+            dump_outputs(args.dump_outputs, {k: out[k] for k in ("image", "depth", "weights_sum")})
 
-    # ---- N > 1: the gathered image must be the single-process image ON EVERY RANK; the same image on ONE GPU for the ratio; and every
+    # ---- N > 1, with --full: the gathered image must be the single-process image ON EVERY RANK; the same image on ONE GPU for the ratio; always: every
     # ---- rank's own numbers in the line (band time, kernel time, time lost waiting on the all-gather), so that one run explains itself ----
     single = gathered_check = per_rank = None
     if multi:           # (world > 1, or --force-dist on one GPU: the same code through RCCL at world size 1)
@@ -372,6 +418,7 @@ def main():
                     "note": "band_ms_per_step: each rank's own wall time per step before the closing barrier (the step time of the line is the max over "
                             "ranks); all_gather_wait_ms_per_step: time the rank's compute stream spent waiting on collectives (HIP events around "
                             "every wait); gather_path: in_place (RCCL alias) or staged"}
+    if multi and args.full:
         beat("single-GPU render of the same image + check on every rank")
         ro_f, rd_f = rm.generate_rays(pose, intr, H, W, device=dev)
         full = torch.empty(H * W, 5, device=dev, dtype=torch.float32)
@@ -468,15 +515,15 @@ def main():
         "other_kernels_ms": {"pack": round(m["pack_ms"], 4) if m["pack_ms"] else None,
                              "prop0": round(m["prop_ms"][0], 4) if m["prop_ms"][0] else None,
                              "prop1": round(m["prop_ms"][1], 4) if m["prop_ms"][1] else None,
-                             "generate_rays": round(raygen_ms, 4)},
+                             "generate_rays": round(raygen_ms, 4) if raygen_ms is not None else None},
         "whole_path": {"algorithmic_bytes_per_ray": algorithmic_bytes_per_ray(steps, s_bytes), "flops_per_ray": flops_per_ray(steps),
-                       "rays_per_s_incl_ray_generation": round(total_rays / ((ms_per_step + raygen_ms) * 1e-3), 1)},
+                       "rays_per_s_incl_ray_generation": round(total_rays / ((ms_per_step + raygen_ms) * 1e-3), 1) if raygen_ms is not None else None},
         "source_fingerprint": fp,
     }
 
     # ---- other configurations of the same path, measured in the same process (N = 1 only, short) ----
     also = None
-    if world == 1 and not multi and not args.primary_only and scaling == "single":
+    if args.full and world == 1 and not multi and not args.primary_only and scaling == "single":
         also = {}
         kc = kernel_counters()
         for sch, tb in (("flat128", "f32"), ("ref", "f32"), ("flat128", "f16"), ("ref", "f16")):
@@ -627,7 +674,7 @@ def main():
         out = m["out"]
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle as orc
@@ -656,7 +703,7 @@ def main():
         cfg_name = {"single": "BASELINE configs[1]", "strong": "BASELINE configs[3]", "weak": "BASELINE configs[1] per GPU"}[scaling]
         line = {
             "metric": f"rays/s full render ({W}x{H}, hashgrid L=16 + 2x64 MLP)", "value": round(value, 1), "unit": "rays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": bool(args.full), "ms_per_step": round(ms_per_step, 4),
             "median_ms_per_step": round(m["median_ms"], 4),
             "higher_is_better": True, "scaling": "weak" if scaling == "weak" else "strong", "vs_baseline": None,
             "dtype": "f32 arithmetic / %s tables" % args.tables, "tables": args.tables, "data": "synthetic",
@@ -682,6 +729,7 @@ def main():
             line["n1_same_image_rays_per_s"] = single["rays_per_s"]      # the base a scaling curve of THIS image must use (not the 800x800 N=1 line)
             line["speedup_vs_single_gpu_same_image"] = round(value / single["rays_per_s"], 3)
             line["gathered_image_check"] = gathered_check
+        if per_rank is not None:
             line["per_rank"] = per_rank
         print(json.dumps(line), file=json_out, flush=True)
     if dog is not None:

@@ -27,10 +27,10 @@ def test_rccl_leg_on_one_gpu():
 
 
 def test_bench_line_schema():
-    """bench.py prints ONE JSON line with the contract's fields; roofline carries bound / achieved / peak / unit / frac / traffic for the
+    """bench.py --full prints ONE JSON line with the contract's fields; roofline carries bound / achieved / peak / unit / frac / traffic for the
     dominant kernel, the workload names BASELINE configs[1], the metric names the image rendered."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -49,6 +49,35 @@ def test_bench_line_schema():
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["max_abs_rgb_diff_vs_gpu"] < 1e-4
     assert d["also"] and "flat128_f32" in d["also"] and "ref_f16" in d["also"]
+
+
+def test_plain_bench_line_and_dumped_outputs(gpu, tmp_path):
+    """A plain bench.py run times exactly --steps steps and carries no extras; --dump-outputs writes what the last timed step returned,
+    equal bit for bit to the same render made here from the same seeded field and camera."""
+    import json
+    from sanerf_hq_amd import raymarching as rm, synth
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False and d["unit"] == "rays/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 640000 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    assert d["cpu_baseline"] is None and d["also"] is None and d["roofline"]["bound"] == "hbm"
+    # the final stage is counted over the timed region only: --steps 3 timed steps of launch.launches launches each
+    assert d["roofline"]["launch"]["launches"] >= 1 and d["roofline"]["launches"] == 3 * d["roofline"]["launch"]["launches"]
+    assert sorted(os.listdir(tmp_path)) == ["depth.npy", "image.npy", "weights_sum.npy"]
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("image", "depth", "weights_sum")}
+    assert got["image"].shape == (640000, 3) and got["depth"].shape == (640000,) and got["weights_sum"].shape == (640000,)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    steps = [128]
+    model = synth.product_model(synth.synthetic_params(steps, seed=0), steps, False, gpu)
+    fx, fy, _, _ = synth.pinhole_intrinsics(800, 800)
+    ro, rd = rm.generate_rays(synth.orbit_pose(1.0, 20.0, 30.0), (fx, fy, 400.0, 400.0), 800, 800, device=gpu)
+    want = rm.render_rays(rm.RenderPlan(model, steps, torch.float16), ro, rd, tile_w=800)
+    for k, a in got.items():
+        assert np.array_equal(a, want[k].cpu().numpy()), k
 
 
 def test_two_processes_share_the_gpu_over_gloo_with_device_tensors():
@@ -83,7 +112,7 @@ def test_bench_multi_rank_branch_runs_on_one_gpu(nproc):
     RCCL itself needs one GPU per rank).  Row bands from dist.band_align / shard_rows, the render written straight into the gather buffer
     (sn_render_io.out_stride), PipelinedGather, barrier + max-over-ranks timing, then rank 0 renders the whole image alone: the N > 1 JSON
     schema is complete and the gathered image equals the single-process image bit for bit."""
-    line = _run_bench(nproc, ["--dist-backend", "gloo", "--shared-device", "--hw", "256", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    line = _run_bench(nproc, ["--dist-backend", "gloo", "--shared-device", "--hw", "256", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert line["n_gpus"] == nproc and line["ranks_joined"] == nproc and line["dist_backend"] == "gloo" and line["shared_device"] is True
     assert line["scaling"] == "strong" and line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "rays/s" and line["value"] > 0
     assert line["config"]["image"] == [256, 256] and line["config"]["rays_per_gpu"] == 256 * 256 // nproc
@@ -99,6 +128,30 @@ def test_bench_multi_rank_branch_runs_on_one_gpu(nproc):
     assert pr["rays"] == [256 * 256 // nproc] * nproc and 0 <= pr["slowest_rank"] < nproc
     assert pr["gather_path"].startswith("staged (gloo")
     assert line["gathered_image_check"]["max_abs_diff_per_rank"] == [0.0] * nproc
+
+
+def test_plain_bench_multi_rank_line_and_dumped_image(gpu, tmp_path):
+    """A plain N > 1 run (no --full) carries every rank's statistics but not the single-GPU render or its image check; --dump-outputs
+    writes the gathered image of the last timed step, equal bit for bit to the whole image rendered here in one process."""
+    from sanerf_hq_amd import raymarching as rm, synth
+    line = _run_bench(2, ["--dist-backend", "gloo", "--shared-device", "--hw", "256", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert line["n_gpus"] == 2 and line["ranks_joined"] == 2 and line["steps"] == 3 and line["full"] is False and line["value"] > 0
+    for key in ("single_gpu_same_image", "n1_same_image_rays_per_s", "speedup_vs_single_gpu_same_image", "gathered_image_check"):
+        assert key not in line, key
+    pr = line["per_rank"]
+    for key in ("band_ms_per_step", "median_frame_ms", "final_kernel_ms", "all_gather_wait_ms_per_step", "shader_clock_mhz", "rays"):
+        assert len(pr[key]) == 2, key
+    assert pr["rays"] == [256 * 128] * 2 and all(t > 0 for t in pr["band_ms_per_step"]) and pr["gather_path"].startswith("staged (gloo")
+    assert sorted(os.listdir(tmp_path)) == ["depth.npy", "image.npy", "weights_sum.npy"]
+    steps = [128]
+    model = synth.product_model(synth.synthetic_params(steps, seed=0), steps, False, gpu)
+    fx, fy, _, _ = synth.pinhole_intrinsics(256, 256)
+    ro, rd = rm.generate_rays(synth.orbit_pose(1.0, 20.0, 30.0), (fx, fy, 128.0, 128.0), 256, 256, device=gpu)
+    want = rm.render_rays(rm.RenderPlan(model, steps, torch.float16), ro, rd, tile_w=256)
+    for k in ("image", "depth", "weights_sum"):
+        got = np.load(tmp_path / f"{k}.npy")
+        assert got.dtype == np.float32 and got.shape == tuple(want[k].shape), (k, got.shape)
+        assert np.array_equal(got, want[k].cpu().numpy()), k
 
 
 def test_bench_watchdog_names_the_stalled_rank():
@@ -121,7 +174,7 @@ def test_bench_force_dist_runs_the_multi_rank_code_through_rccl_at_world_size_on
     per-rank statistics, broadcast of the single-GPU image, the check on every rank -- on the one GPU a box has, through the nccl (= RCCL) backend."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29561")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--scaling", "strong", "--hw", "512", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--primary-only"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--no-cpu-baseline", "--primary-only", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
     import json

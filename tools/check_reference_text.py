@@ -13,7 +13,12 @@ transformed mechanically and compared.
     and (b) the device basis (csrc/sh_basis.inc, generated independently by tools/gen_sh.py; fp32 literals: 1e-7 relative).
     (The derivatives are covered the same way by tools/gen_oracle_sh_grad.py.)
 
-  python tools/check_reference_text.py        # prints what was verified; exit code 0 = all equal
+ 3. Recorded results.  `--write-golden` records what the reference's text computes (the grid index on 20000 random vertices, the 64
+    SH polynomials evaluated at 256 points) in tests/golden/reference_text.npz; tests/test_oracle_identities.py checks the oracle and
+    the device basis against that fixture, so the check runs without the reference.
+
+  python tools/check_reference_text.py                  # prints what was verified; exit code 0 = all equal
+  python tools/check_reference_text.py --write-golden   # rewrites tests/golden/reference_text.npz
 """
 import os
 import re
@@ -140,9 +145,8 @@ def transliterate(body: str, indent: str = "    ") -> str:
     return "\n".join(out)
 
 
-def check_grid_index(trials: int = 200000) -> int:
-    import numpy as np
-    import oracle as orc
+def reference_grid_index():
+    """get_grid_index(D, gridtype, ch, size, res, pg, C) -> int: the executed text of gridencoder.cu:45-79."""
     src = open(os.path.join(REF, "gridencoder/src/gridencoder.cu")).read()
     head = src[:src.index("kernel_grid(")]                      # the helper functions precede the kernels (lines 45-79)
     code = []
@@ -153,10 +157,19 @@ def check_grid_index(trials: int = 200000) -> int:
     assert "2654435761" in text and "805459861" in text and "% hashmap_size" in text and "stride <= hashmap_size" in text, text
     env = {"U32": U32}
     exec(text, env)
+
+    def get_grid_index(D, gridtype, ch, size, res, pg, C):
+        env["D"], env["C"] = D, C
+        return int(env["get_grid_index"](gridtype, ch, size, res, [U32(v) for v in pg]))
+    return get_grid_index
+
+
+def grid_cases(trials):
+    """(D, gridtype, size, res, pg, C, ch): random vertices for D = 2..5, hashed and tiled grids, power-of-two and odd table sizes,
+    resolutions up to 2^20."""
+    import numpy as np
     rng = np.random.default_rng(7)
-    n = 0
     for D in (2, 3, 4, 5):
-        env["D"] = D
         for _ in range(trials // 4):
             gridtype = int(rng.integers(0, 2))
             size = int(rng.choice([1 << int(rng.integers(3, 25)), int(rng.integers(8, 1 << 22)) | 1, 8 * int(rng.integers(1, 1 << 18))]))
@@ -164,11 +177,22 @@ def check_grid_index(trials: int = 200000) -> int:
             pg = [int(v) for v in rng.integers(0, res, size=D)]
             C = int(rng.choice([1, 2, 4, 8]))
             ch = int(rng.integers(0, C))
-            env["C"] = C
-            want = int(env["get_grid_index"](gridtype, ch, size, res, [U32(v) for v in pg]))
-            got = (orc.grid_row(gridtype, size, res, pg) * C + ch) & 0xFFFFFFFF
-            assert want == got, (D, gridtype, size, res, pg, C, ch, want, got)
-            n += 1
+            yield D, gridtype, size, res, pg, C, ch
+
+
+def oracle_grid_index(gridtype, ch, size, res, pg, C):
+    import oracle as orc
+    return (orc.grid_row(gridtype, size, res, pg) * C + ch) & 0xFFFFFFFF
+
+
+def check_grid_index(trials: int = 200000) -> int:
+    ref_index = reference_grid_index()
+    n = 0
+    for D, gridtype, size, res, pg, C, ch in grid_cases(trials):
+        want = ref_index(D, gridtype, ch, size, res, pg, C)
+        got = oracle_grid_index(gridtype, ch, size, res, pg, C)
+        assert want == got, (D, gridtype, size, res, pg, C, ch, want, got)
+        n += 1
     print(f"grid index: the oracle's grid_row equals the executed text of gridencoder.cu:45-79 on {n} random vertices "
           f"(D = 2..5, hash + tiled, wrap-around products)")
     return n
@@ -177,7 +201,7 @@ def check_grid_index(trials: int = 200000) -> int:
 # ------------------------------------------------------------------------------------------------
 # 2. SH forward
 # ------------------------------------------------------------------------------------------------
-def check_sh_forward():
+def _sh_poly_parser():
     import sympy as sp
     import gen_oracle_sh_grad as g
     x, y, z = g.x, g.y, g.z
@@ -186,16 +210,34 @@ def check_sh_forward():
     def poly(expr):
         e = re.sub(r"(\d)f\b", r"\1", expr)
         return g.monomials(sp.sympify(e, locals=names, rational=False))
+    return poly
 
+
+def reference_sh_polys():
+    """{k: {(a, b, c): coefficient}}: every `outputs[k] = ...;` of write_sh (shencoder.cu:50-120) as a polynomial."""
+    poly = _sh_poly_parser()
     src = open(os.path.join(REF, "shencoder/src/shencoder.cu")).read()
     block = src[src.index("auto write_sh = "):src.index("write_sh();")]
     ref = {int(m.group(1)): poly(m.group(2)) for m in re.finditer(r"outputs\[(\d+)\] = (.*?);", block)}
     assert sorted(ref) == list(range(64)), sorted(ref)
+    return ref
+
+
+def own_sh_polys():
+    """(oracle, device): the oracle's forward polynomials (oracle.c:ORC_SH_BODY) and the device basis (csrc/sh_basis.inc)."""
+    import gen_oracle_sh_grad as g
+    poly = _sh_poly_parser()
     orc_polys = [g.monomials(p) for p in g.oracle_polys()]
     dev_src = open(os.path.join(ROOT, "sanerf-hq_amd/csrc/sh_basis.inc")).read()
     dev_block = dev_src[dev_src.index("#define SN_SH_VALUES(o)"):dev_src.index("#define SN_SH_DX(o)")]
     dev = {int(m.group(1)): poly(m.group(2)) for m in re.finditer(r"o\[(\d+)\] = (.*?);", dev_block)}
     assert sorted(dev) == list(range(64)), sorted(dev)
+    return orc_polys, dev
+
+
+def check_sh_forward():
+    ref = reference_sh_polys()
+    orc_polys, dev = own_sh_polys()
     worst = {"oracle": 0.0, "device": 0.0}
     for k in range(64):
         for label, got, tol in (("oracle", orc_polys[k], 1e-12), ("device", dev[k], 2e-7)):
@@ -209,9 +251,86 @@ def check_sh_forward():
     return worst
 
 
+# ------------------------------------------------------------------------------------------------
+# 3. recorded results: tests/golden/reference_text.npz
+# ------------------------------------------------------------------------------------------------
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_text.npz")
+GOLDEN_GRID_TRIALS = 20000
+GOLDEN_SH_POINTS = 256          # > 120, the number of monomials of degree <= 7 in x, y, z: the values pin every coefficient
+
+
+def sh_values(polys, pts):
+    """(values, sum of |term|) of each polynomial at each point, fp64: [P, len(polys)] each."""
+    import numpy as np
+    val = np.zeros((len(pts), len(polys)))
+    mag = np.zeros((len(pts), len(polys)))
+    for k, p in enumerate(polys):
+        for (a, b, c), coef in p.items():
+            t = coef * pts[:, 0] ** a * pts[:, 1] ** b * pts[:, 2] ** c
+            val[:, k] += t
+            mag[:, k] += np.abs(t)
+    return val, mag
+
+
+def write_golden(path=GOLDEN):
+    """Records what the reference's text computes, so that the check runs without it: the grid index of gridencoder.cu:45-79 (executed)
+    on the random vertices of grid_cases, and the 64 SH polynomials of shencoder.cu:50-120 evaluated in fp64 at random points of
+    [-1, 1]^3 (off the sphere: polynomials equal on the sphere only would differ here)."""
+    import numpy as np
+    ref_index = reference_grid_index()
+    cases = list(grid_cases(GOLDEN_GRID_TRIALS))
+    pg = np.zeros((len(cases), 5), np.uint32)
+    for i, c in enumerate(cases):
+        pg[i, :c[0]] = c[4]
+    ref = reference_sh_polys()
+    pts = np.random.default_rng(11).uniform(-1.0, 1.0, size=(GOLDEN_SH_POINTS, 3))
+    val, mag = sh_values([ref[k] for k in range(64)], pts)
+    np.savez_compressed(path, grid_D=np.array([c[0] for c in cases], np.uint8), grid_gridtype=np.array([c[1] for c in cases], np.uint8),
+                        grid_size=np.array([c[2] for c in cases], np.uint32), grid_res=np.array([c[3] for c in cases], np.uint32), grid_pg=pg,
+                        grid_C=np.array([c[5] for c in cases], np.uint8), grid_ch=np.array([c[6] for c in cases], np.uint8),
+                        grid_index=np.array([ref_index(c[0], c[1], c[6], c[2], c[3], c[4], c[5]) for c in cases], np.uint32),
+                        sh_points=pts, sh_values=val, sh_abs_terms=mag)
+    print(f"wrote {path}: {len(cases)} grid vertices, 64 SH polynomials at {len(pts)} points")
+
+
+def check_grid_index_golden(path=GOLDEN) -> int:
+    import numpy as np
+    with np.load(path) as z:
+        f = {k: z[k] for k in z.files if k.startswith("grid_")}
+    n = len(f["grid_index"])
+    for i in range(n):
+        D = int(f["grid_D"][i])
+        got = oracle_grid_index(int(f["grid_gridtype"][i]), int(f["grid_ch"][i]), int(f["grid_size"][i]), int(f["grid_res"][i]),
+                                [int(v) for v in f["grid_pg"][i, :D]], int(f["grid_C"][i]))
+        assert got == int(f["grid_index"][i]), (i, got, int(f["grid_index"][i]))
+    print(f"grid index: the oracle's grid_row equals the recorded results of gridencoder.cu:45-79 on {n} random vertices")
+    return n
+
+
+def check_sh_forward_golden(path=GOLDEN):
+    import numpy as np
+    with np.load(path) as f:
+        pts, want, want_mag = f["sh_points"], f["sh_values"], f["sh_abs_terms"]
+    orc_polys, dev = own_sh_polys()
+    worst = {}
+    for label, polys, tol in (("oracle", orc_polys, 1e-12), ("device", [dev[k] for k in range(64)], 2e-7)):
+        got, mag = sh_values(polys, pts)
+        err = np.abs(got - want) / np.maximum(np.maximum(mag, want_mag), 1e-300)
+        worst[label] = float(err.max())
+        assert worst[label] < tol, (label, np.unravel_index(err.argmax(), err.shape), worst[label])
+    print(f"SH forward: 64 polynomials equal the recorded values of shencoder.cu:50-120 at {len(pts)} points (worst relative difference "
+          f"{worst['oracle']:.1e} for the oracle, {worst['device']:.1e} for the device basis sh_basis.inc, fp32 literals)")
+    return worst
+
+
 def main():
+    if "--write-golden" in sys.argv:
+        write_golden()
+        return 0
     if not os.path.isdir(REF):
-        print("reference not present: nothing checked")
+        print("reference not present: checked against its recorded results")
+        check_grid_index_golden()
+        check_sh_forward_golden()
         return 0
     check_grid_index()
     check_sh_forward()

@@ -67,5 +67,5 @@ python tools/feat_patch_ab.py 2>/dev/null | tail -1 > $out/feat_patch_ab_final.j
 python tools/prop_pair_ab.py 2>/dev/null | tail -1 > $out/prop_pair_ab.json
 python tools/band_small_ab.py 2>/dev/null | tail -1 > $out/band_small_ab.json
 python tools/gemm_f32_bench.py 2>/dev/null | tail -1 > $out/gemm_f32_bench.json
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 ls -la $out
