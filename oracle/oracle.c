@@ -777,7 +777,8 @@ static void mlp_forward_one(const orc_mlp *m, const mlp_prep *p, const float *x,
             for (uint32_t o = 0; o < nout; o++) b[o] = fmaf(w[o], ak, b[o]);
         }
         if (l != m->num_layers - 1) {
-            if (m->activation == 0) { for (uint32_t o = 0; o < nout; o++) b[o] = b[o] > 0 ? b[o] : 0.0f; }
+            /* relu as torch.relu: a NaN stays NaN (leaky: 0.01 * NaN is NaN already) */
+            if (m->activation == 0) { for (uint32_t o = 0; o < nout; o++) b[o] = (b[o] > 0 || b[o] != b[o]) ? b[o] : 0.0f; }
             else { for (uint32_t o = 0; o < nout; o++) b[o] = b[o] > 0 ? b[o] : 0.01f * b[o]; }
         }
         memcpy(a, b, sizeof(float) * nout);

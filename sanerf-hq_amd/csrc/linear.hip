@@ -87,8 +87,8 @@ __global__ __launch_bounds__(256) void k_gemm_f32(GemmArgs g) {
             const uint32_t row = m0 + wm + (r & 3u) + 8u * (r >> 2) + 4u * (lane >> 5);
             if (row < g.M) {
                 float v = acc[r] + bj;
-                if (g.act == 1) v = __builtin_fmaxf(v, 0.0f);
-                else if (g.act == 2) v = __builtin_fmaxf(v, v * 0.01f);
+                if (g.act == 1) v = relu_ieee(v);
+                else if (g.act == 2) v = relu_or_leaky(v, true);
                 g.c[(int64_t)row * g.c_row + col] = v;
             }
         }

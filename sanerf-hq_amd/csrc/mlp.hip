@@ -399,10 +399,10 @@ __global__ __launch_bounds__(256, 1) void k_mlp_wide(WideArgs a) {
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t cc = c + i;
                 const float t = xrow[cc < a.din ? cc : a.din - 1u];
-                mx = fmaxf(mx, cc < a.din ? fabsf(t) : 0.0f);
+                mx = __builtin_elementwise_maximum(mx, cc < a.din ? fabsf(t) : 0.0f);    // a NaN entry makes the row maximum NaN: left unscaled
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        mx = __builtin_elementwise_maximum(mx, __shfl_xor(mx, 32));
         const uint32_t bits = __float_as_uint(mx);
         int e = (int)((bits >> 23) & 255u) - 127;
         if (mx > 0.0f && mx < __builtin_inff() && e > -100 && e < 100) {
@@ -487,7 +487,6 @@ __global__ __launch_bounds__(256, 1) void k_mlp_wide(WideArgs a) {
         split2h(v[4], v[5], bh.z, bl.z); split2h(v[6], v[7], bh.w, bl.w);
     };
 
-    const float act_slope = a.leaky ? 0.01f : 0.0f;
     for (uint32_t l = 0; l < a.nl; ++l) {
         const WideLayer L = a.layer[l];
         wide_trace(128u + l);
@@ -585,10 +584,8 @@ __global__ __launch_bounds__(256, 1) void k_mlp_wide(WideArgs a) {
                     float v[8];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        // t > 0 ? t : t * slope (slope 0.01 or 0) as a multiply and a max: slope < 1, so t * slope > t exactly
-                        // when t < 0 (same product, same result; -0 instead of +0 for ReLU of a negative, which the split maps to 0 too)
-                        const float t = acc[mt][8 * hf + i];
-                        v[i] = __builtin_fmaxf(t, t * act_slope);
+                        // t > 0 ? t : 0.01 t (leaky) or 0 (ReLU) as an IEEE maximum: 0.01 t > t exactly when t < 0; a NaN stays NaN
+                        v[i] = relu_or_leaky(acc[mt][8 * hf + i], a.leaky != 0u);
                     }
                     uint4 &bh = hbh[2 * mt + hf], &bl = hbl[2 * mt + hf];
                     split2h(v[0], v[1], bh.x, bl.x); split2h(v[2], v[3], bh.y, bl.y);
@@ -602,11 +599,16 @@ __global__ __launch_bounds__(256, 1) void k_mlp_wide(WideArgs a) {
     const WideLayer LL = a.layer[a.nl - 1u];
     {   // range check of the split-fp16 arithmetic: an activation beyond 65504 turned into inf in a hi half and reaches
         // the last layer as inf / NaN.  0 * x is NaN exactly for those.  Sticky flag, read by sn_mlp_wide_overflow().
+        // Only the last layer's own tiles: the others still hold a hidden layer's pre-activations, where -inf is legitimate (relu -> 0).
+        const uint32_t out_tiles = a.layer[a.nl - 1u].mt;
         float chk = 0.0f;
 #pragma unroll
-        for (int mt = 0; mt < WIDE_MT; ++mt)
+        for (int mt = 0; mt < WIDE_MT; ++mt) {
+            float t = 0.0f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) chk = __builtin_fmaf(acc[mt][r], 0.0f, chk);
+            for (int r = 0; r < 16; ++r) t = __builtin_fmaf(acc[mt][r], 0.0f, t);
+            chk += (uint32_t)mt < out_tiles ? t : 0.0f;
+        }
         if (ok && chk != chk) g_wide_overflow = 1;
     }
     wide_trace(160u);                      // all layers done; what follows is the output epilogue
@@ -806,10 +808,10 @@ __global__ __launch_bounds__(256, 1) void k_mlp_wide_j(WideArgs a) {
             for (uint32_t i = 0; i < 8u; ++i) {
                 const uint32_t cc = c + i;
                 const float t = xrow[cc < a.din ? cc : a.din - 1u];
-                mx = fmaxf(mx, cc < a.din ? fabsf(t) : 0.0f);
+                mx = __builtin_elementwise_maximum(mx, cc < a.din ? fabsf(t) : 0.0f);    // a NaN entry makes the row maximum NaN: left unscaled
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        mx = __builtin_elementwise_maximum(mx, __shfl_xor(mx, 32));
         const uint32_t mbits = __float_as_uint(mx);
         const int e = (int)((mbits >> 23) & 255u) - 127;
         if (mx > 0.0f && mx < __builtin_inff() && e > -100 && e < 100) {
@@ -944,8 +946,8 @@ __global__ __launch_bounds__(256, 1) void k_mlp_wide_j(WideArgs a) {
     sync_and_prefetch(0u, int_tag<0>{});
     prefetch_first_pair(0u);
 
-    const float act_slope = a.leaky ? 0.01f : 0.0f;
-    auto act = [&](float t) { if constexpr (SAVE == 2) return t; else return __builtin_fmaxf(t, t * act_slope); };   // k_mlp_wide: multiply + max (network.py:65-66); backward: escape_tile applied the derivative
+    const bool leaky = a.leaky != 0u;
+    auto act = [&](float t) { if constexpr (SAVE == 2) return t; else return relu_or_leaky(t, leaky); };   // network.py:65-66; backward: escape_tile applied the derivative
     auto bias_tile = [&](uint32_t l, int mt, floatx16 &b) {      // register r of this lane = neuron 32 mt + (r&3) + 8 (r>>2) + 4 half
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -1330,11 +1332,16 @@ __global__ __launch_bounds__(256, 1) void k_mlp_wide_j(WideArgs a) {
     // ---- epilogue (k_mlp_wide's) ----
     {   // range check of the split-fp16 arithmetic: an activation beyond 65504 turned into inf in a hi half and reaches
         // the last layer as inf / NaN.  0 * x is NaN exactly for those.  Sticky flag, read by sn_mlp_wide_overflow().
+        // Only the last layer's own tiles: the others still hold a hidden layer's pre-activations, where -inf is legitimate (relu -> 0).
+        const uint32_t out_tiles = a.layer[a.nl - 1u].mt;
         float chk = 0.0f;
 #pragma unroll
-        for (int mt = 0; mt < WIDE_MT; ++mt)
+        for (int mt = 0; mt < WIDE_MT; ++mt) {
+            float t = 0.0f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) chk = __builtin_fmaf(acc[mt][r], 0.0f, chk);
+            for (int r = 0; r < 16; ++r) t = __builtin_fmaf(acc[mt][r], 0.0f, t);
+            chk += (uint32_t)mt < out_tiles ? t : 0.0f;
+        }
         if (ok && chk != chk) g_wide_overflow = 1;
     }
     if constexpr (XMODE == 3) {            // renderer.py:384: out[ray, m] = sum_t w[ray, t] * logits[ray, t, m]: this wave's t of this tile

@@ -244,8 +244,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_mask16(WideArgs a) {
 #pragma unroll
     for (int i = 0; i < W16_AHEAD; ++i) read_a(0u, i, i);
 
-    const float act_slope = a.leaky ? 0.01f : 0.0f;
-    auto act = [&](float t) { return __builtin_fmaxf(t, t * act_slope); };   // k_mlp_wide: multiply + max (network.py:65-66)
+    const bool leaky = a.leaky != 0u;
+    auto act = [&](float t) { return relu_or_leaky(t, leaky); };   // network.py:65-66, as in k_mlp_wide
     auto escape_tile = [&](auto tc) {      // (the empty asm makes the moved value opaque: see k_mlp_wide_j)
         constexpr int t = decltype(tc)::value;
         static_for<4>([&](auto rc) { constexpr int r = decltype(rc)::value; float v = acc[t][r]; asm("" : "+v"(v)); prev[4 * t + r] = v; });

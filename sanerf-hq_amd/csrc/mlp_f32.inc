@@ -169,7 +169,7 @@ __global__ __launch_bounds__(F32_THREADS, 1) void k_mlp_f32_train(F32Args a) {
                 const uint32_t rr = rh * 32u + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * hi;      // accumulator register r of lane l: D[(r&3) + 8 (r>>2) + 4 (l>>5)][l & 31]
                 float v = acc[t][r];
                 if (hidden) {
-                    v = v > 0.0f ? v : (a.leaky ? 0.01f * v : 0.0f);
+                    v = relu_or_leaky(v, a.leaky);
                     Ht[n * F32_HT_STRIDE + rr] = v;
                 }
                 if (row0 + rr < a.n_rows && n < N) out[(size_t)(row0 + rr) * N + n] = v;

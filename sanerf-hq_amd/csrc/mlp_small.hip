@@ -157,7 +157,7 @@ __device__ __forceinline__ void layer_finish(const SmallArgs &a, const uint32_t 
                 const bool ok = row[jt] < a.N;
                 if constexpr (!P::BWD) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[q][jt][r] = acc[q][jt][r] > 0.0f ? acc[q][jt][r] : 0.0f;
+                    for (int r = 0; r < 16; ++r) acc[q][jt][r] = relu_ieee(acc[q][jt][r]);
                 } else {
                     tile_gate<E>(a.mask[F], row[jt], ok, h, q, acc[q][jt]);
                 }

@@ -654,7 +654,7 @@ __device__ __forceinline__ void dense_uniform(const float *__restrict__ W, const
         float acc = 0.0f;
 #pragma unroll
         for (int k = 0; k < IN; ++k) acc = __builtin_fmaf(W[o * IN + k], x[k], acc);
-        if (ACT == 1) acc = __builtin_fmaxf(acc, 0.0f);       // ReLU as one v_max_f32 (= acc > 0 ? acc : 0 up to the sign of a zero; NaN -> 0 either way)
+        if (ACT == 1) acc = relu_ieee(acc);                  // ReLU as one v_maximum_f32 (a NaN stays NaN, as torch.relu)
         y[o] = acc;
     }
 }
@@ -722,7 +722,7 @@ __device__ __forceinline__ void dense_ldsw_t(const float *__restrict__ Wl, const
         }
     }
 #pragma unroll
-    for (int o = 0; o < OUT; ++o) y[o] = (ACT == 1) ? __builtin_fmaxf(acc[o], 0.0f) : acc[o];
+    for (int o = 0; o < OUT; ++o) y[o] = (ACT == 1) ? relu_ieee(acc[o]) : acc[o];
 }
 
 // Tiny-MLP weights in the [out][in_padded] layout (view MLP, evaluated once per ray)
@@ -750,7 +750,7 @@ __device__ __forceinline__ void dense_ldsw(const float *__restrict__ Wl, const f
             if (4 * k4 + 2 < IN) acc = __builtin_fmaf(w.z, x[4 * k4 + 2], acc);
             if (4 * k4 + 3 < IN) acc = __builtin_fmaf(w.w, x[4 * k4 + 3], acc);
         }
-        if (ACT == 1) acc = __builtin_fmaxf(acc, 0.0f);       // ReLU as one v_max_f32 (= acc > 0 ? acc : 0 up to the sign of a zero; NaN -> 0 either way)
+        if (ACT == 1) acc = relu_ieee(acc);                  // ReLU as one v_maximum_f32 (a NaN stays NaN, as torch.relu)
         y[o] = acc;
     }
 }
@@ -775,7 +775,7 @@ __device__ __forceinline__ void dense_ldsw_col(const float *__restrict__ Wl, con
             if (4 * k4 + 2 < IN) acc = __builtin_fmaf(w.z, x[4 * k4 + 2], acc);
             if (4 * k4 + 3 < IN) acc = __builtin_fmaf(w.w, x[4 * k4 + 3], acc);
         }
-        if (ACT == 1) acc = __builtin_fmaxf(acc, 0.0f);       // ReLU as one v_max_f32 (= acc > 0 ? acc : 0 up to the sign of a zero; NaN -> 0 either way)
+        if (ACT == 1) acc = relu_ieee(acc);                  // ReLU as one v_maximum_f32 (a NaN stays NaN, as torch.relu)
         yout[o * stride] = acc;
     }
 }
@@ -1214,18 +1214,13 @@ __global__ void k_pack_grid_mlp(const float *__restrict__ w1, const float *__res
     pack[t] = v;
 }
 
-// max(t, 0) of a matrix-core result as one v_max_i32 on the bit pattern (negative floats are negative integers,
-// -0 -> +0 like `t > 0 ? t : 0`).  The float form costs two instructions there: the compiler cannot prove an MFMA
-// output canonical and puts a v_max_f32 t, t, t in front of every v_max_f32 0, t (145 of the final stage's 2236
-// vector instructions per sample).  Differs from the select only for a NaN input with the sign bit clear.
-__device__ __forceinline__ float relu_bits(float t) {
-    const int b = __builtin_bit_cast(int, t);
-    return __builtin_bit_cast(float, b > 0 ? b : 0);
-}
 
+// max(t, 0) of matrix-core results, one IEEE maximum each (relu_ieee: -0 -> +0, a NaN of either sign stays NaN like torch.relu).
+// fmaxf would cost two instructions there: the compiler cannot prove an MFMA output canonical and puts a v_max_f32 t, t, t in front of
+// every v_max_f32 0, t; the maximum needs no canonical input.
 __device__ __forceinline__ floatx16 relu16(floatx16 v) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = relu_bits(v[i]);
+    for (int i = 0; i < 16; ++i) v[i] = relu_ieee(v[i]);
     return v;
 }
 
@@ -1369,7 +1364,7 @@ __device__ __forceinline__ uint32_t pack_h2(float a, float b) {
 __device__ __forceinline__ void acc_to_b_hi(const floatx16 &v, int half, uint4 &bh) {
     float x[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = relu_bits(v[8 * half + i]);
+    for (int i = 0; i < 8; ++i) x[i] = relu_ieee(v[8 * half + i]);
     bh.x = pack_h2(x[0], x[1]); bh.y = pack_h2(x[2], x[3]); bh.z = pack_h2(x[4], x[5]); bh.w = pack_h2(x[6], x[7]);
 }
 
@@ -1377,7 +1372,7 @@ __device__ __forceinline__ void acc_to_b_hi(const floatx16 &v, int half, uint4 &
 __device__ __forceinline__ void acc_to_b(const floatx16 &v, int half, uint4 &bh, uint4 &bl) {
     float x[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = relu_bits(v[8 * half + i]);
+    for (int i = 0; i < 8; ++i) x[i] = relu_ieee(v[8 * half + i]);
     split2(x[0], x[1], bh.x, bl.x); split2(x[2], x[3], bh.y, bl.y);
     split2(x[4], x[5], bh.z, bl.z); split2(x[6], x[7], bh.w, bl.w);
 }
@@ -1599,7 +1594,7 @@ __device__ __forceinline__ void grid_mlp_mfma16_l12(const uint4 *__restrict__ pk
             acc = mfma_np<NP>(ah, al, bh, bl, acc);
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) x[mt * 16 + r] = relu_bits(acc[r]);
+        for (int r = 0; r < 16; ++r) x[mt * 16 + r] = relu_ieee(acc[r]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -1657,7 +1652,7 @@ __device__ __forceinline__ void dense_lds(const float *__restrict__ W, const flo
         float acc = 0.0f;
 #pragma unroll
         for (int k = 0; k < IN; ++k) acc = __builtin_fmaf(W[o * IN + k], x[k], acc);
-        if (ACT == 1) acc = __builtin_fmaxf(acc, 0.0f);       // ReLU as one v_max_f32 (= acc > 0 ? acc : 0 up to the sign of a zero; NaN -> 0 either way)
+        if (ACT == 1) acc = relu_ieee(acc);                  // ReLU as one v_maximum_f32 (a NaN stays NaN, as torch.relu)
         yout[o * stride] = acc;
     }
 }
@@ -2161,7 +2156,7 @@ __device__ __forceinline__ void dense_any_b(const float *__restrict__ W, uint32_
         }
 #pragma unroll
         for (uint32_t q = 0; q < 4u; ++q) {
-            if (o0 + q < out) yout[(o0 + q) * 256u] = relu ? __builtin_fmaxf(acc[q], 0.0f) : acc[q];
+            if (o0 + q < out) yout[(o0 + q) * 256u] = relu ? relu_ieee(acc[q]) : acc[q];
         }
     }
 }

@@ -78,6 +78,11 @@ __device__ __forceinline__ void poison_lds_all() {
 #endif
 
 // ---- device helpers ------------------------------------------------------------------------
+// Activations as torch computes them at every input, NaN and +-inf included ("Non-finite values"): IEEE maximum
+// (v_maximum_f32) keeps a NaN where fmaxf would drop it, and ReLU compares against 0, never against t * 0 (NaN at t = -inf).
+__device__ __forceinline__ float relu_ieee(float t) { return __builtin_elementwise_maximum(t, 0.0f); }
+__device__ __forceinline__ float relu_or_leaky(float t, bool leaky) { return __builtin_elementwise_maximum(t, leaky ? 0.01f * t : 0.0f); }
+
 __device__ __forceinline__ float expf_det(float x) {
     // branch-free: the polynomial runs on the clamped argument; scaling is ONE v_ldexp_f32, which also produces the
     // overflow (+inf from 89 -> k = 128) and underflow (0 from -104 -> k = -150) cases; NaN is selected at the end.

@@ -271,6 +271,49 @@ def test_mlp_matches_torch_linear(orc):
     np.testing.assert_allclose(y, h.numpy(), rtol=1e-5, atol=1e-5)
 
 
+@pytest.mark.parametrize("act", ["relu", "leaky"])
+def test_mlp_keeps_nan_and_infinities_like_torch(orc, act):
+    """Non-finite values through the oracle's MLP ("Non-finite values"): NaN / +inf / -inf in three input rows and a NaN in one
+    hidden weight give torch's NaN mask and torch's infinities; relu(NaN) is NaN and relu(-inf) is 0, as torch.relu."""
+    rng = np.random.default_rng(21)
+    ws = [rng.standard_normal(s).astype(np.float32) * 0.3 for s in ((24, 12), (24, 24), (5, 24))]
+    bs = [rng.standard_normal(s).astype(np.float32) * 0.1 for s in (24, 24, 5)]
+    ws[1][3, 4] = np.nan
+    bs[0][7] = -np.inf
+    x = rng.standard_normal((40, 12)).astype(np.float32)
+    x[2, 0], x[5, 1], x[9, 2] = np.nan, np.inf, -np.inf
+    y = orc.mlp_forward(orc.make_mlp(ws, bs, act, (), dim_in=12), x)
+    f = torch.relu if act == "relu" else (lambda t: torch.nn.functional.leaky_relu(t, 0.01))
+    h = torch.from_numpy(x).double()
+    for i, (w, b) in enumerate(zip(ws, bs)):
+        h = h @ torch.from_numpy(w).double().T + torch.from_numpy(b).double()
+        if i < 2:
+            h = f(h)
+    ref = h.numpy()
+    assert np.isnan(ref).all(axis=1).sum() >= 1
+    np.testing.assert_array_equal(np.isnan(y), np.isnan(ref))
+    np.testing.assert_array_equal(np.isinf(y), np.isinf(ref))
+    np.testing.assert_array_equal(y[np.isinf(ref)], ref[np.isinf(ref)])
+    fin = np.isfinite(ref)
+    np.testing.assert_allclose(y[fin], ref[fin], rtol=1e-5, atol=1e-5)
+
+
+def test_render_nan_view_weight_reaches_every_pixel(orc):
+    """A NaN in one hidden weight of view_mlp: every pixel of the oracle's image is NaN, depth and weights_sum are unchanged (the density path
+    does not see the view MLP)."""
+    from helpers import camera_rays, oracle_cfg, synthetic_params
+    steps = [128, 64, 32]
+    params = synthetic_params(steps, seed=3)
+    _, _, ro, rd = camera_rays(orc, 8, 8)
+    clean = orc.render(oracle_cfg(orc, params, steps), ro, rd)
+    pv = dict(params)
+    pv["view_mlp.net.1.weight"] = params["view_mlp.net.1.weight"].copy()
+    pv["view_mlp.net.1.weight"][4, 9] = np.nan
+    got = orc.render(oracle_cfg(orc, pv, steps), ro, rd)
+    assert np.isnan(got["image"]).all()
+    assert np.array_equal(got["depth"], clean["depth"]) and np.array_equal(got["weights_sum"], clean["weights_sum"])
+
+
 def test_sh_gradient_include_is_what_the_generator_emits(tmp_path, monkeypatch):
     """oracle/sh_grad.inc is generated (tools/gen_oracle_sh_grad.py: symbolic partials of the oracle's own SH polynomials); the
     committed file must be exactly what the generator produces from the committed oracle.c."""
