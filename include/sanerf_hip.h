@@ -191,6 +191,50 @@ int sn_rm_distort_loss(const float *bins, const float *weights, uint32_t N, uint
 int sn_rm_mask_nll(const float *logits, const int64_t *labels, uint32_t N, uint32_t K, float eps, float *loss_per_ray, float *grad_logits,
                    sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The object-field training extras of nerf/trainer.py (scripts/train_obj_nerf.sh: --ray_pair_rgb_loss_weight, --mixed_sampling,
+ * --error_map).  `masks` [.., K] holds softmax probabilities (from_logits = 0: the reference's own signature, un-clamped) or the logits
+ * themselves (from_logits != 0: the softmax runs inside and gradients are with respect to the logits).  No atomics anywhere: two calls on
+ * the same inputs give the same bits.  Limits: K <= 32, S <= 64, G * P < 2^31 (SN_ERR_UNSUPPORTED beyond them).
+ * ------------------------------------------------------------------------------------------ */
+
+/* Which pixels of each group the ray-pair loss compares against (trainer.py:268-276) without torch.multinomial and without a host round
+ * trip: incoherent [G,P] (the rays' error-map values), uniform [G,P] in [0,1) from the caller (one torch.rand per step, like sn_rm_jitter).
+ * Candidates of a group are its pixels with (1 - incoherent) > 0.8, or all its pixels if there is none; sample_index [G,S] int64 receives the S
+ * candidates with the smallest uniform value (lower index first on a tie) in ascending order of that value -- for 0/1 weights the
+ * exponential-race draw that multinomial(replacement=False) makes, so the same distribution.  A group with c < S candidates (the reference
+ * raises there) gets -1 in slots c..S-1. */
+int sn_rm_ray_pair_select(const float *incoherent, const float *uniform, uint32_t G, uint32_t P, uint32_t S, int64_t *sample_index,
+                          sn_stream_t stream);
+
+/* Ray-pair RGB loss (trainer.py:276-303) on rgb [G,P,3], masks [G,P,K], sample_index [G,S]: with q = masks[g, sample_index[g,s]] (detached;
+ * one-hot of its argmax unless use_pred_logistics) and sim_i = |rgb[g,i] - rgb[g,sample_index[g,s]]|_2 < thr,
+ *   loss_per_pair[g,s] = sum_i sim_i exp(-w cos(masks[g,i], q) - eps) / sum_i sim_i        (the reference's loss is its mean)
+ * and, in the same launch, grad_masks [G,P,K] = scale * (scale_dev ? *scale_dev : 1) / n_pairs * d sum(loss_per_pair) / d masks, written for
+ * every element (the caller does not clear it).  rgb gets no gradient (the comparison is boolean), q gets none (detached).  A slot whose
+ * index is -1 (or outside 0..P-1) is no pair: 0 in loss_per_pair, no gradient, not counted in n_pairs (no pairs at all: zero gradient).
+ * pair_count [1] or NULL receives max(n_pairs, 1) as a float, so that the mean is sum(loss_per_pair) / *pair_count without a pass over
+ * sample_index.  loss_per_pair / grad_masks: either may be NULL, not both.  thr > 0.  Cost to know: every group's workgroup counts the call's
+ * pairs itself (G * S index reads per group), so the work grows with G^2 S; meant for the few groups of a training step (the reference: 2-4),
+ * fine up to a few thousand. */
+int sn_rm_ray_pair_rgb_loss(const float *rgb, const float *masks, int from_logits, const int64_t *sample_index, uint32_t G, uint32_t P, uint32_t S,
+                            uint32_t K, float thr, float w, float eps, int use_pred_logistics, float scale, const float *scale_dev,
+                            float *loss_per_pair, float *pair_count, float *grad_masks, sn_stream_t stream);
+
+/* The error measure of the error map (trainer.py:1426-1432): error[n] = exp(-w cos(masks[n], onehot(labels[n])) - eps)
+ * = exp(-w p[label] / max(|p|, 1e-8) - eps); masks [N,K], labels [N] int64 (a label outside 0..K-1: the zero vector, exp(-eps)). */
+int sn_rm_mask_error(const float *masks, int from_logits, const int64_t *labels, uint32_t N, uint32_t K, float w, float eps, float *error,
+                     sn_stream_t stream);
+
+/* The per-step update of the error map (trainer.py:457-464), in place on error_map [map_rows, row_stride]:
+ *   error_map[rows[n], cols[n]] = 0.1 * error_map[rows[n], cols[n]] + 0.9 * error[n],   error as sn_rm_mask_error
+ * rows int64 [n_rows], n_rows = 1 (one image for all rays) or N; cols int64 [N].  Every new value is computed from the map as it was
+ * before the call (first launch, into stage [N], a scratch buffer of the caller) and written by a second launch; of several rays with the
+ * same target any one's value is kept, as with torch's indexed assignment.  Targets outside the map are skipped.  error [N] or NULL. */
+int sn_rm_error_map_update(const float *masks, int from_logits, const int64_t *labels, const int64_t *rows, uint32_t n_rows, const int64_t *cols,
+                           uint32_t N, uint32_t K, float w, float eps, uint32_t map_rows, uint32_t row_stride, float *error_map, float *stage,
+                           float *error, sn_stream_t stream);
+
 /* One stage's sample geometry (renderer.py:277-285): bins [N,T+1] in [0,1] -> real_bins [N,T+1] (distances along the
  * ray through the Mip-360 spacing of nears/fars [N]), rays_t [N,T] (mid-points), xyzs [N,T,3] (positions, contracted
  * into [-2,2]^3 like sn_rm_contract if `contract`).  Nothing here is differentiated by the reference. */

@@ -137,6 +137,10 @@ _SIGNATURES = {
     "sn_rm_profile_read": (_int, [_vp, _vp, _int]),
     "sn_rm_profile_shader_clock": (_int, [_vp, _vp]),
     "sn_rm_mask_nll": (_int, [_vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp]),
+    "sn_rm_ray_pair_select": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "sn_rm_ray_pair_rgb_loss": (_int, [_vp, _vp, _int, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _int, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "sn_rm_mask_error": (_int, [_vp, _int, _vp, _u32, _u32, _f32, _f32, _vp, _vp]),
+    "sn_rm_error_map_update": (_int, [_vp, _int, _vp, _vp, _u32, _vp, _u32, _u32, _f32, _f32, _u32, _u32, _vp, _vp, _vp, _vp]),
     "sn_rm_debug_occupancy": (_int, [_vp, _vp, _int]),
     "sn_rm_last_launch_info": (_int, [_vp]),
     "sn_debug_eval": (_int, [_int, _vp, _vp, _u32, _vp, _vp]),

@@ -458,6 +458,101 @@ def mask_nll(logits, labels, eps: float = 1e-6):
     return _mask_nll.apply(logits, labels, eps)
 
 
+def ray_pair_select(incoherent, S: int, uniform: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The pixels each group of the ray-pair loss compares against (nerf/trainer.py:268-276 without torch.multinomial, sn_rm_ray_pair_select):
+    incoherent [G,P] or [G,P,1] (the rays' error-map values), uniform [G,P] in [0,1) (drawn here with one torch.rand when None) -> int64
+    [G,S]: among a group's pixels with (1 - incoherent) > 0.8 (all its pixels when there is none) the S with the smallest uniform value, in
+    ascending order of it; -1 in the slots a group with fewer than S candidates cannot fill (the reference raises there)."""
+    G, P = incoherent.shape[0], incoherent.shape[1]
+    inc = incoherent.detach().reshape(G, P).contiguous().float()
+    if uniform is None:
+        uniform = torch.rand(G, P, device=inc.device, dtype=torch.float32)
+    u = uniform.detach().reshape(G, P).contiguous().float()
+    out = torch.empty(G, int(S), device=inc.device, dtype=torch.int64)
+    _lib.check(_lib.lib().sn_rm_ray_pair_select(_lib.dev(inc, "incoherent"), _lib.dev(u, "uniform"), G, P, int(S), _lib.dev(out, "sample_index", torch.int64),
+                                                _lib.stream()), "ray_pair_select")
+    return out
+
+
+class _ray_pair_rgb_loss(Function):
+    """nerf/trainer.py:276-303 as one kernel (sn_rm_ray_pair_rgb_loss): the scalar loss, and the gradient with respect to `masks` made in the
+    same launch and kept for backward (the mean's 1 / n_pairs inside it)."""
+
+    @staticmethod
+    def forward(ctx, rgb, masks, sample_index, threshold, exp_weight, epsilon, use_pred_logistics, from_logits):
+        m = masks.detach().contiguous().float()
+        G, P, K = m.shape
+        c = rgb.detach().reshape(G, P, 3).contiguous().float()
+        idx = sample_index.detach().reshape(G, -1).contiguous()
+        S = idx.shape[1]
+        per_pair = torch.empty(G, S, device=m.device, dtype=torch.float32)
+        grad = torch.empty_like(m) if ctx.needs_input_grad[1] else None
+        count = torch.empty(1, device=m.device, dtype=torch.float32)
+        _lib.check(_lib.lib().sn_rm_ray_pair_rgb_loss(_lib.dev(c, "rgb"), _lib.dev(m, "masks"), int(bool(from_logits)), _lib.dev(idx, "sample_index", torch.int64),
+                                                      G, P, S, K, float(threshold), float(exp_weight), float(epsilon), int(bool(use_pred_logistics)),
+                                                      1.0, None, _lib.dev(per_pair, "loss_per_pair"), _lib.dev(count, "pair_count"), _lib.dev(grad, "grad_masks"),
+                                                      _lib.stream()),
+                   "ray_pair_rgb_loss")
+        ctx.save_for_backward(grad)
+        ctx.mshape = masks.shape
+        return per_pair.sum() / count[0]                           # max(pairs, 1) as the kernel counted them; stays on the device
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (grad,) = ctx.saved_tensors
+        return None, (grad * grad_out).view(ctx.mshape), None, None, None, None, None, None
+
+
+def ray_pair_rgb_loss(rgb, masks, sample_index, threshold, exp_weight, epsilon, use_pred_logistics: bool = False, from_logits: bool = False):
+    """The ray-pair RGB loss of nerf/trainer.py:260-305 for given sample indices (ray_pair_select): rgb [G,P,3], masks [G,P,K] (softmax
+    probabilities, or the logits with from_logits=True: then the gradient reaches the logits without a softmax node), sample_index [G,S]
+    int64 (-1 = no pair) -> scalar: the mean over the pairs of sum_i sim exp(-exp_weight cos(masks_i, q) - epsilon) / sum_i sim.  rgb gets no
+    gradient (the colour comparison is boolean), nor does the sampled pixel's q (detached in the reference)."""
+    return _ray_pair_rgb_loss.apply(rgb, masks, sample_index, threshold, exp_weight, epsilon, use_pred_logistics, from_logits)
+
+
+def _mask_rows(masks, labels):
+    m = masks.detach().reshape(-1, masks.shape[-1]).contiguous().float()
+    lb = labels.detach().reshape(-1).contiguous().long()
+    if lb.shape[0] != m.shape[0]:
+        raise RuntimeError(f"{lb.shape[0]} labels for {m.shape[0]} mask rows")
+    return m, lb
+
+
+def mask_error(masks, labels, exp_weight, epsilon, from_logits: bool = False) -> torch.Tensor:
+    """The error measure of the error map (nerf/trainer.py:1426-1432, sn_rm_mask_error): masks [..., K] (probabilities, or logits with
+    from_logits=True), labels [...] -> [...] = exp(-exp_weight cos(masks, onehot(labels)) - epsilon).  No gradient."""
+    m, lb = _mask_rows(masks, labels)
+    N, K = m.shape
+    err = torch.empty(N, device=m.device, dtype=torch.float32)
+    _lib.check(_lib.lib().sn_rm_mask_error(_lib.dev(m, "masks"), int(bool(from_logits)), _lib.dev(lb, "labels", torch.int64), N, K, float(exp_weight),
+                                           float(epsilon), _lib.dev(err, "error"), _lib.stream()), "mask_error")
+    return err.view(masks.shape[:-1])
+
+
+def error_map_update(error_map, index, inds, masks, labels, exp_weight, epsilon, from_logits: bool = False) -> torch.Tensor:
+    """The per-step EMA of nerf/trainer.py:457-464, in place (sn_rm_error_map_update): error_map [M, S*S] float32 contiguous, index [1] or
+    [N] (the rays' images), inds [N] (their coarse cells), masks [N,K], labels [N]:
+    error_map[index, inds] = 0.1 * error_map[index, inds] + 0.9 * mask_error(masks, labels).  Every new value comes from the map as it was
+    before the call; rays that share a target leave one of their values.  Returns the rays' error [N].  No gradient."""
+    m, lb = _mask_rows(masks, labels)
+    N, K = m.shape
+    if error_map.dim() != 2:
+        raise RuntimeError("error_map must be [images, cells]")
+    rows = torch.as_tensor(index, device=m.device).detach().reshape(-1).contiguous().long()
+    cols = inds.detach().reshape(-1).contiguous().long()
+    if cols.shape[0] != N or rows.shape[0] not in (1, N):
+        raise RuntimeError(f"error_map_update: {rows.shape[0]} image indices / {cols.shape[0]} cells for {N} rays")
+    err = torch.empty(N, device=m.device, dtype=torch.float32)
+    stage = torch.empty(N, device=m.device, dtype=torch.float32)
+    _lib.check(_lib.lib().sn_rm_error_map_update(_lib.dev(m, "masks"), int(bool(from_logits)), _lib.dev(lb, "labels", torch.int64),
+                                                 _lib.dev(rows, "index", torch.int64), rows.shape[0], _lib.dev(cols, "inds", torch.int64), N, K,
+                                                 float(exp_weight), float(epsilon), error_map.shape[0], error_map.shape[1],
+                                                 _lib.dev(error_map, "error_map"), _lib.dev(stage, "stage"), _lib.dev(err, "error"), _lib.stream()),
+               "error_map_update")
+    return err
+
+
 class _composite(Function):
     """out[n,k] = sum_t w[n,t] * v[n,t,k]."""
 
