@@ -576,6 +576,38 @@ int sn_linear_wgrad(const float *x, const float *dy, uint32_t M, uint32_t K, uin
 int sn_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, uint64_t n, double lr, double beta1, double beta2,
                  double eps, double weight_decay, uint32_t step, const float *step_device, int maximize, int flags, sn_stream_t stream);
 
+/* The same update for MANY parameter tensors in ONE launch (an optimiser step of the whole model: 13 tensors in RGB mode).  The
+ * records travel to the kernel by value in its kernel arguments -- no host-to-device copy, nothing to synchronise, and a captured
+ * HIP graph keeps them -- so one call takes at most SN_ADAM_MULTI_MAX_TENSORS tensors in at most SN_ADAM_MULTI_MAX_GROUPS groups
+ * (more is an error: split the model into several calls).  Every tensor is cut into chunks of 4096 floats that the workgroups walk
+ * in a grid-stride loop; the arithmetic is sn_adam_step's, element for element (bit-identical results).
+ * Per tensor: the four streams and the element count (n = 0 is fine), the index of its group, and its OWN step count -- torch keeps
+ * one per parameter, and they diverge when a parameter has no gradient in a step: `step` (host, counts from 1), or `step_device`
+ * != NULL (a device float, read when the kernel RUNS; `step` is ignored).  Each device count belongs to one tensor of the call.
+ * Per group: the hyper-parameters as doubles, maximize, flags (SN_ADAM_ZERO_GRAD, SN_ADAM_LAZY as above).
+ * lr_scale_device != NULL: every group's rate is lr x (double)*lr_scale_device, read when the kernel runs (a learning-rate schedule
+ * that a captured graph follows); the step size is formed from it in double.
+ * ticket != NULL: the kernel ALSO advances the device step counts: a tensor with a device count is updated with count + 1, and the
+ * workgroup that finishes last stores the new counts.  `ticket` is a device word, zero before its first use and left zero by every
+ * call; nobody spins or waits on it.  ticket == NULL: the caller has advanced the counts beforehand, as for sn_adam_step.
+ * All arguments are checked on the host before anything touches the device. */
+#define SN_ADAM_MULTI_MAX_TENSORS 32
+#define SN_ADAM_MULTI_MAX_GROUPS 8
+typedef struct sn_adam_tensor {
+    float *param, *grad, *exp_avg, *exp_avg_sq;
+    uint64_t n;
+    float *step_device;       /* NULL: `step` holds the count */
+    uint32_t step;
+    uint32_t group;           /* index into the call's groups */
+} sn_adam_tensor;
+typedef struct sn_adam_group {
+    double lr, beta1, beta2, eps, weight_decay;
+    int32_t maximize;
+    int32_t flags;
+} sn_adam_group;
+int sn_adam_step_multi(const sn_adam_tensor *tensors, uint32_t n_tensors, const sn_adam_group *groups, uint32_t n_groups,
+                       const float *lr_scale_device, uint32_t *ticket, sn_stream_t stream);
+
 /* Measurement hook (bench.py): bracket every kernel sn_rm_render_rays launches with hipEvents on the
  * caller's stream.  Classes: 0 weight pack, 1..3 proposal stage k, 4 final stage.  profile_read
  * synchronises, returns summed device milliseconds and launch counts per class, and resets. */

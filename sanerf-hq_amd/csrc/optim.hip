@@ -72,6 +72,112 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
     }
 }
 
+// ---- many tensors, one launch (sn_adam_step_multi) ---------------------------------------------------------------------------
+// The records sit in the kernel arguments (2.8 KiB of the 4 KiB limit): eager steps hand over fresh gradient addresses every step
+// without a copy, a captured graph keeps them.  A chunk is 4096 floats = four 16-byte accesses per thread and stream; a workgroup
+// walks chunk ids blockIdx.x, blockIdx.x + gridDim.x, ... and finds the tensor of each by scanning the prefix of chunk counts
+// (ids only grow, so the scan never restarts; every value involved is uniform over the workgroup: scalar loads, no LDS).
+constexpr uint32_t MULTI_CHUNK = 4096;
+
+struct AdamMultiTensor {
+    float *p, *g, *m, *v;
+    uint64_t n;
+    float *step_dev;              // device count (capturable form) or NULL
+    double bc1;                   // host count: 1 - beta1^step, formed on the host as sn_adam_step forms it ...
+    float inv_bc2_sqrt;           // ... and 1 / sqrt(1 - beta2^step)
+    uint32_t group;
+};
+struct AdamMultiGroup {
+    double lr, beta1_d, beta2_d;
+    float one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay;
+    uint32_t bits;                // 1 zero_grad, 2 maximize, 4 lazy
+};
+struct AdamMultiArgs {
+    AdamMultiTensor t[SN_ADAM_MULTI_MAX_TENSORS];
+    AdamMultiGroup grp[SN_ADAM_MULTI_MAX_GROUPS];
+    uint32_t first_chunk[SN_ADAM_MULTI_MAX_TENSORS + 1];
+    uint32_t n_tensors;
+    const float *lr_scale;
+    uint32_t *ticket;
+};
+static_assert(sizeof(AdamMultiArgs) <= 4096, "the records must fit the kernel-argument block");
+static_assert(SN_ADAM_MULTI_MAX_TENSORS <= 64, "one wave stores the new step counts");
+
+__global__ __launch_bounds__(256) void k_adam_multi(const AdamMultiArgs a) {
+    SN_POISON_ALL();
+    const double lr_scale = a.lr_scale ? (double)*a.lr_scale : 1.0;
+    const uint32_t total = a.first_chunk[a.n_tensors];
+    uint32_t ti = 0, loaded = ~0u;
+    AdamArgs s;                                                              // the tensor at hand, in the form adam_one reads
+    for (uint32_t c = blockIdx.x; c < total; c += gridDim.x) {
+        while (c >= a.first_chunk[ti + 1]) ++ti;
+        if (ti != loaded) {
+            loaded = ti;
+            const AdamMultiTensor &t = a.t[ti];
+            const AdamMultiGroup &g = a.grp[t.group];
+            s.p = t.p; s.g = t.g; s.m = t.m; s.v = t.v; s.n = t.n;
+            s.one_minus_beta1 = g.one_minus_beta1; s.beta2 = g.beta2; s.one_minus_beta2 = g.one_minus_beta2; s.eps = g.eps; s.weight_decay = g.weight_decay;
+            s.zero_grad = g.bits & 1; s.maximize = (g.bits >> 1) & 1; s.lazy = (g.bits >> 2) & 1;
+            const double lr = a.lr_scale ? g.lr * lr_scale : g.lr;
+            double bc1 = t.bc1;
+            s.inv_bc2_sqrt = t.inv_bc2_sqrt;
+            if (t.step_dev) {                                                // as k_adam: both corrections from the device count, in double
+                const float count = *t.step_dev;
+                const double step = (double)(a.ticket ? count + 1.0f : count);
+                bc1 = 1.0 - pow(g.beta1_d, step);
+                s.inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow(g.beta2_d, step)));
+            }
+            s.step_size = (float)(lr / bc1);
+        }
+        const uint64_t nq = s.n >> 2;
+        const uint64_t q0 = (uint64_t)(c - a.first_chunk[ti]) * (MULTI_CHUNK / 4) + threadIdx.x;
+#pragma unroll
+        for (uint32_t k = 0; k < MULTI_CHUNK / 4 / 256; ++k) {
+            const uint64_t i = q0 + k * 256u;
+            if (i < nq) {
+                float4 p = reinterpret_cast<float4 *>(s.p)[i], m = reinterpret_cast<float4 *>(s.m)[i], v = reinterpret_cast<float4 *>(s.v)[i];
+                const float4 g = reinterpret_cast<const float4 *>(s.g)[i];
+                bool any = adam_one(p.x, g.x, m.x, v.x, s);
+                any |= adam_one(p.y, g.y, m.y, v.y, s);
+                any |= adam_one(p.z, g.z, m.z, v.z, s);
+                any |= adam_one(p.w, g.w, m.w, v.w, s);
+                if (any) {
+                    reinterpret_cast<float4 *>(s.p)[i] = p; reinterpret_cast<float4 *>(s.m)[i] = m; reinterpret_cast<float4 *>(s.v)[i] = v;
+                    if (s.zero_grad) reinterpret_cast<float4 *>(s.g)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                }
+            }
+        }
+        // the tensor's last chunk takes the n % 4 elements behind the last whole quad
+        const uint64_t e = (nq << 2) + threadIdx.x;
+        if (c + 1 == a.first_chunk[ti + 1] && e < s.n) {
+            float p = s.p[e], m = s.m[e], v = s.v[e];
+            if (adam_one(p, s.g[e], m, v, s)) {
+                s.p[e] = p; s.m[e] = m; s.v[e] = v;
+                if (s.zero_grad) s.g[e] = 0.0f;
+            }
+        }
+    }
+    // Advancing the device counts: nobody may store a new count while a workgroup can still read the old one.  Each workgroup takes
+    // one ticket after its last read (the barrier: all its waves are through the loop; the acq_rel add: this wave's own loads have
+    // returned before the add is issued).  The workgroup whose ticket is the last one knows every other is past its reads, stores
+    // count + 1 for each tensor and puts the ticket back to zero for the next launch.  Nobody waits for anybody.
+    if (a.ticket) {
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            uint32_t mine = 0;
+            if (threadIdx.x == 0) mine = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            mine = (uint32_t)__builtin_amdgcn_readfirstlane((int)mine);
+            if (mine == gridDim.x - 1) {
+                if (threadIdx.x < a.n_tensors) {
+                    float *count = a.t[threadIdx.x].step_dev;
+                    if (count) *count = *count + 1.0f;
+                }
+                if (threadIdx.x == 0) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
 }  // namespace sn
 
 using namespace sn;
@@ -104,5 +210,56 @@ extern "C" int sn_adam_step(float *param, float *grad, float *exp_avg, float *ex
     if (blocks == 0) blocks = 1;
     hipLaunchKernelGGL(k_adam, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, a);
     SN_LAUNCH_CHECK("k_adam");
+    return SN_OK;
+}
+
+extern "C" int sn_adam_step_multi(const sn_adam_tensor *tensors, uint32_t n_tensors, const sn_adam_group *groups, uint32_t n_groups,
+                                  const float *lr_scale_device, uint32_t *ticket, sn_stream_t stream) {
+    SN_REQUIRE(n_tensors <= SN_ADAM_MULTI_MAX_TENSORS, "adam_step_multi: %u tensors, at most %d per call (split the model into several calls)", n_tensors, SN_ADAM_MULTI_MAX_TENSORS);
+    SN_REQUIRE(n_groups <= SN_ADAM_MULTI_MAX_GROUPS, "adam_step_multi: %u groups, at most %d per call", n_groups, SN_ADAM_MULTI_MAX_GROUPS);
+    if (n_tensors == 0) return SN_OK;
+    SN_REQUIRE(tensors && groups && n_groups >= 1, "adam_step_multi: tensors and groups must be host arrays");
+    SN_REQUIRE((reinterpret_cast<uintptr_t>(lr_scale_device) & 3u) == 0 && (reinterpret_cast<uintptr_t>(ticket) & 3u) == 0, "adam_step_multi: lr_scale_device / ticket must be 4-byte aligned");
+    AdamMultiArgs a = {};
+    for (uint32_t j = 0; j < n_groups; ++j) {
+        const sn_adam_group &g = groups[j];
+        SN_REQUIRE(g.beta1 >= 0.0 && g.beta1 < 1.0 && g.beta2 >= 0.0 && g.beta2 < 1.0 && g.lr >= 0.0 && g.eps >= 0.0, "adam_step_multi: invalid hyper-parameters (group %u)", j);
+        SN_REQUIRE(!((g.flags & SN_ADAM_LAZY) && g.weight_decay != 0.0), "adam_step_multi: lazy mode is defined for weight_decay = 0 (a decayed zero gradient is not a skipped element)");
+        AdamMultiGroup &d = a.grp[j];
+        d.lr = g.lr; d.beta1_d = g.beta1; d.beta2_d = g.beta2;
+        d.one_minus_beta1 = (float)(1.0 - g.beta1); d.beta2 = (float)g.beta2; d.one_minus_beta2 = (float)(1.0 - g.beta2);
+        d.eps = (float)g.eps; d.weight_decay = (float)g.weight_decay;
+        d.bits = ((g.flags & SN_ADAM_ZERO_GRAD) ? 1u : 0u) | (g.maximize ? 2u : 0u) | ((g.flags & SN_ADAM_LAZY) ? 4u : 0u);
+    }
+    uint64_t chunks = 0;
+    for (uint32_t i = 0; i < n_tensors; ++i) {
+        const sn_adam_tensor &t = tensors[i];
+        SN_REQUIRE(t.group < n_groups, "adam_step_multi: tensor %u names group %u of %u", i, t.group, n_groups);
+        if (t.n) {
+            SN_REQUIRE(t.param && t.grad && t.exp_avg && t.exp_avg_sq, "adam_step_multi: param/grad/exp_avg/exp_avg_sq must be device pointers (tensor %u)", i);
+            SN_REQUIRE(table_aligned(t.param) && table_aligned(t.grad) && table_aligned(t.exp_avg) && table_aligned(t.exp_avg_sq), "adam_step_multi: tensors must be 16-byte aligned (tensor %u)", i);
+        }
+        SN_REQUIRE(t.step >= 1 || t.step_device, "adam_step_multi: step counts from 1 (tensor %u)", i);
+        SN_REQUIRE((reinterpret_cast<uintptr_t>(t.step_device) & 3u) == 0, "adam_step_multi: step_device must be 4-byte aligned (tensor %u)", i);
+        for (uint32_t k = 0; k < i && t.step_device; ++k)
+            SN_REQUIRE(tensors[k].step_device != t.step_device, "adam_step_multi: tensors %u and %u share one device step count", k, i);
+        const sn_adam_group &g = groups[t.group];
+        const double hstep = t.step_device ? 1.0 : (double)t.step;       // (device count: the kernel recomputes both corrections)
+        AdamMultiTensor &d = a.t[i];
+        d.p = t.param; d.g = t.grad; d.m = t.exp_avg; d.v = t.exp_avg_sq; d.n = t.n; d.step_dev = t.step_device; d.group = t.group;
+        d.bc1 = 1.0 - pow(g.beta1, hstep);
+        d.inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow(g.beta2, hstep)));
+        a.first_chunk[i] = (uint32_t)chunks;
+        chunks += (t.n + MULTI_CHUNK - 1) / MULTI_CHUNK;
+        SN_REQUIRE(chunks < (1ull << 31), "adam_step_multi: more than 2^43 elements in one call");
+    }
+    a.first_chunk[n_tensors] = (uint32_t)chunks;
+    a.n_tensors = n_tensors; a.lr_scale = lr_scale_device; a.ticket = ticket;
+    if (chunks == 0 && !ticket) return SN_OK;
+    uint64_t blocks = chunks;
+    if (blocks > 256u * 16u) blocks = 256u * 16u;                         // 16 workgroups per CU, grid-stride beyond
+    if (blocks == 0) blocks = 1;                                          // nothing to update, counts to advance
+    hipLaunchKernelGGL(k_adam_multi, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    SN_LAUNCH_CHECK("k_adam_multi");
     return SN_OK;
 }

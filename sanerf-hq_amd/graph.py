@@ -7,7 +7,8 @@ step (host copies of offsets / aabb are memoised, the fp16 range guard only re-e
 cached tensors, every kernel goes to torch's current stream, the binned grid backward has static grids, and
 `sanerf_hq_amd.optim.Adam(capturable=True)` keeps its step count on the device.  `GraphedStep` captures `fn()` once and replays it.
 
-    opt = Adam(params, lr=..., eps=1e-15, capturable=True)
+    opt = Adam(params, lr=..., eps=1e-15, capturable=True, multi_tensor=True)     # one launch for all parameter tensors, counts advanced in-kernel
+    sched = DeviceLRScale(opt, lambda it: 0.1 ** min(it / iters, 1))              # the reference's LambdaLR (main.py:298-303), factor on the device
     def step():
         opt.zero_grad(set_to_none=True)
         out = model.render(rays_o, rays_d, ...)          # rays_o / rays_d / targets: STATIC tensors, refilled with .copy_() between replays
@@ -18,6 +19,9 @@ cached tensors, every kernel goes to torch's current stream, the binned grid bac
     for batch in loader:
         rays_o.copy_(batch.rays_o); ...
         loss = g()                                        # one graph launch; `loss` is the same tensor object every time
+        sched.step()                                      # the next replay reads the new factor: a captured step follows the schedule
+
+(The per-tensor route, `multi_tensor=False`, takes its rate as a host number: a captured step keeps the rate it was captured with.)
 
 Random numbers drawn inside the step (perturb=True: torch.rand) advance correctly under replay (torch registers the generator with the
 graph).  Anything that changes the step's SHAPE (number of rays, which parameters require gradients, update_proposal on / off) needs its

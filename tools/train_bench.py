@@ -6,7 +6,12 @@
         error-map EMA), two routes in one run: the extras as the reference's torch lines (trainer.py:260-305, 434-464) and as the HIP operators
         (nerf.mask_step.mask_train_loss).  `mask_extras_torch K` / `mask_extras_ops K` run K eager steps of one route and nothing else: for a
         kernel trace of its own (launches per step = the difference of two such runs' dispatch counts / the difference of their K)
-usage: train_bench.py [rgb|mask|both|mask_extras]  -> one JSON line.  Eager forward+backward, + single-pass Adam, the step as a HIP graph, and (rgb) the
+  rgb_multi / mask_multi  the same two steps with optim.Adam(multi_tensor=True): one sn_adam_step_multi launch for all parameter tensors
+  adam_ab [PAIRS]  both steps "with Adam", eager and as a HIP graph, the per-tensor and the multi-tensor route alternating PAIRS (3) times in
+        this one process: the spread between the per-tensor runs is the yardstick for the difference between the routes
+  rgb_steps / mask_steps K per_tensor|multi_tensor [capturable]  K eager steps of one route and nothing else, for a kernel trace of its own
+        (launches per step = the difference of two such runs' dispatch counts / the difference of their K)
+usage: train_bench.py [rgb|mask|both|mask_extras|...]  -> one JSON line.  Eager forward+backward, + single-pass Adam, the step as a HIP graph, and (rgb) the
 step without proposal update (4 of 5 steps after step 3000, trainer.py:372-373)."""
 import json
 import os
@@ -37,7 +42,7 @@ def rays():
     return roF[pix].contiguous(), rdF[pix].contiguous()
 
 
-def rgb():
+def rgb_setup(multi=False):
     ro, rd = rays()
     opt = make_opt()
     opt.lambda_proposal, opt.lambda_distort = 1.0, 0.0
@@ -45,7 +50,8 @@ def rgb():
     model.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic_params([128, 64, 32], seed=1).items()}, strict=False)
     model = model.to(dev).train()
     gt = torch.from_numpy(synth.hash_uniform((N, 3), 42, 0.0, 1.0)).to(dev)
-    box = {"optim": HipAdam(model.get_params(1e-2), eps=1e-15), "upd": True}
+    new_optim = lambda capturable=False, multi=multi: HipAdam(model.get_params(1e-2), eps=1e-15, capturable=capturable, multi_tensor=multi)   # noqa: E731
+    box = {"optim": new_optim(), "upd": True}
 
     def fwd_bwd():
         box["optim"].zero_grad(set_to_none=True)
@@ -58,13 +64,18 @@ def rgb():
     def step():
         fwd_bwd()
         box["optim"].step()
+    return box, fwd_bwd, step, new_optim
+
+
+def rgb(multi=False):
+    box, fwd_bwd, step, new_optim = rgb_setup(multi)
     out = {"fwd_bwd_ms": round(best(fwd_bwd) * 1e3, 3), "step_ms": round(best(step) * 1e3, 3)}
     box["upd"] = False
     out["fwd_bwd_without_proposal_update_ms"] = round(best(fwd_bwd) * 1e3, 3)
     out["step_without_proposal_update_ms"] = round(best(step) * 1e3, 3)
     for upd, key in ((True, "step_as_hip_graph_ms"), (False, "step_without_proposal_update_as_hip_graph_ms")):
         box["upd"] = upd
-        box["optim"] = HipAdam(model.get_params(1e-2), eps=1e-15, capturable=True)
+        box["optim"] = new_optim(True)
         try:
             g = GraphedStep(step, warmup=3)
             out[key] = round(best(g) * 1e3, 3)
@@ -74,7 +85,7 @@ def rgb():
     return out
 
 
-def mask():
+def mask_setup(multi=False):
     ro, rd = rays()
     opt = make_opt(with_mask=True)
     model = NeRFNetwork(opt)
@@ -84,8 +95,8 @@ def mask():
         p.requires_grad_(n_.startswith("m_grid") or n_.startswith("mask_mlp"))
     labels = torch.from_numpy((synth.hash_u01(N, 100) < 0.5).astype(np.int64)).to(dev)
     train = [p for p in model.parameters() if p.requires_grad]
-    box = {"optim": HipAdam(train, lr=1e-3, eps=1e-15)}
-    ops.WGRAD_SIDE_STREAM = True
+    new_optim = lambda capturable=False, multi=multi: HipAdam(train, lr=1e-3, eps=1e-15, capturable=capturable, multi_tensor=multi)   # noqa: E731
+    box = {"optim": new_optim()}
 
     def fwd_bwd():
         box["optim"].zero_grad(set_to_none=True)
@@ -95,8 +106,14 @@ def mask():
     def step():
         fwd_bwd()
         box["optim"].step()
+    return box, fwd_bwd, step, new_optim
+
+
+def mask(multi=False):
+    box, fwd_bwd, step, new_optim = mask_setup(multi)
+    ops.WGRAD_SIDE_STREAM = True
     out = {"fwd_bwd_ms": round(best(fwd_bwd) * 1e3, 3), "step_ms": round(best(step) * 1e3, 3)}
-    box["optim"] = HipAdam(train, lr=1e-3, eps=1e-15, capturable=True)
+    box["optim"] = new_optim(True)
     try:
         g = GraphedStep(step, warmup=3)
         out["step_as_hip_graph_ms"] = round(best(g) * 1e3, 3)
@@ -105,6 +122,40 @@ def mask():
         out["step_as_hip_graph_ms"] = f"failed: {type(e).__name__}: {e}"
     ops.WGRAD_SIDE_STREAM = False
     return out
+
+
+def adam_ab(setup, pairs=3, side_stream=False):
+    """The step with Adam, eager and as a HIP graph: per-tensor and multi-tensor route in turn, `pairs` times, same model and process."""
+    box, _, step, new_optim = setup()
+    ops.WGRAD_SIDE_STREAM = side_stream
+    out = {"eager_step_ms": [], "step_as_hip_graph_ms": []}
+    for _ in range(pairs):
+        eager, graph = {}, {}
+        for name, multi in (("per_tensor", False), ("multi_tensor", True)):
+            box["optim"] = new_optim(False, multi)
+            eager[name] = round(best(step) * 1e3, 3)
+            box["optim"] = new_optim(True, multi)
+            try:
+                g = GraphedStep(step, warmup=3)
+                graph[name] = round(best(g) * 1e3, 3)
+                del g
+            except Exception as e:   # noqa: BLE001
+                graph[name] = f"failed: {type(e).__name__}: {e}"
+        out["eager_step_ms"].append(eager)
+        out["step_as_hip_graph_ms"].append(graph)
+    ops.WGRAD_SIDE_STREAM = False
+    return out
+
+
+def eager_steps(setup, k, multi, capturable, side_stream=False):
+    box, _, step, new_optim = setup()
+    ops.WGRAD_SIDE_STREAM = side_stream
+    box["optim"] = new_optim(capturable, multi)
+    for _ in range(k):
+        step()
+    torch.cuda.synchronize()
+    ops.WGRAD_SIDE_STREAM = False
+    return {"eager_steps_run": k, "multi_tensor": multi, "capturable": capturable}
 
 
 def torch_extras_loss(o, data, opt, error_map):
@@ -203,6 +254,17 @@ if __name__ == "__main__":
         res["rgb_training_step_4096_rays"] = rgb()
     if which in ("mask", "both"):
         res["c5_mask_training_step_4096_rays"] = mask()
+    if which == "rgb_multi":
+        res["rgb_training_step_4096_rays_multi_tensor_adam"] = rgb(multi=True)
+    if which == "mask_multi":
+        res["c5_mask_training_step_4096_rays_multi_tensor_adam"] = mask(multi=True)
+    if which == "adam_ab":
+        pairs = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+        res["rgb_training_step_4096_rays"] = adam_ab(rgb_setup, pairs)
+        res["c5_mask_training_step_4096_rays"] = adam_ab(mask_setup, pairs, side_stream=True)
+    if which in ("rgb_steps", "mask_steps"):
+        res[which] = eager_steps(rgb_setup if which == "rgb_steps" else mask_setup, int(sys.argv[2]), sys.argv[3] == "multi_tensor",
+                                 "capturable" in sys.argv[4:], side_stream=which == "mask_steps")
     if which == "mask_extras":
         res["mask_step_with_ray_pair_loss_and_error_map_4096_plus_256_rays"] = mask_extras()
     if which in ("mask_extras_torch", "mask_extras_ops"):
