@@ -235,6 +235,70 @@ int sn_rm_error_map_update(const float *masks, int from_logits, const int64_t *l
                            uint32_t N, uint32_t K, float w, float eps, uint32_t map_rows, uint32_t row_stride, float *error_map, float *stage,
                            float *error, sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The mask field's output stage and the device-side evaluation meters: everything the reference does between
+ * `instance_mask_logits` and what a user sees (test_step) or scores (eval_step, nerf/metrics.py).  Streaming kernels, one launch per
+ * image each, nothing synchronises, no float atomics, two calls on the same inputs give the same bits (the accumulators included).
+ * Limits: K <= 32, C <= 32 classes for the meters, N < 2^31 (SN_ERR_UNSUPPORTED beyond them).  N = 0 returns SN_OK and does nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_MASK_MAX_CLASSES 32
+enum { SN_MASK_OUT_NONE = 0, SN_MASK_OUT_HEATMAP = 1, SN_MASK_OUT_COMPOSITION = 2, SN_MASK_OUT_MASK = 3 };
+
+/* test_step's mask branch (nerf/trainer.py:730-777), the overlays it calls (nerf/utils.py:49-60 overlay_mask_composition, :63-77
+ * overlay_mask_heatmap) and the host-side (x * 255).astype(np.uint8) of trainer.py:726-727 / 780-781, in one launch:
+ *   p = softmax(logits[n, :]) (K = 1: sigmoid, trainer.py:734-739);  conf, id = max, argmax of p (the lowest index on a tie, a NaN as the
+ *   greatest value: torch's rules; K = 1: id = 0, conf = p);
+ *   mode HEATMAP      rgb = color_map[id] * conf, or color_map[render_id] * p[render_id] when 0 <= render_id < K
+ *   mode COMPOSITION  rgb = image * alpha + (render_id == -1 || id == render_id ? color_map[id] : image) * (1 - alpha)
+ *   mode MASK         rgb = image * m + (1 - m) * bg,  m = (id == render_id)
+ *   mode NONE         rgb = image                       (the plain render's 8-bit image)
+ *   rgb8 = trunc(clamp(255 * rgb, 0, 255)), NaN -> 0.  On [0,1] that is the reference's astype(np.uint8); outside [0,1] the reference's
+ *   cast wraps modulo 256 (and is undefined for NaN) where this one saturates.
+ * logits [N,K] f32; image: rows of image_stride >= 3 floats (3: a packed [N,3] image; 5: the [N,5] rgb|depth|weights_sum render buffer
+ * read in place), may be NULL for HEATMAP; color_map [C,3] f32 on the device with C >= K (an id >= C cannot occur then), read by
+ * HEATMAP and COMPOSITION; bg: 3 floats on the device, read by MASK.  Outputs, each may be NULL (at least one is given): probs [N,K],
+ * instance_id [N] int64, confidence [N], rgb [N,3] f32, rgb8 [N,3] uint8 (4-byte aligned: the 3-byte pixels are staged in LDS and
+ * stored as dwords).  A NULL output is not touched. */
+int sn_rm_mask_output(const float *logits, uint32_t N, uint32_t K, const float *image, uint32_t image_stride, const float *color_map, uint32_t C,
+                      int mode, int render_id, float alpha, const float *bg, float *probs, int64_t *instance_id, float *confidence, float *rgb,
+                      uint8_t *rgb8, sn_stream_t stream);
+
+/* The evaluation record of a validation epoch, on the device, 8-byte aligned, zeroed by the caller before the first image.  The
+ * reference's meters keep V (a running sum of per-image values) and N (images); so does this record, for all four of them. */
+typedef struct sn_eval_record {
+    double nll_mean_sum;   /* sum over images of eval_step's loss (trainer.py:1603-1604 total_loss += loss.item()) */
+    double miou_sum;       /* MeanIoUMeter.V */
+    double mse_sum;        /* MSEMeter.V */
+    double psnr_sum;       /* PSNRMeter.V */
+    uint64_t images;       /* images seen by sn_rm_mask_eval_accumulate */
+    uint64_t rgb_images;   /* images seen by sn_rm_image_sqerr_accumulate */
+    uint64_t inter[SN_MASK_MAX_CLASSES], pred[SN_MASK_MAX_CLASSES], truth[SN_MASK_MAX_CLASSES];   /* the LAST image's class counts, for inspection */
+} sn_eval_record;
+
+/* Scratch of the two accumulating entry points: SN_MASK_EVAL_WORKSPACE_BYTES on the device, 8-byte aligned, zeroed ONCE by the caller;
+ * every launch leaves it zeroed again.  Launches that share a workspace must be ordered (one stream). */
+#define SN_MASK_EVAL_WORKSPACE_BYTES 8192
+
+/* eval_step's mask branch (trainer.py:599-627: softmax / sigmoid, clamp, NLL over the labelled pixels, its `labeled.sum() > 0` host branch
+ * as a device-side select) + evaluate_one_epoch's loss.item() (:1603-1604) + MeanIoUMeter.update (nerf/metrics.py:165-179), one launch:
+ *   nll_mean_sum += sum_n nll[n] / #{labels[n] != -1}   (0 when no pixel is labelled), nll[n] = -log(clamp(p[n, labels[n]], eps, 1 - eps))
+ *                   per pixel as sn_rm_mask_nll defines it (a label outside 0..K-1: 0), p as in sn_rm_mask_output, summed in double in a fixed order;
+ *   miou_sum     += mean over the classes i < C with union_i > 0 of inter_i / union_i (double), on (argmax id, label): pred_i = #{id = i},
+ *                   truth_i = #{label = i}, inter_i = #{id = label = i}, union_i = pred_i + truth_i - inter_i.  A label outside 0..C-1 (-1:
+ *                   unlabelled) matches no class, but its pixel still counts in the union of its predicted class, as np.logical_or does.
+ *                   Stated difference: the reference hands its meter the float probabilities, which the meter's astype(int64) turns into
+ *                   zeros; here the meter gets the ids.
+ *   images       += 1;  inter / pred / truth = this image's counts.
+ * logits [N,K] f32, labels [N] int64, K <= C <= 32. */
+int sn_rm_mask_eval_accumulate(const float *logits, const int64_t *labels, uint32_t N, uint32_t K, uint32_t C, float eps, sn_eval_record *record,
+                               void *workspace, sn_stream_t stream);
+
+/* MSEMeter.update and PSNRMeter.update (nerf/metrics.py:217-221, 28-38) for one image: pred, truth: N rows of >= 3 floats (row strides in
+ * floats: 3 = packed, 5 = the render buffer).  The difference is taken in fp32, squared and summed in double in a fixed order:
+ *   mse = sum / (3 N);  mse_sum += mse;  psnr_sum += -10 log10(mse);  rgb_images += 1. */
+int sn_rm_image_sqerr_accumulate(const float *pred, uint32_t pred_stride, const float *truth, uint32_t truth_stride, uint32_t N,
+                                 sn_eval_record *record, void *workspace, sn_stream_t stream);
+
 /* One stage's sample geometry (renderer.py:277-285): bins [N,T+1] in [0,1] -> real_bins [N,T+1] (distances along the
  * ray through the Mip-360 spacing of nears/fars [N]), rays_t [N,T] (mid-points), xyzs [N,T,3] (positions, contracted
  * into [-2,2]^3 like sn_rm_contract if `contract`).  Nothing here is differentiated by the reference. */

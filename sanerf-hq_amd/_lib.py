@@ -39,6 +39,8 @@ EXP_NONE, EXP_ROLE_SPLIT, EXP_LDS_LEVEL0, EXP_FINAL_ONE_WG = 0, 1, 2, 3         
 BUILD_EXPERIMENTS, BUILD_POISON_LDS = 1, 2                           # sn_build_flags()
 ADAM_ZERO_GRAD, ADAM_LAZY = 1, 2                                     # sn_adam_step flags
 ADAM_MULTI_MAX_TENSORS, ADAM_MULTI_MAX_GROUPS = 32, 8                # sn_adam_step_multi: per call
+MASK_MAX_CLASSES, MASK_EVAL_WORKSPACE_BYTES = 32, 8192               # sn_rm_mask_output / sn_rm_mask_eval_accumulate
+MASK_OUT_MODES = {"none": 0, "heatmap": 1, "composition": 2, "mask": 3}
 
 
 class AdamTensor(C.Structure):
@@ -49,6 +51,13 @@ class AdamTensor(C.Structure):
 class AdamGroup(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("maximize", C.c_int32), ("flags", C.c_int32)]
+
+
+class EvalRecord(C.Structure):
+    """sn_eval_record: what the device-side meters have accumulated (raymarching.mask_eval_accumulate / image_sqerr_accumulate)."""
+    _fields_ = [("nll_mean_sum", C.c_double), ("miou_sum", C.c_double), ("mse_sum", C.c_double), ("psnr_sum", C.c_double),
+                ("images", C.c_uint64), ("rgb_images", C.c_uint64), ("inter", C.c_uint64 * MASK_MAX_CLASSES),
+                ("pred", C.c_uint64 * MASK_MAX_CLASSES), ("truth", C.c_uint64 * MASK_MAX_CLASSES)]
 
 
 class RenderTuning(C.Structure):
@@ -153,6 +162,9 @@ _SIGNATURES = {
     "sn_rm_ray_pair_rgb_loss": (_int, [_vp, _vp, _int, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _int, _f32, _vp, _vp, _vp, _vp, _vp]),
     "sn_rm_mask_error": (_int, [_vp, _int, _vp, _u32, _u32, _f32, _f32, _vp, _vp]),
     "sn_rm_error_map_update": (_int, [_vp, _int, _vp, _vp, _u32, _vp, _u32, _u32, _f32, _f32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "sn_rm_mask_output": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _u32, _int, _int, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sn_rm_mask_eval_accumulate": (_int, [_vp, _vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp]),
+    "sn_rm_image_sqerr_accumulate": (_int, [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "sn_rm_debug_occupancy": (_int, [_vp, _vp, _int]),
     "sn_rm_last_launch_info": (_int, [_vp]),
     "sn_debug_eval": (_int, [_int, _vp, _vp, _u32, _vp, _vp]),

@@ -553,6 +553,148 @@ def error_map_update(error_map, index, inds, masks, labels, exp_weight, epsilon,
     return err
 
 
+def _image_rows(t, name, N):
+    """An [N, >=3] float32 image whose rows are `stride` floats apart (the packed [N,5] render buffer's image columns are read in place)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor")
+    t = t.detach()
+    if t.dim() != 2:
+        t = t.reshape(-1, t.shape[-1])
+    if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < 3 or t.shape[1] < 3:
+        t = t[:, :3].float().contiguous()
+    if t.shape[0] != N:
+        raise RuntimeError(f"{name}: {t.shape[0]} rows for {N} pixels")
+    return t, t.data_ptr(), t.stride(0)
+
+
+def mask_output(logits, color_map=None, image=None, mode: str = "none", render_id: int = -1, alpha: float = 0.7, bg_color=None,
+                want: Sequence[str] = ("probs", "instance_id", "confidence", "rgb", "rgb8"), out: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+    """The mask field's output stage in one launch (sn_rm_mask_output; nerf/trainer.py:730-781 + nerf/utils.py:49-77): logits [..., K],
+    K <= 32 (K = 1: sigmoid) -> the tensors named in `want`: probs [..., K], instance_id [...] int64 (argmax, lowest index on a tie),
+    confidence [...] (max probability), rgb [..., 3] float32 and rgb8 [..., 3] uint8 = trunc(clamp(255 rgb, 0, 255)).
+    mode: 'heatmap' (color_map[id] * confidence, or color_map[render_id] * p[render_id] for 0 <= render_id < K), 'composition'
+    (image * alpha + (render_id == -1 or id == render_id ? color_map[id] : image) * (1 - alpha)), 'mask' (image where id == render_id,
+    bg_color elsewhere) or 'none' (rgb = image).  image: [..., 3] float32, rows may be strided (a view of the packed [N,5] render buffer);
+    color_map [C,3] with C >= K; bg_color: a number or 3 values (tensor: on the device, nothing is read on the host).
+    out: a dict of preallocated tensors to write into (a captured graph keeps its outputs); a wanted output that is missing from it is
+    allocated and added, one of the wrong shape, dtype or device raises.  No gradient."""
+    if mode not in _lib.MASK_OUT_MODES:
+        raise ValueError(f"mask_output: mode {mode!r}, one of {sorted(_lib.MASK_OUT_MODES)}")
+    unknown = set(want) - {"probs", "instance_id", "confidence", "rgb", "rgb8"}
+    if unknown:
+        raise ValueError(f"mask_output: unknown outputs {sorted(unknown)}")
+    K = logits.shape[-1]
+    lead = logits.shape[:-1]
+    lg = logits.detach().reshape(-1, K).contiguous().float()
+    N = lg.shape[0]
+    lg_ptr = _lib.dev(lg, "logits")
+    dev = lg.device
+    colour = "rgb" in want or "rgb8" in want
+    img_ptr, img_stride, cm_ptr, n_colors, bg_ptr, keep = None, 0, None, 0, None, []
+    if colour:
+        if mode != "heatmap":
+            if image is None:
+                raise RuntimeError(f"mask_output: mode {mode!r} needs the rendered image")
+            img, img_ptr, img_stride = _image_rows(image, "image", N)
+            keep.append(img)
+        if mode in ("heatmap", "composition"):
+            if color_map is None:
+                raise RuntimeError(f"mask_output: mode {mode!r} needs a color_map")
+            cm = color_map.detach().reshape(-1, 3).contiguous().float()
+            cm_ptr, n_colors = _lib.dev(cm, "color_map"), cm.shape[0]
+            keep.append(cm)
+        if mode == "mask":
+            if bg_color is None:
+                raise RuntimeError("mask_output: mode 'mask' needs bg_color (trainer.py:777)")
+            if torch.is_tensor(bg_color):
+                bg = bg_color.detach().to(device=dev, dtype=torch.float32).reshape(-1)
+                if bg.numel() not in (1, 3):
+                    raise RuntimeError(f"mask_output: bg_color has {bg.numel()} values (1 or 3; a per-ray background is not built)")
+                bg = bg.expand(3).contiguous()
+            else:
+                vals = [float(v) for v in (bg_color if isinstance(bg_color, (list, tuple)) else [bg_color] * 3)]
+                if len(vals) != 3:
+                    raise RuntimeError(f"mask_output: bg_color has {len(vals)} values (a number or 3)")
+                bg = torch.empty(3, device=dev, dtype=torch.float32)
+                for j, v in enumerate(vals):                         # fills, not a host-to-device copy: they can be captured
+                    bg[j:j + 1].fill_(v)
+            bg_ptr = _lib.dev(bg, "bg_color")
+            keep.append(bg)
+    shapes = {"probs": ((*lead, K), torch.float32), "instance_id": (tuple(lead), torch.int64), "confidence": (tuple(lead), torch.float32),
+              "rgb": ((*lead, 3), torch.float32), "rgb8": ((*lead, 3), torch.uint8)}
+    res, ptr = {} if out is None else out, {}
+    for name, (shape, dtype) in shapes.items():
+        if name not in want:
+            ptr[name] = None
+            continue
+        t = res.get(name)
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dtype)
+            res[name] = t
+        elif tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+            raise RuntimeError(f"mask_output: out[{name!r}] must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, "
+                               f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        ptr[name] = _lib.dev(t, name, dtype)
+    _lib.check(_lib.lib().sn_rm_mask_output(lg_ptr, N, K, img_ptr, img_stride, cm_ptr, n_colors, _lib.MASK_OUT_MODES[mode], int(render_id), float(alpha), bg_ptr,
+                                            ptr["probs"], ptr["instance_id"], ptr["confidence"], ptr["rgb"], ptr["rgb8"], _lib.stream()), "mask_output")
+    return res
+
+
+EVAL_RECORD_BYTES = C.sizeof(_lib.EvalRecord)
+
+
+def eval_record(device) -> torch.Tensor:
+    """A zeroed sn_eval_record on the device (as int64 words; read it with `read_eval_record`)."""
+    return torch.zeros(EVAL_RECORD_BYTES // 8, device=device, dtype=torch.int64)
+
+
+def eval_workspace(device) -> torch.Tensor:
+    """The zero-at-rest scratch of mask_eval_accumulate / image_sqerr_accumulate (one per stream)."""
+    return torch.zeros(_lib.MASK_EVAL_WORKSPACE_BYTES // 8, device=device, dtype=torch.int64)
+
+
+def read_eval_record(record: torch.Tensor) -> dict:
+    """The record's fields on the host (this is the host read: it synchronises)."""
+    raw = record.detach().cpu().numpy().tobytes()
+    r = _lib.EvalRecord.from_buffer_copy(raw)
+    return {"nll_mean_sum": r.nll_mean_sum, "miou_sum": r.miou_sum, "mse_sum": r.mse_sum, "psnr_sum": r.psnr_sum, "images": int(r.images),
+            "rgb_images": int(r.rgb_images), "inter": np.array(r.inter[:], dtype=np.uint64), "pred": np.array(r.pred[:], dtype=np.uint64),
+            "truth": np.array(r.truth[:], dtype=np.uint64)}
+
+
+def _record_ptrs(record, workspace):
+    if record.dtype != torch.int64 or record.numel() * 8 < EVAL_RECORD_BYTES:
+        raise RuntimeError("record must come from raymarching.eval_record()")
+    if workspace.dtype != torch.int64 or workspace.numel() * 8 < _lib.MASK_EVAL_WORKSPACE_BYTES:
+        raise RuntimeError("workspace must come from raymarching.eval_workspace()")
+    return _lib.dev(record, "record", torch.int64), _lib.dev(workspace, "workspace", torch.int64)
+
+
+def mask_eval_accumulate(logits, labels, record: torch.Tensor, workspace: torch.Tensor, eps: float = 1e-6, num_classes: Optional[int] = None) -> None:
+    """eval_step's mask branch + the loss and mIoU meters for one image, in one launch and without a host read (sn_rm_mask_eval_accumulate;
+    nerf/trainer.py:599-627, 1603-1604, nerf/metrics.py:165-179): logits [..., K], labels [...] (-1: unlabelled) -> `record` gets the image's
+    mean NLL over its labelled pixels (0 when there is none) and its mean IoU of (argmax id, label) over num_classes >= K classes
+    (default K) added, and its class counts stored."""
+    m, lb = _mask_rows(logits, labels)
+    N, K = m.shape
+    m_ptr, lb_ptr = _lib.dev(m, "logits"), _lib.dev(lb, "labels", torch.int64)
+    rec, ws = _record_ptrs(record, workspace)
+    _lib.check(_lib.lib().sn_rm_mask_eval_accumulate(m_ptr, lb_ptr, N, K, int(K if num_classes is None else num_classes), float(eps), rec, ws, _lib.stream()),
+               "mask_eval_accumulate")
+
+
+def image_sqerr_accumulate(pred, truth, record: torch.Tensor, workspace: torch.Tensor) -> None:
+    """MSEMeter.update and PSNRMeter.update for one image without a host read (sn_rm_image_sqerr_accumulate; nerf/metrics.py:28-38, 217-221):
+    pred, truth [..., 3] float32 (rows may be strided) -> `record` gets mean((pred - truth)^2) and -10 log10 of it added."""
+    if not pred.is_cuda or not truth.is_cuda:
+        raise RuntimeError("pred / truth must be a CUDA tensor")
+    N = pred.numel() // pred.shape[-1] if pred.dim() != 2 else pred.shape[0]
+    p, p_ptr, p_stride = _image_rows(pred, "pred", N)
+    t, t_ptr, t_stride = _image_rows(truth, "truth", N)
+    rec, ws = _record_ptrs(record, workspace)
+    _lib.check(_lib.lib().sn_rm_image_sqerr_accumulate(p_ptr, p_stride, t_ptr, t_stride, N, rec, ws, _lib.stream()), "image_sqerr_accumulate")
+
+
 class _composite(Function):
     """out[n,k] = sum_t w[n,t] * v[n,t,k]."""
 
