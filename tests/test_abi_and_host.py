@@ -115,6 +115,22 @@ def test_invalid_arguments_return_error_codes_not_exceptions():
     assert l.sn_freq_encode_forward(dummy, 4, 3, 4, 26, dummy, None) == -1
 
 
+def test_binned_backward_refuses_a_row_stride_with_the_lbc_layout():
+    """grad_row_stride describes rows of a wider [B, *] tensor: with the [L,B,C] layout there is no such row, and the call says so before
+    any launch (with the default stride 0 the same arguments pass this check and fail on the NULL workspace)."""
+    from sanerf_hq_amd import _lib
+    l = _lib.lib()
+    offs = _lib.host_i32([0, 8, 16])
+    dummy = ctypes.c_void_p(16)
+    args = (dummy, offs, dummy, 4, 3, 2, 2, 2, 0.5, 16, 0, 0, 0)
+    assert l.sn_grid_encode_backward_binned_rows(dummy, 4, *args, _lib.LAYOUT_LBC, dummy, 1 << 20, None) == -1
+    assert b"needs the [B, L*C] layout" in l.sn_last_error()
+    assert l.sn_grid_encode_backward_binned_rows(dummy, 3, *args, _lib.LAYOUT_BLC, dummy, 1 << 20, None) == -1      # shorter than L*C
+    assert b"needs the [B, L*C] layout and >= L*C = 4" in l.sn_last_error()
+    assert l.sn_grid_encode_backward_binned_rows(dummy, 0, *args, _lib.LAYOUT_LBC, None, 0, None) == -1
+    assert b"NULL device pointer" in l.sn_last_error()
+
+
 def test_python_operators_refuse_cpu_tensors():
     """No silent CPU path: the operators raise like the reference's CHECK_CUDA (gridencoder.cu:15)."""
     from sanerf_hq_amd.gridencoder import GridEncoder

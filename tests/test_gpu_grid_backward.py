@@ -1,4 +1,10 @@
-"""GPU tests of the grid encoder beyond tests/test_gpu_ops.py: every (D, C) instantiation of the reference, the binned gradient scatter at its extremes (split bins, one row, large batches beyond the slab bound)."""
+"""GPU tests of the grid encoder beyond tests/test_gpu_ops.py: every (D, C) instantiation of the reference, the binned gradient scatter at its extremes (split bins, one row, large batches beyond the slab bound).
+
+These go through the Python operators, i.e. the [B, L*C] layout and, for C >= 2, the pull form of the scatter (up to 3 M samples).  The rest of the
+encoder's routes are in tests/test_gpu_grid_layouts.py, through the raw C ABI and against the fp64 reference tests/grid_ref64.py (anchored to
+tests/golden/kat_encoders.npz and to the oracle by tests/test_grid_ref64.py): the [L,B,C] layout in all five kernels that branch on it (forward
+with fp32 / fp16 tables and dy_dx, atomic and binned backward, input gradient, split bins), max_level < L in the forward and in both backward
+routes, and the push form of the binned scatter (k_bin_scatter + k_bin_accum, C = 2..32) at 2^22 samples with 2^22 - 1 as the pull form's last batch."""
 import ctypes as C  # noqa: F401
 import os
 import subprocess  # noqa: F401
