@@ -39,7 +39,8 @@ typedef enum {
     SN_ERR_INVALID = -1,     /* bad argument (null pointer, unsupported D/C, ...) */
     SN_ERR_UNSUPPORTED = -2, /* valid in the reference but not built here */
     SN_ERR_HIP = -3,         /* HIP runtime error (launch failed, no device) */
-    SN_ERR_WORKSPACE = -4    /* workspace too small */
+    SN_ERR_WORKSPACE = -4,   /* workspace too small */
+    SN_ERR_WINDOW = -5       /* an image smaller than the operator's window (sn_rm_image_ssim_accumulate: H or W < 11) */
 } sn_status;
 
 enum { SN_F32 = 0, SN_F16 = 1 };                 /* table storage type */
@@ -298,6 +299,35 @@ int sn_rm_mask_eval_accumulate(const float *logits, const int64_t *labels, uint3
  *   mse = sum / (3 N);  mse_sum += mse;  psnr_sum += -10 log10(mse);  rgb_images += 1. */
 int sn_rm_image_sqerr_accumulate(const float *pred, uint32_t pred_stride, const float *truth, uint32_t truth_stride, uint32_t N,
                                  sn_eval_record *record, void *workspace, sn_stream_t stream);
+
+/* SSIMMeter.update (nerf/metrics.py:124-131) for one image pair, without a host read.  The reference calls torchmetrics'
+ * structural_similarity_index_measure at its defaults; the quantity, stated here because the package is not a dependency:
+ *   g = exp(-(d / 1.5)^2 / 2), d = -5 .. 5, divided by its sum; the window is w = g (x) g (11 x 11);
+ *   data_range = the given value if > 0, else max(pred.max - pred.min, truth.max - truth.min) over all pixels and channels of each image;
+ *   c1 = (0.01 data_range)^2, c2 = (0.03 data_range)^2;
+ *   per channel and pixel, w-weighted over the window: mu_p, mu_t, E[pp], E[tt], E[pt];  s_p^2 = max(E[pp] - mu_p^2, 0), s_t^2 alike,
+ *   s_pt = E[pt] - mu_p mu_t;  ssim = ((2 mu_p mu_t + c1)(2 s_pt + c2)) / ((mu_p^2 + mu_t^2 + c1)(s_p^2 + s_t^2 + c2));
+ *   value = mean of ssim over the 3 channels and the pixels 5 <= y < H - 5, 5 <= x < W - 5 (the package reflect-pads by 5 and crops 5: the
+ *   padding never reaches a kept pixel).
+ * Evaluated in fp32 on moments centred on a per-tile pivot (variances and the covariance do not change under a shift; raw fp32 moments
+ * cancel when data_range is small), summed in double in a fixed order: equal bits run to run.  A NaN anywhere gives NaN; two constant
+ * images with a derived data_range give 0 / 0 = NaN.
+ * The record: on the device, 8-byte aligned, zeroed by the caller before the first image. */
+typedef struct sn_ssim_record {
+    double ssim_sum;       /* SSIMMeter.V */
+    double last;           /* the last image's value */
+    uint64_t images;       /* SSIMMeter.N */
+} sn_ssim_record;
+
+/* Scratch of sn_rm_image_ssim_accumulate: on the device, 8-byte aligned, zeroed ONCE by the caller; every call leaves it zeroed again.
+ * Calls that share a workspace must be ordered (one stream). */
+#define SN_SSIM_WORKSPACE_BYTES 8192
+
+/* ssim_sum += value; last = value; images += 1.  pred, truth: H * W rows of >= 3 floats (row strides in floats, 3 .. 64: 3 = packed, 5 =
+ * the render buffer read in place; beyond 64: SN_ERR_UNSUPPORTED).  data_range <= 0: derived on the device (one more launch).
+ * H or W < 11: SN_ERR_WINDOW (the package's reflect pad fails there too); H * W >= 2^31: SN_ERR_UNSUPPORTED. */
+int sn_rm_image_ssim_accumulate(const float *pred, uint32_t pred_stride, const float *truth, uint32_t truth_stride, uint32_t H, uint32_t W,
+                                float data_range /* <= 0: derive */, sn_ssim_record *record, void *workspace, sn_stream_t stream);
 
 /* One stage's sample geometry (renderer.py:277-285): bins [N,T+1] in [0,1] -> real_bins [N,T+1] (distances along the
  * ray through the Mip-360 spacing of nears/fars [N]), rays_t [N,T] (mid-points), xyzs [N,T,3] (positions, contracted

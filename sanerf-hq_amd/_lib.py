@@ -41,6 +41,7 @@ ADAM_ZERO_GRAD, ADAM_LAZY = 1, 2                                     # sn_adam_s
 ADAM_MULTI_MAX_TENSORS, ADAM_MULTI_MAX_GROUPS = 32, 8                # sn_adam_step_multi: per call
 MASK_MAX_CLASSES, MASK_EVAL_WORKSPACE_BYTES = 32, 8192               # sn_rm_mask_output / sn_rm_mask_eval_accumulate
 MASK_OUT_MODES = {"none": 0, "heatmap": 1, "composition": 2, "mask": 3}
+SSIM_WORKSPACE_BYTES, SSIM_MAX_STRIDE, SSIM_WINDOW = 8192, 64, 11     # sn_rm_image_ssim_accumulate
 
 
 class AdamTensor(C.Structure):
@@ -58,6 +59,11 @@ class EvalRecord(C.Structure):
     _fields_ = [("nll_mean_sum", C.c_double), ("miou_sum", C.c_double), ("mse_sum", C.c_double), ("psnr_sum", C.c_double),
                 ("images", C.c_uint64), ("rgb_images", C.c_uint64), ("inter", C.c_uint64 * MASK_MAX_CLASSES),
                 ("pred", C.c_uint64 * MASK_MAX_CLASSES), ("truth", C.c_uint64 * MASK_MAX_CLASSES)]
+
+
+class SsimRecord(C.Structure):
+    """sn_ssim_record: what raymarching.image_ssim_accumulate has accumulated (SSIMMeter's V and N, and the last image's value)."""
+    _fields_ = [("ssim_sum", C.c_double), ("last", C.c_double), ("images", C.c_uint64)]
 
 
 class RenderTuning(C.Structure):
@@ -165,6 +171,7 @@ _SIGNATURES = {
     "sn_rm_mask_output": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _u32, _int, _int, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sn_rm_mask_eval_accumulate": (_int, [_vp, _vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp]),
     "sn_rm_image_sqerr_accumulate": (_int, [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "sn_rm_image_ssim_accumulate": (_int, [_vp, _u32, _vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp]),
     "sn_rm_debug_occupancy": (_int, [_vp, _vp, _int]),
     "sn_rm_last_launch_info": (_int, [_vp]),
     "sn_debug_eval": (_int, [_int, _vp, _vp, _u32, _vp, _vp]),

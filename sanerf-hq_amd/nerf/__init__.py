@@ -5,3 +5,4 @@ from .utils import freeze_loaded_parameters, load_checkpoint, save_checkpoint  #
 from .sam_cache import SamFeatureCache, feature_map  # noqa: F401
 from .mask_step import build_error_map, mask_train_loss  # noqa: F401
 from .mask_output import DeviceMeters, mask_eval_step, mask_test_outputs, reference_color_map  # noqa: F401
+from .metrics import SSIMMeter  # noqa: F401

@@ -5,10 +5,11 @@ operators of `raymarching`:
     eval_step's mask branch (trainer.py:599-627)            rm.mask_eval_accumulate    mask_eval_step, DeviceMeters.update_mask
     MeanIoUMeter / loss.item() (metrics.py:165-179, trainer.py:1603-1611)       "
     PSNRMeter / MSEMeter (metrics.py:28-38, 217-221)         rm.image_sqerr_accumulate  DeviceMeters.update_rgb
+    SSIMMeter (metrics.py:102-144)                           rm.image_ssim_accumulate   DeviceMeters(ssim=True).update_rgb, nerf.metrics.SSIMMeter
 
-The output stage is one launch per frame, the evaluation of a view one launch (two with the RGB meters).  Nothing here reads a device value
-on the host before `DeviceMeters.measure()`, so a render followed by these calls can be captured as a HIP graph, and a validation epoch
-synchronises once.  SSIM and LPIPS need third-party networks and stay out.
+The output stage is one launch per frame, the evaluation of a view one launch (two with the RGB meters; SSIM adds one, or two when it
+derives its data range).  Nothing here reads a device value on the host before `DeviceMeters.measure()`, so a render followed by these
+calls can be captured as a HIP graph, and a validation epoch synchronises once.  LPIPS needs a third-party network (a VGG) and stays out.
 """
 from __future__ import annotations
 
@@ -75,37 +76,52 @@ def mask_test_outputs(outputs, opt, color_map, bg_color=None, H=None, W=None, rg
 
 class DeviceMeters:
     """The reference's MeanIoUMeter, PSNRMeter, MSEMeter and the running loss of evaluate_one_epoch as one record on the device:
-    update_mask / update_rgb add an image without a host read, measure() does the only one."""
+    update_mask / update_rgb add an image without a host read, measure() does the only one.  ssim=True: a second record beside it holds
+    the SSIMMeter, fed by update_rgb too."""
 
-    def __init__(self, device, num_classes=None, eps: float = 1e-6):
+    def __init__(self, device, num_classes=None, eps: float = 1e-6, ssim: bool = False):
         self.device = torch.device(device)
         self.num_classes = num_classes
         self.eps = float(eps)
         self.record = rm.eval_record(self.device)
         self.workspace = rm.eval_workspace(self.device)
+        self.ssim = bool(ssim)
+        if self.ssim:
+            self.ssim_record = rm.ssim_record(self.device)
+            self.ssim_workspace = rm.ssim_workspace(self.device)
 
     def clear(self) -> None:
         self.record.zero_()
+        if self.ssim:
+            self.ssim_record.zero_()
 
     def update_mask(self, logits, labels, eps=None) -> None:
         """One image's logits [..., K] and labels [...] (-1: unlabelled): eval_step's loss and MeanIoUMeter.update(argmax id, label).
         eps: the clamp of the loss for this image (default: the constructor's)."""
         rm.mask_eval_accumulate(logits, labels, self.record, self.workspace, self.eps if eps is None else float(eps), self.num_classes)
 
-    def update_rgb(self, preds, truths) -> None:
-        """One image's prediction and ground truth [..., 3]: MSEMeter.update and PSNRMeter.update."""
+    def update_rgb(self, preds, truths, H=None, W=None) -> None:
+        """One image's prediction and ground truth [..., 3]: MSEMeter.update and PSNRMeter.update; with ssim=True also SSIMMeter.update,
+        which needs the image's shape: [H,W,3] inputs, or H and W beside [N,3] rows."""
         rm.image_sqerr_accumulate(preds, truths, self.record, self.workspace)
+        if self.ssim:
+            rm.image_ssim_accumulate(preds, truths, self.ssim_record, self.ssim_workspace, H=H, W=W)
 
     def read(self) -> dict:
         """The raw record (sums, image counts, the last image's class counts) on the host."""
         return rm.read_eval_record(self.record)
 
     def measure(self) -> dict:
-        """{'mIoU', 'loss', 'PSNR', 'MSE'}: means over the images seen, 0 for a meter that saw none (as the reference's meters)."""
+        """{'mIoU', 'loss', 'PSNR', 'MSE'} (and 'SSIM' with ssim=True): means over the images seen, 0 for a meter that saw none (as the
+        reference's meters)."""
         r = self.read()
         n, m = r["images"], r["rgb_images"]
-        return {"mIoU": r["miou_sum"] / n if n else 0, "loss": r["nll_mean_sum"] / n if n else 0,
-                "PSNR": r["psnr_sum"] / m if m else 0, "MSE": r["mse_sum"] / m if m else 0}
+        res = {"mIoU": r["miou_sum"] / n if n else 0, "loss": r["nll_mean_sum"] / n if n else 0,
+               "PSNR": r["psnr_sum"] / m if m else 0, "MSE": r["mse_sum"] / m if m else 0}
+        if self.ssim:
+            s = rm.read_ssim_record(self.ssim_record)
+            res["SSIM"] = s["ssim_sum"] / s["images"] if s["images"] else 0
+        return res
 
 
 def mask_eval_step(outputs, data, opt, meters: DeviceMeters):

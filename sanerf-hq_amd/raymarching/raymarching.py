@@ -695,6 +695,57 @@ def image_sqerr_accumulate(pred, truth, record: torch.Tensor, workspace: torch.T
     _lib.check(_lib.lib().sn_rm_image_sqerr_accumulate(p_ptr, p_stride, t_ptr, t_stride, N, rec, ws, _lib.stream()), "image_sqerr_accumulate")
 
 
+SSIM_RECORD_BYTES = C.sizeof(_lib.SsimRecord)
+
+
+def ssim_record(device) -> torch.Tensor:
+    """A zeroed sn_ssim_record on the device (as int64 words; read it with `read_ssim_record`)."""
+    return torch.zeros(SSIM_RECORD_BYTES // 8, device=device, dtype=torch.int64)
+
+
+def ssim_workspace(device) -> torch.Tensor:
+    """The zero-at-rest scratch of image_ssim_accumulate (one per stream)."""
+    return torch.zeros(_lib.SSIM_WORKSPACE_BYTES // 8, device=device, dtype=torch.int64)
+
+
+def read_ssim_record(record: torch.Tensor) -> dict:
+    """The record's fields on the host (this is the host read: it synchronises)."""
+    r = _lib.SsimRecord.from_buffer_copy(record.detach().cpu().numpy().tobytes())
+    return {"ssim_sum": r.ssim_sum, "last": r.last, "images": int(r.images)}
+
+
+def image_ssim_accumulate(pred, truth, record: torch.Tensor, workspace: torch.Tensor, H: Optional[int] = None, W: Optional[int] = None,
+                          data_range: Optional[float] = None) -> None:
+    """SSIMMeter.update for one image pair without a host read (sn_rm_image_ssim_accumulate; nerf/metrics.py:124-131, torchmetrics'
+    structural_similarity_index_measure at its defaults: 11 x 11 Gaussian window of sigma 1.5, mean over channels and the pixels a whole
+    window fits around): pred, truth [H,W,3] float32, or [N,3] / row-strided views (the image columns of the packed [N,5] render buffer are
+    read in place) with explicit H and W -> `record` gets the image's value added.  data_range: a positive number, or None as the reference
+    calls it: max(pred.max() - pred.min(), truth.max() - truth.min()), found on the device by one more launch."""
+    if not pred.is_cuda or not truth.is_cuda:
+        raise RuntimeError("pred / truth must be a CUDA tensor")
+    if H is None or W is None:
+        if pred.dim() != 3:
+            raise RuntimeError(f"image_ssim_accumulate: H and W are needed for a pred of shape {tuple(pred.shape)} (only [H,W,3] carries them)")
+        H, W = pred.shape[0], pred.shape[1]
+    H, W = int(H), int(W)
+    if data_range is not None and not float(data_range) > 0:
+        raise ValueError(f"image_ssim_accumulate: data_range {data_range!r} must be positive (None: derived from the images)")
+    rows = []
+    for t, name in ((pred, "pred"), (truth, "truth")):
+        t, _, stride = _image_rows(t, name, H * W)
+        if stride > _lib.SSIM_MAX_STRIDE:                            # the kernel reads a tile's rows whole: a sparser image is packed first
+            t = t.contiguous()
+        rows.append(t)
+    if record.dtype != torch.int64 or record.numel() * 8 < SSIM_RECORD_BYTES:
+        raise RuntimeError("record must come from raymarching.ssim_record()")
+    if workspace.dtype != torch.int64 or workspace.numel() * 8 < _lib.SSIM_WORKSPACE_BYTES:
+        raise RuntimeError("workspace must come from raymarching.ssim_workspace()")
+    rec, ws = _lib.dev(record, "record", torch.int64), _lib.dev(workspace, "workspace", torch.int64)
+    _lib.check(_lib.lib().sn_rm_image_ssim_accumulate(rows[0].data_ptr(), rows[0].stride(0), rows[1].data_ptr(), rows[1].stride(0), H, W,
+                                                      0.0 if data_range is None else float(data_range), rec, ws, _lib.stream()),
+               "image_ssim_accumulate")
+
+
 class _composite(Function):
     """out[n,k] = sum_t w[n,t] * v[n,t,k]."""
 
