@@ -55,7 +55,9 @@ int sn_abi_version(void);
 #define SN_BUILD_POISON_LDS 2
 int sn_build_flags(void);
 /* Experiments builds only (SN_ERR_UNSUPPORTED otherwise): process-wide A/B switches of variants that are not reachable through a
- * descriptor.  Keys: "wide_jit" (0: the superseded k_mlp_wide forward instead of k_mlp_wide_j). */
+ * descriptor.  Keys: "wide_jit" (0: the superseded k_mlp_wide forward instead of k_mlp_wide_j).
+ * One key is honoured by every build: "distill_general" (1: sn_rm_feature_distill_loss / sn_rm_feature_map take the general four-tap path
+ * also where h, w == Ho, Wo, so that the identity fast path can be compared with it; sn_rm_feature_distill_workspace_bytes follows). */
 int sn_debug_set(const char *key, int value);
 const char *sn_last_error(void);
 /* number of HIP devices visible; <0 on error.  Lets hosts fail loudly before any launch. */
@@ -328,6 +330,40 @@ typedef struct sn_ssim_record {
  * H or W < 11: SN_ERR_WINDOW (the package's reflect pad fails there too); H * W >= 2^31: SN_ERR_UNSUPPORTED. */
 int sn_rm_image_ssim_accumulate(const float *pred, uint32_t pred_stride, const float *truth, uint32_t truth_stride, uint32_t H, uint32_t W,
                                 float data_range /* <= 0: derive */, sn_ssim_record *record, void *workspace, sn_stream_t stream);
+
+/* The loss tail of the SAM-feature distillation step (nerf/trainer.py:540-550; evaluation :664-670), without a host read:
+ *   pred = F.interpolate(samvit.reshape(1, h, w, C).permute(0, 3, 1, 2), (Ho, Wo), mode="bilinear");  loss = MSELoss(pred, target).mean()
+ * and the gradient of the loss with respect to samvit.  The quantity, stated here because no torch backend is the contract (torch's fp32
+ * CPU kernel rounds its weights differently, by up to 7e-6).  The taps of output index o on an axis of n_in samples resized to n_out,
+ * by exactly this fp32 chain (nothing contracted):
+ *   s = float(n_in) / float(n_out);  src = max((o + 0.5f) * s - 0.5f, 0);  i0 = min(int(src), n_in - 1);  i1 = i0 + (i0 < n_in - 1);
+ *   l1 = src - i0;  l0 = 1 - l1.
+ * With (y0, y1, l0y, l1y) the taps of oy on h -> Ho and (x0, x1, l0x, l1x) those of ox on w -> Wo, f[y, x, c] = feat[(y w + x) feat_stride + c]:
+ *   pred[c, oy, ox] = l0y (l0x f[y0,x0,c] + l1x f[y0,x1,c]) + l1y (l0x f[y1,x0,c] + l1x f[y1,x1,c])        in fp32;
+ *   d = pred - target in fp32;  loss = sum d^2 / n, n = C Ho Wo, squared and summed in double in a fixed order (no float atomics: two
+ *   calls on the same inputs give equal bits), stored as a float;
+ *   grad_feat[y w + x, c] = (scale * (scale_dev ? *scale_dev : 1)) * (2 / float(n)) * sum_oy wy(oy -> y) sum_ox wx(ox -> x) d[c, oy, ox],
+ *   w(o -> i) = (i0(o) == i ? l0 : 0) + (i1(o) == i ? l1 : 0), over the contiguous range of outputs with i - 1 <= i0(o) <= i, in ascending
+ *   order in fp32.  Every element of grad_feat is written exactly once (0 where no output reaches the pixel, e.g. 64 -> 16); the caller does
+ *   not clear it.
+ * Stated differences from torch: where h, w == Ho, Wo every l1 is 0 and a fast path (one launch) reads f[oy, ox, c] alone -- on finite
+ * inputs its values are equal to the general path's; a non-finite value in a zero-weight neighbour (0 * inf) does not reach the result
+ * there, as it does in torch and in the general path.  Otherwise NaN and Inf propagate: a non-finite input with a non-zero weight gives a
+ * non-finite loss.
+ * feat: h w rows of C floats, feat_stride >= C floats apart (the render's `samvit`, read in place); target, resized: packed [C, Ho, Wo];
+ * loss [1]; grad_feat packed [h w, C]; grad_feat and resized may each be NULL.  Any sizes >= 1; h w C and n below 2^31 (beyond:
+ * SN_ERR_UNSUPPORTED).  Launches: one where h, w == Ho, Wo or grad_feat is NULL, else two.
+ * The workspace: on the device, 8-byte aligned.  Its first SN_DISTILL_WORKSPACE_FIXED_BYTES are zeroed ONCE by the caller and left zeroed by
+ * every call (calls that share a workspace must be ordered: one stream); a resize with a gradient needs n more floats behind them, which
+ * every such call writes before it reads and which carry nothing from call to call (SN_ERR_WORKSPACE when workspace_bytes is too small). */
+#define SN_DISTILL_WORKSPACE_FIXED_BYTES 8256
+size_t sn_rm_feature_distill_workspace_bytes(uint32_t h, uint32_t w, uint32_t C, uint32_t Ho, uint32_t Wo);   /* 0: sizes not supported */
+int sn_rm_feature_distill_loss(const float *feat, uint32_t feat_stride, uint32_t h, uint32_t w, uint32_t C, const float *target, uint32_t Ho,
+                               uint32_t Wo, float scale, const float *scale_dev, float *loss, float *grad_feat, float *resized, void *workspace,
+                               size_t workspace_bytes, sn_stream_t stream);
+/* The forward half alone: out [C, Ho, Wo] = pred above (what decode_step, trainer.py:928-930, and store_sam_feautres need). */
+int sn_rm_feature_map(const float *feat, uint32_t feat_stride, uint32_t h, uint32_t w, uint32_t C, uint32_t Ho, uint32_t Wo, float *out,
+                      sn_stream_t stream);
 
 /* One stage's sample geometry (renderer.py:277-285): bins [N,T+1] in [0,1] -> real_bins [N,T+1] (distances along the
  * ray through the Mip-360 spacing of nears/fars [N]), rays_t [N,T] (mid-points), xyzs [N,T,3] (positions, contracted

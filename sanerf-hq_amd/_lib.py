@@ -42,6 +42,7 @@ ADAM_MULTI_MAX_TENSORS, ADAM_MULTI_MAX_GROUPS = 32, 8                # sn_adam_s
 MASK_MAX_CLASSES, MASK_EVAL_WORKSPACE_BYTES = 32, 8192               # sn_rm_mask_output / sn_rm_mask_eval_accumulate
 MASK_OUT_MODES = {"none": 0, "heatmap": 1, "composition": 2, "mask": 3}
 SSIM_WORKSPACE_BYTES, SSIM_MAX_STRIDE, SSIM_WINDOW = 8192, 64, 11     # sn_rm_image_ssim_accumulate
+DISTILL_WORKSPACE_FIXED_BYTES = 8256                                  # sn_rm_feature_distill_loss: the zero-at-rest part of its workspace
 
 
 class AdamTensor(C.Structure):
@@ -172,6 +173,9 @@ _SIGNATURES = {
     "sn_rm_mask_eval_accumulate": (_int, [_vp, _vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp]),
     "sn_rm_image_sqerr_accumulate": (_int, [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "sn_rm_image_ssim_accumulate": (_int, [_vp, _u32, _vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp]),
+    "sn_rm_feature_distill_workspace_bytes": (C.c_size_t, [_u32, _u32, _u32, _u32, _u32]),
+    "sn_rm_feature_distill_loss": (_int, [_vp, _u32, _u32, _u32, _u32, _vp, _u32, _u32, _f32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "sn_rm_feature_map": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "sn_rm_debug_occupancy": (_int, [_vp, _vp, _int]),
     "sn_rm_last_launch_info": (_int, [_vp]),
     "sn_debug_eval": (_int, [_int, _vp, _vp, _u32, _vp, _vp]),

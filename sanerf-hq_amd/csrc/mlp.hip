@@ -1477,6 +1477,7 @@ static constexpr int g_wide_bwd_j = 0;
 
 extern "C" int sn_debug_set(const char *key, int value) {
     SN_REQUIRE(key, "debug_set: NULL key");
+    if (strcmp(key, "distill_general") == 0) { g_distill_general = value != 0; return SN_OK; }   // distill.hip; in every build: the product's tests compare the two paths
 #ifdef SN_EXPERIMENTS
     if (strcmp(key, "wide_jit") == 0) { g_wide_jit = value; return SN_OK; }
     if (strcmp(key, "wide_narrow1") == 0) { g_wide_narrow1 = value; return SN_OK; }

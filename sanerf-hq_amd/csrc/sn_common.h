@@ -313,5 +313,6 @@ static inline bool levels_fast(const GridLevels &g) {
 
 
 extern int g_bin_pull;        // grid_binned.hip (entry form of the binned grid backward; set by sn_debug_set in experiments builds)
+extern int g_distill_general; // distill.hip (1: the identity shapes of the feature-distillation loss take the general path; sn_debug_set in every build)
 
 }  // namespace sn
