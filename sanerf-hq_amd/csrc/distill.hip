@@ -28,16 +28,15 @@
 // and backward cannot disagree.  A lane owns 4 channels (1 when C is no multiple of 4) of one source pixel, adds wy (sum_ox wx d) in
 // ascending order and writes its element exactly once -- 0 where no output reaches the pixel; the caller does not clear grad_feat.
 //
-// Reduction: the ticket pattern of k_image_ssim (publish_and_draw of mask_output.hip): a lane adds its elements in ascending tile order
-// in double, the waves by a butterfly, the workgroup publishes its partial and takes a ticket; the workgroup that draws the last one sums
-// the partials in ascending order, divides, stores the loss and returns the fixed part of the workspace to zero.
-#include "sn_common.h"
+// Reduction: the ticket reduction of sn_reduce.h.  A lane adds its elements in ascending tile order in double; the workgroup that draws
+// the last ticket sums the partials, divides, stores the loss and returns the fixed part of the workspace to zero.
+#include "sn_reduce.h"
 
 namespace sn {
 
 int g_distill_general = 0;       // sn_debug_set("distill_general", 1): the identity shapes take the general (four-tap, two-launch) path too
 
-constexpr uint32_t DI_THREADS = 256;
+constexpr uint32_t DI_THREADS = SN_REDUCE_THREADS;
 constexpr uint32_t DI_CT = 64, DI_OT = 32;        // a tile: channels x ox
 constexpr uint32_t DI_ROW = DI_OT + 1;            // floats between the tile's rows in LDS
 constexpr uint32_t DI_MAX_PARTIALS = 1024;        // workgroups of k_feature_distill (a workgroup loops over tiles beyond)
@@ -90,12 +89,6 @@ struct DistillArgs {
 __device__ __forceinline__ float distill_coef(float scale, const float *scale_dev, uint32_t n) {
     const float sd = scale_dev ? *scale_dev : 1.0f;
     return (scale * sd) * (2.0f / (float)n);
-}
-
-__device__ __forceinline__ double distill_wave_sum(double v) {          // butterfly: the same order of additions in every run
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 template <bool IDENT>
@@ -164,30 +157,9 @@ __global__ __launch_bounds__(256) void k_feature_distill(const DistillArgs a) {
     }
     if (!a.loss) return;                                                 // sn_rm_feature_map: nothing to reduce (uniform over the launch)
 
-    // the workgroup's partial, the ticket (as k_image_ssim; publish_and_draw of mask_output.hip)
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    sum = distill_wave_sum(sum);
-    if (lane == 0) s_wave[wave] = sum;
-    __syncthreads();
-    if (tid == 0) a.ws->part_sum[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-    __threadfence();
-    __syncthreads();
+    if (!publish_and_draw(sum, 0u, &a.ws->ticket, a.ws->part_sum, nullptr, s_wave, nullptr, &s_flag)) return;
+    const double total = sum_partials(a.ws->part_sum, nullptr, s_part, nullptr, nullptr);
     if (tid == 0) {
-        const uint32_t mine = __hip_atomic_fetch_add(&a.ws->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        s_flag = mine == gridDim.x - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (s_flag == 0u) return;
-    __threadfence();
-    // the last workgroup: everyone has published; the partials in ascending order, the fixed workspace back to zero
-    for (uint32_t i = tid; i < gridDim.x; i += DI_THREADS) {
-        s_part[i] = __hip_atomic_load(&a.ws->part_sum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&a.ws->part_sum[i], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double total = 0.0;
-        for (uint32_t i = 0; i < gridDim.x; ++i) total += s_part[i];
         *a.loss = (float)(total / (double)a.n);
         __hip_atomic_store(&a.ws->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -242,10 +214,7 @@ static int distill_shape(const char *who, uint32_t feat_stride, uint32_t h, uint
     SN_REQUIRE(feat_stride >= C, "%s: feat_stride %u floats is less than C = %u", who, feat_stride, C);
     const bool fits = (uint64_t)h * w < (1ull << 31) && (uint64_t)h * w * C < (1ull << 31) && (uint64_t)Ho * Wo < (1ull << 31) &&
                       (uint64_t)Ho * Wo * C < (1ull << 31);
-    if (!fits) {
-        set_error("%s: h * w * C and C * Ho * Wo must stay below 2^31 (got %u x %u -> %u x %u, C = %u)", who, h, w, Ho, Wo, C);
-        return SN_ERR_UNSUPPORTED;
-    }
+    SN_UNSUPPORTED(fits, "%s: h * w * C and C * Ho * Wo must stay below 2^31 (got %u x %u -> %u x %u, C = %u)", who, h, w, Ho, Wo, C);
     return SN_OK;
 }
 

@@ -4,19 +4,13 @@
 // The reference states each of them as a chain of torch element-wise ops plus torch.multinomial; here each is one launch (the EMA: two, so
 // that every new value is computed from the map as it was before the call), without atomics: every sum has a fixed order and two runs give
 // the same bits.  exp is sn::expf_det, division and sqrt are IEEE-rounded (Makefile flags), nothing is contracted into an fma.
-#include "sn_common.h"
+#include "sn_reduce.h"
 
 namespace sn {
 
 constexpr uint32_t RP_MAX_S = 64;        // samples (pairs) per group
 constexpr uint32_t RP_MAX_K = 32;        // instances
 constexpr float COS_EPS = 1e-8f;         // F.cosine_similarity's eps
-
-__device__ __forceinline__ float wave_sum_fixed(float v) {       // butterfly: the same order of additions in every run
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
 #pragma unroll
@@ -32,15 +26,7 @@ template <int KT>
 __device__ __forceinline__ void load_probs(const float *__restrict__ row, uint32_t K, bool from_logits, float (&p)[KT]) {
 #pragma unroll
     for (int k = 0; k < KT; ++k) p[k] = (uint32_t)k < K ? row[k] : 0.0f;
-    if (!from_logits) return;
-    float mx = p[0];
-#pragma unroll
-    for (int k = 1; k < KT; ++k) if ((uint32_t)k < K) mx = fmaxf(mx, p[k]);
-    float sum = 0.0f;
-#pragma unroll
-    for (int k = 0; k < KT; ++k) if ((uint32_t)k < K) { p[k] = expf_det(p[k] - mx); sum += p[k]; }
-#pragma unroll
-    for (int k = 0; k < KT; ++k) if ((uint32_t)k < K) p[k] = p[k] / sum;
+    if (from_logits) softmax_row<KT>(p, K);
 }
 
 template <int KT>
@@ -61,9 +47,7 @@ __global__ __launch_bounds__(256) void k_ray_pair_select(const float *__restrict
     const float *inc = incoherent + (size_t)g * P, *u = uniform + (size_t)g * P;
     uint32_t mine = 0;
     for (uint32_t i = lane; i < P; i += 64u) mine += (1.0f - inc[i]) > 0.8f ? 1u : 0u;
-    uint32_t cand = mine;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) cand += __shfl_xor(cand, off, 64);
+    const uint32_t cand = wave_sum(mine);
     const bool all = cand == 0u;                     // trainer.py:270-273: a group without candidates draws from all its pixels
     uint64_t prev = 0;
     bool have_prev = false;
@@ -115,8 +99,7 @@ __global__ __launch_bounds__(256) void k_ray_pair_rgb_loss(const float *__restri
         const int64_t v = sample_index[t];
         valid += (v >= 0 && v < (int64_t)P) ? 1u : 0u;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) valid += __shfl_xor(valid, off, 64);
+    valid = wave_sum(valid);
     if (lane == 0) s_cnt[wave] = valid;
     if (tid < S) {
         const int64_t v = sample_index[(size_t)g * S + tid];
@@ -179,7 +162,7 @@ __global__ __launch_bounds__(256) void k_ray_pair_rgb_loss(const float *__restri
             cnt += (uint32_t)__popcll(__ballot(sim));
             acc += e;
         }
-        acc = wave_sum_fixed(acc);
+        acc = wave_sum(acc);
         if (lane == 0) {
             s_coef[s] = cnt ? total / (float)cnt : 0.0f;
             if (loss_per_pair) loss_per_pair[(size_t)g * S + s] = acc / (float)cnt;      // 0 matches (NaN colours): 0 / 0 like the reference
@@ -297,14 +280,6 @@ __global__ __launch_bounds__(256) void k_error_map_scatter(const int64_t *__rest
 
 using namespace sn;
 
-#define SN_UNSUPPORTED(cond, ...)             \
-    do {                                      \
-        if (!(cond)) {                        \
-            ::sn::set_error(__VA_ARGS__);     \
-            return SN_ERR_UNSUPPORTED;        \
-        }                                     \
-    } while (0)
-
 extern "C" {
 
 int sn_rm_ray_pair_select(const float *incoherent, const float *uniform, uint32_t G, uint32_t P, uint32_t S, int64_t *sample_index,
@@ -334,11 +309,7 @@ int sn_rm_ray_pair_rgb_loss(const float *rgb, const float *masks, int from_logit
 #define SN_RP_LAUNCH(KT)                                                                                                                       \
     hipLaunchKernelGGL(k_ray_pair_rgb_loss<KT>, dim3(G), dim3(256), 0, st, rgb, masks, from_logits, sample_index, G, P, S, K, thr, w, eps,        \
                        use_pred_logistics, scale, scale_dev, loss_per_pair, pair_count, grad_masks)
-    if (K <= 2) SN_RP_LAUNCH(2);
-    else if (K <= 4) SN_RP_LAUNCH(4);
-    else if (K <= 8) SN_RP_LAUNCH(8);
-    else if (K <= 16) SN_RP_LAUNCH(16);
-    else SN_RP_LAUNCH(32);
+    SN_DISPATCH_KT(K, SN_RP_LAUNCH);
 #undef SN_RP_LAUNCH
     SN_LAUNCH_CHECK("k_ray_pair_rgb_loss");
     return SN_OK;

@@ -17,11 +17,11 @@
 // Stores.  rgb8 is 3 bytes a pixel: the tile's 768 bytes (192 per wave) are staged in LDS and leave as 192 dword stores; only the
 // last <= 3 bytes of an image whose size is not a multiple of 4 bytes are byte stores.  The float rgb is staged alike (consecutive dwords).
 //
-// The two accumulating kernels end with the ticket reduction of k_adam_multi (optim.hip): a workgroup publishes its partial sum (and adds
-// its LDS class histogram to the workspace's counts with one integer atomic per class), takes a ticket, and the workgroup that draws the
-// last ticket sums the partials in ascending order, forms the image's values, adds them to the caller's record and puts the workspace
-// back to zero.  Nobody waits for anybody, the host reads nothing.
-#include "sn_common.h"
+// The two accumulating kernels end with the ticket reduction of sn_reduce.h: a workgroup publishes its partial sum (and adds its LDS class
+// histogram to the workspace's counts with one integer atomic per class), takes a ticket, and the workgroup that draws the last ticket
+// sums the partials in ascending order, forms the image's values, adds them to the caller's record and puts the workspace back to zero.
+// Nobody waits for anybody, the host reads nothing.
+#include "sn_reduce.h"
 
 namespace sn {
 
@@ -37,6 +37,7 @@ struct EvalWorkspace {
     uint32_t part_cnt[MO_MAX_PARTIALS];
 };
 static_assert(sizeof(EvalWorkspace) <= SN_MASK_EVAL_WORKSPACE_BYTES, "the workspace constant of the header is too small");
+static_assert(MO_TILE == SN_REDUCE_THREADS, "the accumulating kernels end with the reduction of sn_reduce.h");
 
 static inline uint32_t mo_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
@@ -121,14 +122,7 @@ __device__ __forceinline__ void probs_argmax(float (&p)[KT], uint32_t K, int &ar
     if (K == 1u) {
         p[0] = 1.0f / (1.0f + expf_det(-p[0]));
     } else {
-        float mx = p[0];
-#pragma unroll
-        for (int k = 1; k < KT; ++k) if ((uint32_t)k < K) mx = fmaxf(mx, p[k]);
-        float sum = 0.0f;
-#pragma unroll
-        for (int k = 0; k < KT; ++k) if ((uint32_t)k < K) { p[k] = expf_det(p[k] - mx); sum += p[k]; }
-#pragma unroll
-        for (int k = 0; k < KT; ++k) if ((uint32_t)k < K) p[k] = p[k] / sum;
+        softmax_row<KT>(p, K);
     }
     arg = 0; conf = p[0];
 #pragma unroll
@@ -235,53 +229,6 @@ __global__ __launch_bounds__(256) void k_mask_output(const MaskOutArgs a) {
     }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {                // butterfly: the same order of additions in every run
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// The workgroup's partial (sum, count) into the workspace, then the ticket.  True in every lane of the workgroup that drew the last
-// ticket: all the others have published.  (Each lane's own stores and atomics are fenced before the barrier; lane 0's acq_rel add at
-// agent scope orders them before the ticket, and the last workgroup's reads after it.)
-__device__ __forceinline__ bool publish_and_draw(EvalWorkspace *ws, double sum, uint32_t count, double *s_wave, uint32_t *s_cnt, uint32_t *s_flag) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    sum = wave_sum_f64(sum);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) count += __shfl_xor(count, off, 64);
-    if (lane == 0) { s_wave[wave] = sum; s_cnt[wave] = count; }
-    __syncthreads();
-    if (tid == 0) {
-        ws->part_sum[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-        ws->part_cnt[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    }
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        const uint32_t mine = __hip_atomic_fetch_add(&ws->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        *s_flag = mine == gridDim.x - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    const bool last = *s_flag != 0u;
-    if (last) __threadfence();
-    return last;
-}
-
-// In the last workgroup: the partials in ascending order (lane 0's values are the ones to use); their slots go back to zero, so that
-// the whole workspace is zero at rest.
-__device__ __forceinline__ void sum_partials(EvalWorkspace *ws, double *s_part, uint32_t *s_pcnt, double &sum, uint64_t &count) {
-    for (uint32_t i = threadIdx.x; i < gridDim.x; i += blockDim.x) {
-        s_part[i] = __hip_atomic_load(&ws->part_sum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_pcnt[i] = __hip_atomic_load(&ws->part_cnt[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ws->part_sum[i], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ws->part_cnt[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    sum = 0.0; count = 0;
-    if (threadIdx.x == 0)
-        for (uint32_t i = 0; i < gridDim.x; ++i) { sum += s_part[i]; count += s_pcnt[i]; }
-}
-
 template <int KT>
 __global__ __launch_bounds__(256) void k_mask_eval_accumulate(const float *__restrict__ logits, const int64_t *__restrict__ labels, uint32_t N, uint32_t K,
                                                               uint32_t C, float eps, sn_eval_record *__restrict__ rec, EvalWorkspace *__restrict__ ws) {
@@ -325,11 +272,10 @@ __global__ __launch_bounds__(256) void k_mask_eval_accumulate(const float *__res
     }
     __syncthreads();
     if (tid < 3 * MO_MAX_K && s_hist[tid] != 0u) atomicAdd(&ws->counts[tid], (unsigned long long)s_hist[tid]);
-    if (!publish_and_draw(ws, sum, labelled, s_wave, s_cnt, &s_flag)) return;
+    if (!publish_and_draw(sum, labelled, &ws->ticket, ws->part_sum, ws->part_cnt, s_wave, s_cnt, &s_flag)) return;
 
-    double total;
     uint64_t n_lab;
-    sum_partials(ws, s_part, s_pcnt, total, n_lab);
+    const double total = sum_partials(ws->part_sum, ws->part_cnt, s_part, s_pcnt, &n_lab);
     uint64_t mine = 0;
     if (tid < 3 * MO_MAX_K) {
         mine = __hip_atomic_load(&ws->counts[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -372,10 +318,9 @@ __global__ __launch_bounds__(256) void k_image_sqerr_accumulate(const float *__r
             sum += d * d;
         }
     }
-    if (!publish_and_draw(ws, sum, 0u, s_wave, s_cnt, &s_flag)) return;
-    double total;
+    if (!publish_and_draw(sum, 0u, &ws->ticket, ws->part_sum, ws->part_cnt, s_wave, s_cnt, &s_flag)) return;
     uint64_t unused;
-    sum_partials(ws, s_part, s_pcnt, total, unused);
+    const double total = sum_partials(ws->part_sum, ws->part_cnt, s_part, s_pcnt, &unused);
     if (threadIdx.x == 0) {
         const double mse = total / (3.0 * (double)N);
         rec->mse_sum += mse;                                     // MSEMeter.update
@@ -388,23 +333,6 @@ __global__ __launch_bounds__(256) void k_image_sqerr_accumulate(const float *__r
 }  // namespace sn
 
 using namespace sn;
-
-#define SN_UNSUPPORTED(cond, ...)             \
-    do {                                      \
-        if (!(cond)) {                        \
-            ::sn::set_error(__VA_ARGS__);     \
-            return SN_ERR_UNSUPPORTED;        \
-        }                                     \
-    } while (0)
-
-#define SN_MO_DISPATCH(K, LAUNCH) \
-    do {                          \
-        if ((K) <= 2) LAUNCH(2);  \
-        else if ((K) <= 4) LAUNCH(4); \
-        else if ((K) <= 8) LAUNCH(8); \
-        else if ((K) <= 16) LAUNCH(16); \
-        else LAUNCH(32);          \
-    } while (0)
 
 extern "C" {
 
@@ -437,7 +365,7 @@ int sn_rm_mask_output(const float *logits, uint32_t N, uint32_t K, const float *
     a.probs = probs; a.instance_id = instance_id; a.confidence = confidence; a.rgb = rgb; a.rgb8 = rgb8;
     hipStream_t st = (hipStream_t)stream;
 #define SN_MO_LAUNCH(KT) hipLaunchKernelGGL(k_mask_output<KT>, dim3(div_up(N, MO_TILE)), dim3(MO_TILE), 0, st, a)
-    SN_MO_DISPATCH(K, SN_MO_LAUNCH);
+    SN_DISPATCH_KT(K, SN_MO_LAUNCH);
 #undef SN_MO_LAUNCH
     SN_LAUNCH_CHECK("k_mask_output");
     return SN_OK;
@@ -458,7 +386,7 @@ int sn_rm_mask_eval_accumulate(const float *logits, const int64_t *labels, uint3
     hipStream_t st = (hipStream_t)stream;
     EvalWorkspace *ws = static_cast<EvalWorkspace *>(workspace);
 #define SN_ME_LAUNCH(KT) hipLaunchKernelGGL(k_mask_eval_accumulate<KT>, dim3(blocks), dim3(MO_TILE), 0, st, logits, labels, N, K, C, eps, record, ws)
-    SN_MO_DISPATCH(K, SN_ME_LAUNCH);
+    SN_DISPATCH_KT(K, SN_ME_LAUNCH);
 #undef SN_ME_LAUNCH
     SN_LAUNCH_CHECK("k_mask_eval_accumulate");
     return SN_OK;

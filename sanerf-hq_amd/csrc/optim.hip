@@ -161,6 +161,7 @@ __global__ __launch_bounds__(256) void k_adam_multi(const AdamMultiArgs a) {
     // one ticket after its last read (the barrier: all its waves are through the loop; the acq_rel add: this wave's own loads have
     // returned before the add is issued).  The workgroup whose ticket is the last one knows every other is past its reads, stores
     // count + 1 for each tensor and puts the ticket back to zero for the next launch.  Nobody waits for anybody.
+    // (sn_reduce.h builds the meters' reduction on the same ticket and states the ordering argument in full.)
     if (a.ticket) {
         __syncthreads();
         if (threadIdx.x < 64) {

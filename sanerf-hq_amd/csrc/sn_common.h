@@ -28,6 +28,24 @@ int hip_fail(hipError_t e, const char *what);
         }                                     \
     } while (0)
 
+#define SN_UNSUPPORTED(cond, ...)             \
+    do {                                      \
+        if (!(cond)) {                        \
+            ::sn::set_error(__VA_ARGS__);     \
+            return SN_ERR_UNSUPPORTED;        \
+        }                                     \
+    } while (0)
+
+// The kernels that keep a row of K <= 32 class values in registers are instantiated for KT in {2, 4, 8, 16, 32}: LAUNCH(KT) for the smallest KT >= K.
+#define SN_DISPATCH_KT(K, LAUNCH)       \
+    do {                                \
+        if ((K) <= 2) LAUNCH(2);        \
+        else if ((K) <= 4) LAUNCH(4);   \
+        else if ((K) <= 8) LAUNCH(8);   \
+        else if ((K) <= 16) LAUNCH(16); \
+        else LAUNCH(32);                \
+    } while (0)
+
 #define SN_HIP_OK(call)                                   \
     do {                                                  \
         hipError_t e__ = (call);                          \
@@ -102,6 +120,20 @@ __device__ __forceinline__ float expf_det(float x) {
     p = p + 1.0f;
     const float y = __builtin_amdgcn_ldexpf(p, (int)k);
     return x != x ? x : y;
+}
+
+// torch's softmax over the first K entries of a row in registers: exp(x - max) / sum, the sum in ascending k, an IEEE divide.  A NaN or
+// +inf entry (or a row of -inf) makes the whole row NaN, as in torch.  Entries past K are left alone.
+template <int KT>
+__device__ __forceinline__ void softmax_row(float (&p)[KT], uint32_t K) {
+    float mx = p[0];
+#pragma unroll
+    for (int k = 1; k < KT; ++k) if ((uint32_t)k < K) mx = fmaxf(mx, p[k]);
+    float sum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < KT; ++k) if ((uint32_t)k < K) { p[k] = expf_det(p[k] - mx); sum += p[k]; }
+#pragma unroll
+    for (int k = 0; k < KT; ++k) if ((uint32_t)k < K) p[k] = p[k] / sum;
 }
 
 template <typename T> __device__ __forceinline__ float table_ld(const T *p);

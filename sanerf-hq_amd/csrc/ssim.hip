@@ -34,21 +34,20 @@
 // disjoint banks (a group that straddles two halo rows can meet a bank twice, which a ds_write_b32 absorbs at no cost).
 // LDS per workgroup: 6 planes * 1099 + 5 maps * 26 * 32 floats = 43 016 bytes, three workgroups per CU.
 //
-// Reduction: the ticket pattern of k_adam_multi / k_image_sqerr_accumulate.  A lane adds its pixels in ascending (tile, channel, row)
-// order in double, the waves by a butterfly, the workgroup publishes its partial and takes a ticket; the workgroup that draws the last one
-// sums the partials in ascending order, divides, adds to the record and returns the workspace to zero.
+// Reduction: the ticket reduction of sn_reduce.h.  A lane adds its pixels in ascending (tile, channel, row) order in double; the workgroup
+// that draws the last ticket sums the partials (out of the maps' LDS), divides, adds to the record and returns the workspace to zero.
 //
 // k_image_range (only when data_range is derived): min and max of both images in one launch, consecutive dwords as above; a wave's
 // results enter the workspace through integer atomic maxima on an order-preserving key (of x for the maximum, of -x for the minimum; key 0
 // = nothing seen yet, so the workspace is zero at rest), a NaN through an atomic OR.  k_image_ssim decodes them on the same stream.
-#include "sn_common.h"
+#include "sn_reduce.h"
 
 namespace sn {
 
 constexpr uint32_t SS_TAPS = 11, SS_R = SS_TAPS / 2;
 constexpr uint32_t SS_TW = 32, SS_TH = 16;                              // interior pixels of a tile
 constexpr uint32_t SS_HW = SS_TW + 2 * SS_R, SS_HH = SS_TH + 2 * SS_R;  // its halo: 42 x 26
-constexpr uint32_t SS_THREADS = 256;
+constexpr uint32_t SS_THREADS = SN_REDUCE_THREADS;
 constexpr uint32_t SS_PLANE = 1099;                                     // floats per channel plane: 26 * 42 = 1092, padded to 11 mod 32
 constexpr uint32_t SS_MAX_PARTIALS = 512;                               // workgroups of k_image_ssim (a workgroup loops over tiles beyond)
 constexpr uint32_t SS_MAX_RANGE_BLOCKS = 1024;
@@ -142,12 +141,6 @@ __device__ __forceinline__ void stage_halo(const float *__restrict__ img, uint32
     }
 }
 
-__device__ __forceinline__ double ssim_wave_sum(double v) {              // butterfly: the same order of additions in every run
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_image_ssim(const SsimArgs a) {
     SN_POISON_ALL();
     __shared__ float s_img[2 * 3 * SS_PLANE];                            // centred pred | truth, a plane per channel, rows of SS_HW floats
@@ -221,32 +214,11 @@ __global__ __launch_bounds__(256) void k_image_ssim(const SsimArgs a) {
         }
     }
 
-    // the workgroup's partial, the ticket (as publish_and_draw of mask_output.hip)
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    sum = ssim_wave_sum(sum);
-    if (lane == 0) s_wave[wave] = sum;
-    __syncthreads();
-    if (tid == 0) a.ws->part_sum[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        const uint32_t mine = __hip_atomic_fetch_add(&a.ws->ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        s_flag = mine == gridDim.x - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (s_flag == 0u) return;
-    __threadfence();
-    // the last workgroup: everyone has published (and has long read the range keys); the partials in ascending order, the workspace back to zero
-    double *s_part = reinterpret_cast<double *>(s_h);
-    for (uint32_t i = tid; i < gridDim.x; i += SS_THREADS) {
-        s_part[i] = __hip_atomic_load(&a.ws->part_sum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&a.ws->part_sum[i], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (!publish_and_draw(sum, 0u, &a.ws->ticket, a.ws->part_sum, nullptr, s_wave, nullptr, &s_flag)) return;
+    // the last workgroup: everyone has published (and has long read the range keys); the workspace back to zero
     if (tid < 4u) __hip_atomic_store(&a.ws->key[tid], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
+    const double total = sum_partials(a.ws->part_sum, nullptr, reinterpret_cast<double *>(s_h), nullptr, nullptr);
     if (tid == 0) {
-        double total = 0.0;
-        for (uint32_t i = 0; i < gridDim.x; ++i) total += s_part[i];
         const double value = total / (3.0 * (double)Hi * (double)Wi);
         a.rec->ssim_sum += value;                                        // SSIMMeter.V
         a.rec->last = value;
@@ -259,14 +231,6 @@ __global__ __launch_bounds__(256) void k_image_ssim(const SsimArgs a) {
 }  // namespace sn
 
 using namespace sn;
-
-#define SN_UNSUPPORTED(cond, ...)             \
-    do {                                      \
-        if (!(cond)) {                        \
-            ::sn::set_error(__VA_ARGS__);     \
-            return SN_ERR_UNSUPPORTED;        \
-        }                                     \
-    } while (0)
 
 extern "C" {
 
