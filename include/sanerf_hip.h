@@ -568,7 +568,9 @@ typedef struct sn_render_io {
     size_t       workspace_bytes;
 } sn_render_io;
 
-/* bytes of device workspace sn_rm_render_rays needs for N rays (tile_w as in sn_render_io) */
+/* bytes of device workspace sn_rm_render_rays needs for N rays (tile_w as in sn_render_io).  sn_rm_render_rays checks io->workspace_bytes
+ * against this figure before its first launch (SN_ERR_WORKSPACE): for every schedule, single-stage ones included, and for both row-band
+ * slots whenever the call is planned as two bands. */
 size_t sn_rm_render_workspace_bytes(const sn_render_cfg *cfg, uint32_t N, uint32_t tile_w);
 int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_stream_t stream);
 /* What the last sn_rm_render_rays call of THIS THREAD launched as its last stage (measurement: bench.py prices the gather stream of the
@@ -579,6 +581,11 @@ typedef struct sn_launch_info {
     uint32_t workgroups, lds_bytes, dense_levels, gathers_per_wave_sample, launches;
 } sn_launch_info;
 int sn_rm_last_launch_info(sn_launch_info *info);
+/* Dry run: what sn_rm_last_launch_info would report after a successful sn_rm_render_rays(cfg, io) -- the last chunk's workgroups, launches =
+ * last-stage launches over all chunks, all zero for skip_final -- from the same validation and the same route planning, on the host alone:
+ * nothing is launched, no pointer is dereferenced, io->workspace is not needed.  Same statuses and messages as sn_rm_render_rays.
+ * (lds_bytes is the dynamic LDS of the launch itself, the 84 KiB of SN_EXP_FINAL_ONE_WG included.) */
+int sn_rm_render_route_info(const sn_render_cfg *cfg, const sn_render_io *io, sn_launch_info *out);
 
 /* Feature-head accumulation, nerf/renderer.py:301-302 + 361: out[n, :] = sum_j weights[n,j] * grid(xyzs[n,j])
  * = composite(weights, s_grid(xyzs, bound)) without materialising the [N*T, L*C] per-sample features.

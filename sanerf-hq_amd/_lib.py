@@ -178,6 +178,7 @@ _SIGNATURES = {
     "sn_rm_feature_map": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "sn_rm_debug_occupancy": (_int, [_vp, _vp, _int]),
     "sn_rm_last_launch_info": (_int, [_vp]),
+    "sn_rm_render_route_info": (_int, [C.POINTER(RenderCfg), C.POINTER(RenderIO), _vp]),
     "sn_debug_eval": (_int, [_int, _vp, _vp, _u32, _vp, _vp]),
 }
 

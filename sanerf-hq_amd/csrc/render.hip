@@ -3128,16 +3128,6 @@ static uint32_t final_sp_max_rays(const sn_render_cfg *cfg) {
 // several-lanes-per-ray / role-split kernels, which all evaluate the third layer per sample)
 static bool lt_enabled(const sn_render_cfg *cfg) { return cfg->tuning.per_sample_form == 0; }
 
-// the role-split final stage (k_final_stage_rs, experiments builds) where it applies
-static bool rs_enabled(const sn_render_cfg *cfg) {
-#ifdef SN_EXPERIMENTS
-    return cfg->tuning.experiment == SN_EXP_ROLE_SPLIT;
-#else
-    (void)cfg;
-    return false;
-#endif
-}
-
 static uint32_t tile_log2w(const sn_render_cfg *cfg) { return (cfg && cfg->tuning.wave_tile >= 1 && cfg->tuning.wave_tile <= 5) ? (uint32_t)cfg->tuning.wave_tile : 3u; }
 static uint32_t blocks_for(uint32_t n, uint32_t W, uint32_t tlw) {
     if (W) {                                                      // four wave tiles of 2^tlw x 2^(6 - tlw) pixels each (ray_of_lane)
@@ -3312,6 +3302,10 @@ int sn_rm_debug_occupancy(int32_t *out, int32_t *lds, int n) {
     return SN_OK;
 }
 
+}  // extern "C"
+
+namespace sn {
+
 // Densified levels (round 3).  The first hashed levels of the main grid have few enough vertices (102^3, 148^3) to be re-laid out per
 // render call like the dense ones: one 16-byte pair / quad row per VERTEX, fetched through the hash once per vertex by k_pack_pairs
 // instead of once per sample-corner by the march.  The final stage then reads them with 4 (fp32) / 2 (fp16) aligned, spatially coherent
@@ -3336,7 +3330,7 @@ static int densify_levels(const GridLevels &g, int K, uint64_t samples, bool f16
 }
 
 // floats of a grid's packed pair / quad rows; densify_samples != 0: the main grid, whose levels 5-6 may be densified for this call
-// (sized by the same rule the launch applies: table dtype and tuning.densify)
+// (sized by table dtype and tuning.densify alone, so that the size does not depend on the outputs a call asks for)
 static size_t pair_floats_of(const sn_grid_desc *d, uint64_t densify_samples = 0, int densify_mode = 1) {
     GridLevels g;
     if (d->D != 3 || d->C != 2 || build_grid_levels(&g, d->offsets, d->D, d->C, d->L, d->S, d->H, d->gridtype, (int)d->align_corners, d->interp) != SN_OK) return 0;
@@ -3345,39 +3339,252 @@ static size_t pair_floats_of(const sn_grid_desc *d, uint64_t densify_samples = 0
     const int K = dense_prefix(g);
     return (size_t)pair_layout(g, densify_samples ? densify_levels(g, K, densify_samples, d->table_dtype == SN_F16, densify_mode) : K, off) * 4u;
 }
-static size_t pair_region_floats(const sn_render_cfg *cfg, uint64_t main_samples) {
-    size_t f = pair_floats_of(&cfg->grid, main_samples, cfg->tuning.densify);
-    for (uint32_t k = 0; k + 1 < cfg->num_stages && k < SN_MAX_STAGES; ++k) f += pair_floats_of(&cfg->prop_grid[k]);
-    return f;
+
+// does the grid have the FinalLv shape with K dense levels (given that its pair rows are packed)?
+static bool final_lv_fits(const GridLevels &g, int K, uint32_t row_bytes) {
+    FinalLv probe;
+    PairTab pt;
+    pt.base = &probe;
+    for (int l = 0; l < 8; ++l) pt.off[l] = 0;
+    return build_final_lv(g, K, pt, &probe, row_bytes, probe);
 }
 
-size_t sn_rm_render_workspace_bytes(const sn_render_cfg *cfg, uint32_t N, uint32_t tile_w) {
-    if (!cfg || N == 0) return (size_t)PACK_FLOATS * sizeof(float);
-    const BandPlan bp = band_plan(cfg, N, tile_w);
-    const uint32_t nc = bp.chunk < N ? bp.chunk : N;
-    const size_t npad = (size_t)blocks_for(nc, tile_w, tile_log2w(cfg)) * 256u;
-    const uint64_t samples = (uint64_t)N * cfg->num_steps[cfg->num_stages ? cfg->num_stages - 1 : 0];
-    return ((size_t)bp.slots * stage_scratch_floats(cfg, (uint32_t)npad) + (size_t)PACK_FLOATS + pair_region_floats(cfg, samples)) * sizeof(float);
+// ---- the route of a render call: what sn_rm_render_rays launches, decided on the host before anything is launched ----------------------
+// plan_render() is the only place where a kernel instantiation, a launch geometry or a workspace size is chosen; sn_rm_render_rays
+// launches what the route says, sn_rm_render_route_info reports it, sn_rm_render_workspace_bytes sizes the workspace with plan_workspace().
+
+constexpr int VIEW_W = 32 * 32 + 32 * 32 + 3 * 32;     // padded view_mlp rows
+static_assert(VIEW_W <= PACK_FLOATS, "view weights overlay the packed MLP weights");
+constexpr size_t LDS_F16X3 = (size_t)(PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE) * sizeof(float);      // 72 KiB: packed weights + two sample slabs per wave
+constexpr size_t LDS_F16X3_L0 = (size_t)(PACK_FLOATS + 4 * 2 * 64 * 16 + L0_MAX_ROWS) * sizeof(float);
+constexpr size_t LDS_MFMA32 = (size_t)(PACK_FLOATS + 4 * 32 * 64) * sizeof(float);                  // 64 KiB
+constexpr size_t LDS_VALU = (size_t)(2 * 64 * 256 + VIEW_W) * sizeof(float);                        // 136 KiB + the view weights
+
+// tuning.experiment as this build honours it (plan_render refuses a non-zero value on a build without the experiments)
+static int experiment_of(const sn_render_cfg *cfg) {
+#ifdef SN_EXPERIMENTS
+    return cfg->tuning.experiment;
+#else
+    (void)cfg;
+    return SN_EXP_NONE;
+#endif
 }
 
-int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_stream_t stream) {
-    SN_REQUIRE(cfg && io, "render_rays: cfg/io is NULL");
-    if (io->N == 0) return SN_OK;   // empty batch: nothing to launch, pointers may be NULL
-    g_launch = sn_launch_info{};
+struct FinalRoute {
+    enum Family { NONE, ANY, SP, CMP, RS, LT, LT_L0, PER_SAMPLE, MFMA32, VALU };
+    Family family = NONE;                  // NONE: skip_final
+    bool f16 = false;                      // table type
+    int K = -1;                            // dense levels the instantiation reads as packed rows (-1: level kind at run time)
+    bool aux = false, eo = false;          // AUX (last-stage weights out / early stop), EO (exact early-out)
+    int np = 3;                            // products per split multiply
+    uint32_t grid = 0, block = 256;
+    size_t lds = 0;                        // dynamic LDS bytes of the launch
+    const char *name = "";                 // what sn_launch_info reports, with the two figures below
+    int dense = 0;
+    uint32_t gathers = 0;
+    uint32_t lpr_log2 = 0, spl_log2 = 0;   // SP: lanes per ray, samples per lane
+};
+struct PropRoute {
+    int K = -1;                            // dense prefix the instantiation is built for (3, 2, or -1: run time)
+    bool f16 = false, sp = false, pair = false;
+    uint32_t lanes = 32, grid = 0;         // sp: lanes per ray
+};
+struct FeatRoute {
+    uint32_t C = 0, lg = 2, patch_levels = 0;        // level_dim, levels per workgroup pass, leading levels that run the LDS-patch instantiation
+    bool f16 = false;
+};
+struct ChunkRoute {                        // what depends on the rays of one chunk only through their number
+    uint32_t n = 0, nblk = 0, Npad = 0;
+    PropRoute prop[SN_MAX_STAGES];
+    FinalRoute fin;
+};
+struct WorkspacePlan {
+    BandPlan bands;
+    size_t pair_main = 0, pair_prop[SN_MAX_STAGES] = {};   // floats of the packed pair rows: main grid (sized for its densified layout), proposal grids
+    size_t pair_floats = 0, slot_floats = 0;         // all pair rows; stage scratch of one band slot
+    size_t head_floats() const { return (size_t)PACK_FLOATS + pair_floats; }
+    size_t bytes() const { return ((size_t)bands.slots * slot_floats + head_floats()) * sizeof(float); }
+};
+struct RenderRoute {
+    GridLevels gl_prop[SN_MAX_STAGES], gl_main, gl_feat;
+    bool is_main = false, is_any = false;
+    AnyShape any;
+    int mlp_mode = MLP_F16X3, mlp_np = 3;
+    bool use_cmp = false;
+    int Kmain = -1;                        // dense prefix of the main grid if it has the FinalLv shape, else -1
+    int Kv_main = 0;                       // levels of the main grid packed as pair rows for this call (7: levels 5-6 densified)
+    float stop_cum = 0.0f;
+    WorkspacePlan ws;
+    FinalRoute fin;                        // the last stage but for what depends on a chunk's ray count (plan_chunk completes it)
+    FeatRoute feat;
+    uint32_t chunks = 0;
+    ChunkRoute full, last;                 // every chunk but the last one; the last one (the only one of a call that fits one chunk)
+};
+
+static WorkspacePlan plan_workspace(const sn_render_cfg *cfg, uint32_t N, uint32_t W) {
+    WorkspacePlan w;
+    w.bands = band_plan(cfg, N, W);
+    const uint32_t nc = w.bands.chunk < N ? w.bands.chunk : N;
+    w.slot_floats = stage_scratch_floats(cfg, blocks_for(nc, W, tile_log2w(cfg)) * 256u);
+    w.pair_floats = w.pair_main = pair_floats_of(&cfg->grid, (uint64_t)N * cfg->num_steps[cfg->num_stages - 1], cfg->tuning.densify);
+    for (uint32_t k = 0; k + 1 < cfg->num_stages; ++k) w.pair_floats += w.pair_prop[k] = pair_floats_of(&cfg->prop_grid[k]);
+    return w;
+}
+
+// the io pointers every call needs (sn_rm_render_rays and sn_rm_render_route_info check them before plan_render)
+static int check_io_pointers(const sn_render_cfg *cfg, const sn_render_io *io) {
     SN_REQUIRE(io->rays_o && io->rays_d, "render_rays: rays must be device pointers");
-    if (io->skip_final) SN_REQUIRE(cfg->num_stages >= 2 && io->bins[cfg->num_stages - 1] && !cfg->with_feat,
+    if (io->skip_final) SN_REQUIRE(cfg->num_stages >= 2 && (cfg->num_stages > SN_MAX_STAGES /* refused below, by the num_stages check */ || io->bins[cfg->num_stages - 1]) && !cfg->with_feat,
                                    "render_rays: skip_final needs >= 2 stages, io->bins[last] for the resampled bins, and no feature stage");
     else SN_REQUIRE(io->image && io->depth && io->weights_sum, "render_rays: outputs must be device pointers");
+    return SN_OK;
+}
+
+// The last stage of the call, but for what depends on a chunk's ray count (plan_chunk).  The chain below is the ONE statement of which
+// kernel family runs when.
+static void plan_final(const sn_render_cfg *cfg, const sn_render_io *io, RenderRoute *r) {
+    const uint32_t S = cfg->num_stages;
+    const bool f16 = cfg->grid.table_dtype == SN_F16;
+    const int dp = dense_prefix(r->gl_main);
+    const uint64_t main_samples = (uint64_t)io->N * cfg->num_steps[S - 1];
+    r->Kv_main = r->is_any ? 0 : dp;
+    // pair rows of the main grid exist whenever it has a packable dense prefix; the kernels that read FinalLv need them
+    const bool have_pairs = !r->is_any && dp > 0 && r->ws.pair_main != 0;
+    r->Kmain = have_pairs && final_lv_fits(r->gl_main, dp, 2u * (f16 ? 2u : 4u)) ? dp : -1;      // the K = 5 instantiations read FinalLv
+    // opt-in compaction: k_final_stage_cmp replaces the last stage when nothing per-sample leaves the call (those tensors
+    // must be complete) and the table has the FinalLv shape; the proposal stages then drop waves of missed rays as well
+    if (cfg->compact_live && r->mlp_mode == MLP_F16X3 && !cfg->with_feat && !io->xyzs_last && !io->geo_feat_last && !io->skip_final &&
+        io->bins0_ray_stride == 0) {
+        bool any_dbg = false;
+        for (uint32_t k = 1; k < S; ++k) any_dbg = any_dbg || io->u_ray_stride[k] != 0;      // per-ray jitter tables: the default kernels
+        for (uint32_t k = 0; k < S; ++k) any_dbg = any_dbg || io->bins[k] || io->weights[k] || io->sigmas[k] || io->inds[k];
+        r->use_cmp = !any_dbg && dp == 5 && r->Kmain == 5;
+    }
+    if (io->skip_final) return;            // proposal stages only
+    // early termination is honoured only when nothing per-sample leaves the kernel (those tensors would be left unwritten past the stop)
+    const bool dbg_last = io->bins[S - 1] || io->weights[S - 1] || io->sigmas[S - 1] || io->xyzs_last || io->geo_feat_last;
+    const bool per_sample_out = dbg_last || cfg->with_feat;
+    r->stop_cum = (cfg->early_stop_eps > 0.0f && cfg->early_stop_eps < 1.0f && !per_sample_out) ? -logf(cfg->early_stop_eps) : 0.0f;
+    // gather instructions of one wave-sample = dense levels as packed rows (fp32 tables: pair rows, 4 loads; fp16: quad rows, 2 loads)
+    // + 8 corners per hashed level
+    auto lv_gathers = [&](int kd) -> uint32_t { return (uint32_t)kd * (f16 ? 2u : 4u) + (uint32_t)(16 - kd) * 8u; };
+    FinalRoute &f = r->fin;
+    f.f16 = f16;
+    f.aux = cfg->with_feat || r->stop_cum > 0.0f;
+    // exact early-out of the LAST stage (linear-tail instantiations): opt-in (tuning.exact_early_out = 2).  Measured on the opaque field
+    // (profiles/r04/bench_configs.json): behind proposal stages the last stage's 32 samples sit around the surface and the test buys nothing
+    // (1.953 vs 1.952 ms -- the proposal stages' own early-out, always on, is what takes that render from 3.19 to 1.95 ms) while it costs a
+    // semi-transparent scene 0.2-0.3 %; a single-stage schedule gains (6.07 -> 4.43 ms) but its kernel is the bench line's (0.5-1 % cost).
+    f.eo = cfg->tuning.exact_early_out == 2;
+    const int xp = experiment_of(cfg);
+    const bool f16x3 = r->mlp_mode == MLP_F16X3;
+    if (r->is_any) {      // sizes at run time.  (io->head_stride is accepted here although this kernel never writes the rgb | depth columns:
+                          //  ADVICE.md; plan_render's head_stride check is the place to refuse it)
+        f.family = FinalRoute::ANY; f.name = "k_final_stage_any";
+        f.lds = (size_t)(2u * r->any.rows + (r->any.dg[r->any.ng] - 1u)) * 256u * sizeof(float);
+        f.dense = 0; f.gathers = cfg->grid.L * 8u;
+    } else if (r->use_cmp) {
+        // per-ray termination + live-sample compaction (k_final_stage_cmp); f_image stays available
+        f.family = FinalRoute::CMP; f.name = "k_final_stage_cmp"; f.K = 5; f.lds = LDS_F16X3; f.dense = 5; f.gathers = lv_gathers(5);
+    } else if (f16x3 && r->Kmain == 5 && !f.aux && !per_sample_out && xp == SN_EXP_ROLE_SPLIT) {
+        // role-split waves (k_final_stage_rs, experiments builds): 768-thread workgroups over 32x16-pixel tiles (512 rays in linear order)
+        f.family = FinalRoute::RS; f.name = "k_final_stage_rs"; f.K = 5; f.dense = 5; f.gathers = lv_gathers(5);
+    } else if (f16x3 && r->Kmain == 5 && !dbg_last && lt_enabled(cfg)) {
+        // linear tail: layer 3 off the matrix cores (per-sample geometry features are not available in this form)
+        // SN_EXP_LDS_LEVEL0 (opt-in, experiments builds): fp16 tables whose level 0 fits 16 KiB keep that level LDS-resident.  Bit-identical
+        // and measured SLOWER than the texture path (800x800 [128]: 6.44 -> 6.58 ms, profiles/r03/ab_round3_experiments.txt): with fp16
+        // tables the kernel is not bound by the texture addressers, and the 8 ds_read_b32 + swizzled slab addressing cost more than 2 gathers save
+        const bool l0 = f16 && (uint64_t)r->gl_main.res[0] * r->gl_main.res[0] * r->gl_main.res[0] <= (uint64_t)L0_MAX_ROWS && xp == SN_EXP_LDS_LEVEL0;
+        // levels 5 and 6 densified for this call (densify_levels): only the plain instantiation reads them, and compact_live keeps K = 5
+        if (!f.aux && !cfg->compact_live) r->Kv_main = densify_levels(r->gl_main, 5, main_samples, f16, cfg->tuning.densify);
+        const bool dens = r->Kv_main == 7 && !l0 && final_lv_fits(r->gl_main, 7, 2u * (f16 ? 2u : 4u));
+        f.family = l0 ? FinalRoute::LT_L0 : FinalRoute::LT;
+        f.K = dens ? 7 : 5;
+        f.name = l0 ? "k_final_stage<lt,K=5,lds-level0>" : dens ? "k_final_stage<lt,K=7>" : f.aux ? "k_final_stage<lt,K=5,aux>" : "k_final_stage<lt,K=5>";
+        f.dense = f.K; f.gathers = lv_gathers(f.K) - (l0 ? 2u : 0u);
+        // SN_MLP_F16X1: the reduced form of the plain launch with fp16 tables
+        if (f16 && !f.eo && r->mlp_np == 1 && !f.aux && !l0) f.np = 1;
+        // SN_EXP_FINAL_ONE_WG (round 6): the last stage asks for 84 KiB of LDS, so only ONE of its workgroups fits a CU and half of every SIMD's
+        // registers stay free for the proposal-stage workgroups of the OTHER row band (tuning.band_streams): vector-ALU-bound waves beside
+        // texture-bound ones on the same SIMD instead of on different CUs
+        f.lds = l0 ? LDS_F16X3_L0 : (xp == SN_EXP_FINAL_ONE_WG && !dens && f.np == 3) ? (size_t)(84 * 1024) : LDS_F16X3;
+    } else if (f16x3) {
+        f.family = FinalRoute::PER_SAMPLE; f.K = r->Kmain == 5 ? 5 : -1; f.lds = LDS_F16X3;           // main grid: levels 0-4 dense
+        f.name = r->Kmain == 5 ? "k_final_stage<per-sample,K=5>" : "k_final_stage<per-sample,generic>";
+        f.dense = r->Kmain; f.gathers = r->Kmain == 5 ? lv_gathers(5) : (uint32_t)dp * 4u + (16u - (uint32_t)dp) * 8u;
+    } else if (r->mlp_mode == MLP_F32) {
+        f.family = FinalRoute::MFMA32; f.name = "k_final_stage<mfma32>"; f.aux = true; f.lds = LDS_MFMA32; f.dense = -1; f.gathers = 16u * 8u;
+    } else {
+        f.family = FinalRoute::VALU; f.name = "k_final_stage<valu>"; f.aux = true; f.lds = LDS_VALU; f.dense = -1; f.gathers = 16u * 8u;
+    }
+}
+
+// the launches of one chunk of n rays
+static ChunkRoute plan_chunk(const sn_render_cfg *cfg, const sn_render_io *io, const RenderRoute &r, uint32_t n) {
+    const uint32_t S = cfg->num_stages, W = io->tile_w;
+    ChunkRoute c;
+    c.n = n; c.nblk = blocks_for(n, W, tile_log2w(cfg)); c.Npad = c.nblk * 256u;
+    for (uint32_t k = 0; k + 1 < S; ++k) {
+        PropRoute &p = c.prop[k];
+        const int K = dense_prefix(r.gl_prop[k]);
+        p.K = (K == 3 || K == 2) ? K : -1;       // prop0: res 16, 27, 46 dense (network.py:135); prop1: res 16, 32 dense (network.py:140)
+        p.f16 = cfg->prop_grid[k].table_dtype != SN_F32;
+        // few rays in linear order (training batches): several lanes per ray instead of one (k_prop_stage_sp)
+        p.sp = W == 0 && n <= prop_sp_max_rays(cfg) && cfg->num_steps[k] <= SP_MAX_T;
+        // lanes per ray of the small-batch kernel (tuning.prop_sp_lanes forces 8 / 16 / 32)
+        p.lanes = 32u;      // (measured, profiles/r06/prop_sp_lanes_ab.json: 32 lanes are the fastest from 1024 to 32768 rays)
+        if (cfg->tuning.prop_sp_lanes == 8 || cfg->tuning.prop_sp_lanes == 16 || cfg->tuning.prop_sp_lanes == 32) p.lanes = (uint32_t)cfg->tuning.prop_sp_lanes;
+        // two samples of a ray at once (k_prop_stage<..., UN = 2>): tuning.prop_pair 2 = always, 1 = never, 0 = automatic
+        p.pair = cfg->tuning.prop_pair == 2 ||
+                 (cfg->tuning.prop_pair == 0 && prop_pair_auto(r.ws.bands.slots == 2u ? blocks_for(io->N, W, tile_log2w(cfg)) : c.nblk));   // (two bands run side by side)
+        p.grid = p.sp ? c.Npad / (256u / p.lanes) : c.nblk;   // sp: every scratch column, like the one-lane-per-ray launch
+    }
+    c.fin = r.fin;
+    FinalRoute &f = c.fin;
+    f.grid = c.nblk;
+    const uint32_t T = cfg->num_steps[S - 1];
+#ifdef SN_EXPERIMENTS
+    if (f.family == FinalRoute::RS) {
+        f.grid = W ? ((W + 31u) >> 5) * ((n / W + 15u) >> 4) : div_up(n, (uint32_t)(RS_PROD * 64));
+        f.block = RS_THREADS; f.lds = (size_t)RS_LDS_FLOATS * sizeof(float);
+    }
+#endif
+    // few rays in linear order: lanes share rays (k_final_stage_sp); fewer samples per lane while CUs would idle
+    if (f.family != FinalRoute::NONE && f.family != FinalRoute::ANY && W == 0 && r.mlp_mode == MLP_F16X3 && r.stop_cum == 0.0f && !r.use_cmp &&
+        n <= final_sp_max_rays(cfg) && T <= 64u * FSP_MAX_SPL) {
+        auto lpr_log2_of = [&](uint32_t sl) { const uint32_t need = div_up(T, 1u << sl); uint32_t l2 = 0; while ((1u << l2) < need) ++l2; return l2; };
+        uint32_t spl_log2 = 2;
+        while (spl_log2 > 0 && div_up(T, 1u << (spl_log2 - 1)) <= 64u && (((size_t)c.Npad << lpr_log2_of(spl_log2)) >> 8) < SN_FINAL_SP_MIN_BLOCKS) --spl_log2;
+        FinalRoute sp;
+        sp.family = FinalRoute::SP; sp.name = "k_final_stage_sp"; sp.f16 = f.f16; sp.K = r.Kmain == 5 ? 5 : -1;
+        sp.spl_log2 = spl_log2; sp.lpr_log2 = lpr_log2_of(spl_log2);
+        sp.grid = (uint32_t)(((size_t)c.Npad << sp.lpr_log2) >> 8);
+        sp.lds = final_sp_lds_floats(1u << spl_log2) * sizeof(float);
+        sp.dense = r.Kmain; sp.gathers = r.Kmain == 5 ? (uint32_t)5 * (f.f16 ? 2u : 4u) + 11u * 8u : 16u * 8u;
+        f = sp;
+    }
+    return c;
+}
+
+static void plan_chunks(const sn_render_cfg *cfg, const sn_render_io *io, RenderRoute *r) {
+    const uint32_t chunk = r->ws.bands.chunk;
+    r->chunks = div_up(io->N, chunk);
+    r->full = plan_chunk(cfg, io, *r, io->N < chunk ? io->N : chunk);
+    const uint32_t n_last = io->N - (r->chunks - 1u) * chunk;
+    r->last = n_last == r->full.n ? r->full : plan_chunk(cfg, io, *r, n_last);
+}
+
+// Validates cfg / io (all but the workspace) and fills *r.  Calls no HIP API, touches no global.  io->N >= 1 and check_io_pointers() passed.
+static int plan_render(const sn_render_cfg *cfg, const sn_render_io *io, RenderRoute *r) {
     SN_REQUIRE(io->out_stride == 0u || io->out_stride >= 5u, "render_rays: out_stride %u must be 0 (dense outputs) or at least 5 floats (rgb | depth | weights_sum per row)", io->out_stride);
     SN_REQUIRE(io->head_stride == 0u || (io->f_image && io->head_stride >= 31u + 4u && !io->skip_final),
                "render_rays: head_stride %u needs f_image and room for f_image | rgb | depth (>= 35 floats per row)", io->head_stride);
     SN_REQUIRE(cfg->tuning.wave_tile >= 0 && cfg->tuning.wave_tile <= 5, "render_rays: tuning.wave_tile %d outside 0..5", cfg->tuning.wave_tile);
-    SN_REQUIRE(!(rs_enabled(cfg) && cfg->tuning.wave_tile != 0 && cfg->tuning.wave_tile != 3), "render_rays: the role-split experiment is built for 8x8 wave tiles (tuning.wave_tile 0 or 3)");
+    SN_REQUIRE(!(experiment_of(cfg) == SN_EXP_ROLE_SPLIT && cfg->tuning.wave_tile != 0 && cfg->tuning.wave_tile != 3), "render_rays: the role-split experiment is built for 8x8 wave tiles (tuning.wave_tile 0 or 3)");
     const uint32_t S = cfg->num_stages;
     SN_REQUIRE(S >= 1 && S <= SN_MAX_STAGES, "render_rays: num_stages=%u outside 1..%d", S, SN_MAX_STAGES);
     for (uint32_t k = 0; k < S; ++k) SN_REQUIRE(cfg->num_steps[k] >= 1, "render_rays: num_steps[%u] must be >= 1", k);
     SN_REQUIRE(cfg->sh_degree == 4, "render_rays: fused path is built for SH degree 4 (network.py:97), got %u", cfg->sh_degree);
-    if (io->N == 0) return SN_OK;
     if (io->tile_w) SN_REQUIRE(io->N % io->tile_w == 0, "render_rays: N=%u is not a multiple of tile_w=%u", io->N, io->tile_w);
     // per-ray tables: a row holds T+1 values (sanerf_hip.h); a shorter stride would read past the caller's rows
     SN_REQUIRE(io->bins0_ray_stride == 0 || (io->bins0_table && io->bins0_ray_stride >= cfg->num_steps[0] + 1u),
@@ -3385,32 +3592,27 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
     for (uint32_t k = 1; k < S; ++k)
         SN_REQUIRE(io->u_ray_stride[k] == 0 || (io->u_table[k] && io->u_ray_stride[k] >= cfg->num_steps[k] + 1u),
                    "render_rays: u_ray_stride[%u]=%u needs u_table[%u] and at least num_steps[%u]+1=%u values per ray", k, io->u_ray_stride[k], k, k, cfg->num_steps[k] + 1u);
-    const hipStream_t st_main = (hipStream_t)stream;
-    hipStream_t st = st_main;      // (the chunk loop below shadows it with the chunk's own stream when the image is rendered as bands on two streams)
 
-    // ---- which kernel instantiations does this configuration map to? ----
+    // ---- which field is this? ----
     static const uint32_t d_prop[3] = {10, 16, 1};
     static const uint32_t d_main[4] = {32, 64, 64, 16};
     static const uint32_t d_view[4] = {31, 32, 32, 3};
-    GridLevels gl_prop[SN_MAX_STAGES], gl_main;
     for (uint32_t k = 0; k + 1 < S; ++k) {
-        int rc = to_levels(&gl_prop[k], &cfg->prop_grid[k]);
+        int rc = to_levels(&r->gl_prop[k], &cfg->prop_grid[k]);
         if (rc) return rc;
-        if (!(cfg->prop_grid[k].L == 5 && cfg->prop_grid[k].C == 2 && mlp_is(&cfg->prop_mlp[k], 2, d_prop) && levels_fast(gl_prop[k]))) {
+        if (!(cfg->prop_grid[k].L == 5 && cfg->prop_grid[k].C == 2 && mlp_is(&cfg->prop_mlp[k], 2, d_prop) && levels_fast(r->gl_prop[k]))) {
             set_error("render_rays: proposal stage %u is not the L=5,F=2 grid + 10-16-1 bias-free ReLU MLP this build fuses (network.py:135-143)", k);
             return SN_ERR_UNSUPPORTED;
         }
     }
     {
-        int rc = to_levels(&gl_main, &cfg->grid);
+        int rc = to_levels(&r->gl_main, &cfg->grid);
         if (rc) return rc;
     }
-    const bool is_main = cfg->grid.L == 16 && cfg->grid.C == 2 && mlp_is(&cfg->grid_mlp, 3, d_main) && mlp_is(&cfg->view_mlp, 3, d_view) && levels_fast(gl_main);
+    r->is_main = cfg->grid.L == 16 && cfg->grid.C == 2 && mlp_is(&cfg->grid_mlp, 3, d_main) && mlp_is(&cfg->view_mlp, 3, d_view) && levels_fast(r->gl_main);
     // any other field of the same structure (sizes at run time: k_final_stage_any; BASELINE configs[0] is one)
-    AnyShape any_shape;
-    memset(&any_shape, 0, sizeof(any_shape));
-    bool is_any = false;
-    if (!is_main) {
+    memset(&r->any, 0, sizeof(r->any));
+    if (!r->is_main) {
         const sn_mlp_desc *gm = &cfg->grid_mlp, *vm = &cfg->view_mlp;
         auto plain = [](const sn_mlp_desc *m) {
             if (m->num_layers < 1u || m->num_layers > ANY_LAYERS || m->activation != 0u || m->skip_mask != 0u) return false;
@@ -3418,94 +3620,237 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
             for (uint32_t l = 0; l <= m->num_layers; ++l) if (m->dims[l] < 1u || m->dims[l] > ANY_W) return false;
             return true;
         };
-        is_any = cfg->grid.D == 3 && cfg->grid.C == 2 && cfg->grid.L >= 1 && cfg->grid.L * 2u <= ANY_W && plain(gm) && plain(vm) &&
-                 gm->dims[0] == cfg->grid.L * 2u && gm->dims[gm->num_layers] >= 2u && gm->dims[gm->num_layers] - 1u <= ANY_GEO &&
-                 cfg->sh_degree == 4u && vm->dims[0] == gm->dims[gm->num_layers] - 1u + 16u && vm->dims[vm->num_layers] == 3u;
-        if (is_any) {
-            any_shape.ng = gm->num_layers; any_shape.nv = vm->num_layers;
-            for (uint32_t l = 0; l <= gm->num_layers; ++l) any_shape.dg[l] = gm->dims[l];
-            for (uint32_t l = 0; l <= vm->num_layers; ++l) any_shape.dv[l] = vm->dims[l];
-            for (uint32_t l = 0; l < gm->num_layers; ++l) any_shape.wg[l] = gm->weight[l];
-            for (uint32_t l = 0; l < vm->num_layers; ++l) any_shape.wv[l] = vm->weight[l];
+        r->is_any = cfg->grid.D == 3 && cfg->grid.C == 2 && cfg->grid.L >= 1 && cfg->grid.L * 2u <= ANY_W && plain(gm) && plain(vm) &&
+                    gm->dims[0] == cfg->grid.L * 2u && gm->dims[gm->num_layers] >= 2u && gm->dims[gm->num_layers] - 1u <= ANY_GEO &&
+                    cfg->sh_degree == 4u && vm->dims[0] == gm->dims[gm->num_layers] - 1u + 16u && vm->dims[vm->num_layers] == 3u;
+        if (r->is_any) {
+            AnyShape &a = r->any;
+            a.ng = gm->num_layers; a.nv = vm->num_layers;
+            for (uint32_t l = 0; l <= gm->num_layers; ++l) a.dg[l] = gm->dims[l];
+            for (uint32_t l = 0; l <= vm->num_layers; ++l) a.dv[l] = vm->dims[l];
+            for (uint32_t l = 0; l < gm->num_layers; ++l) a.wg[l] = gm->weight[l];
+            for (uint32_t l = 0; l < vm->num_layers; ++l) a.wv[l] = vm->weight[l];
             uint32_t wmax = 0;
             for (uint32_t l = 0; l <= gm->num_layers; ++l) wmax = gm->dims[l] > wmax ? gm->dims[l] : wmax;
             for (uint32_t l = 0; l <= vm->num_layers; ++l) wmax = vm->dims[l] > wmax ? vm->dims[l] : wmax;
-            any_shape.rows = wmax <= 16u ? 16u : wmax <= 32u ? 32u : 64u;
+            a.rows = wmax <= 16u ? 16u : wmax <= 32u ? 32u : 64u;
         }
     }
-    if (!is_main && !is_any) {
+    if (!r->is_main && !r->is_any) {
         set_error("render_rays: the field is neither the L=16,F=2 grid + 32-64-64-16 / 31-32-32-3 MLPs (network.py:93-98) nor of the shape the "
                   "size-agnostic final stage takes (3-D grid with level_dim 2 and <= 32 levels' worth of 64 features, bias-free ReLU MLPs of "
                   "<= 4 layers and <= 64 neurons, <= 31 geometry channels, degree-4 SH)");
         return SN_ERR_UNSUPPORTED;
     }
-    if (is_any && (cfg->compact_live || cfg->with_feat)) {
+    if (r->is_any && (cfg->compact_live || cfg->with_feat)) {
         set_error("render_rays: compact_live / the in-render feature stage are instantiated for the reference network's sizes only");
         return SN_ERR_UNSUPPORTED;
     }
-    GridLevels gl_feat;
-    int feat_lg = 2;   // levels per workgroup pass of the feature stage (more passes = more workgroups, fewer registers)
     if (cfg->with_feat) {
         SN_REQUIRE(io->f_feat, "render_rays: with_feat is set but io->f_feat is NULL");
         SN_REQUIRE(cfg->feat_grid.embeddings && table_aligned(cfg->feat_grid.embeddings) && table_aligned(io->f_feat),
                    "render_rays: feature grid table / f_feat must be 16-byte aligned device pointers");
-        int rc = to_levels(&gl_feat, &cfg->feat_grid);
+        int rc = to_levels(&r->gl_feat, &cfg->feat_grid);
         if (rc) return rc;
-        if (!levels_fast(gl_feat) || !(gl_feat.C == 2 || gl_feat.C == 4 || gl_feat.C == 8)) {
+        const GridLevels &gf = r->gl_feat;
+        if (!levels_fast(gf) || !(gf.C == 2 || gf.C == 4 || gf.C == 8)) {
             set_error("render_rays: feature grid must be a hash grid with level_dim 2/4/8, align_corners=False, linear "
                       "interpolation (network.py:103); use sn_rm_grid_composite for other grids");
             return SN_ERR_UNSUPPORTED;
         }
-        if (cfg->tuning.feat_levels) feat_lg = cfg->tuning.feat_levels;
-        if (feat_lg != 1 && feat_lg != 2 && feat_lg != 4) feat_lg = 2;
-        while (gl_feat.L % (uint32_t)feat_lg) feat_lg >>= 1;
+        int lg = 2;   // levels per workgroup pass of the feature stage (more passes = more workgroups, fewer registers)
+        if (cfg->tuning.feat_levels) lg = cfg->tuning.feat_levels;
+        if (lg != 1 && lg != 2 && lg != 4) lg = 2;
+        while (gf.L % (uint32_t)lg) lg >>= 1;
+        FeatRoute &ft = r->feat;
+        ft.C = gf.C; ft.lg = (uint32_t)lg; ft.f16 = cfg->feat_grid.table_dtype == SN_F16;
+        // dense prefix of the feature grid: its passes run the LDS-patch instantiation (k_feat_stage<..., PATCH = true>), the hashed rest the plain one
+        uint32_t n_dense = 0;
+        while (n_dense < gf.L && (gf.mode[n_dense] & 1u) == 0u) ++n_dense;
+        const uint32_t whole = ((n_dense + ft.lg - 1u) / ft.lg) * ft.lg;
+        ft.patch_levels = cfg->tuning.feat_patch != 1 ? 0u : whole > gf.L ? gf.L : whole;
     }
     // tuning.mlp_mode: SN_MLP_AUTO (fp16 hi/lo split on the matrix cores, fp32 accumulate, unless cfg->mlp_exact_fp32), SN_MLP_F16X3 (forced),
     //                  SN_MLP_MFMA32 (exact fp32 v_mfma_f32_32x32x2_f32), SN_MLP_VALU (vector-ALU fallback)
-    int mlp_mode = cfg->mlp_exact_fp32 ? MLP_F32 : MLP_F16X3;
-    int mlp_np = 3;                // products per split multiply (SN_MLP_F16X2 / SN_MLP_F16X1: opt-in reduced forms of the plain linear-tail launch with fp16 tables)
+    r->mlp_mode = cfg->mlp_exact_fp32 ? MLP_F32 : MLP_F16X3;
+    r->mlp_np = 3;                // products per split multiply (SN_MLP_F16X1: opt-in reduced form of the plain linear-tail launch with fp16 tables)
     switch (cfg->tuning.mlp_mode) {
-        case SN_MLP_F16X1: mlp_mode = MLP_F16X3; mlp_np = 1; break;
+        case SN_MLP_F16X1: r->mlp_mode = MLP_F16X3; r->mlp_np = 1; break;
         case SN_MLP_AUTO: break;
-        case SN_MLP_F16X3: mlp_mode = MLP_F16X3; break;
-        case SN_MLP_MFMA32: mlp_mode = MLP_F32; break;
-        case SN_MLP_VALU: mlp_mode = MLP_VALU; break;
+        case SN_MLP_F16X3: r->mlp_mode = MLP_F16X3; break;
+        case SN_MLP_MFMA32: r->mlp_mode = MLP_F32; break;
+        case SN_MLP_VALU: r->mlp_mode = MLP_VALU; break;
         default: set_error("render_rays: unknown tuning.mlp_mode=%d", cfg->tuning.mlp_mode); return SN_ERR_INVALID;
     }
     if (cfg->tuning.experiment != SN_EXP_NONE && !(sn_build_flags() & SN_BUILD_EXPERIMENTS)) {
         set_error("render_rays: tuning.experiment=%d needs a library built with -DSN_EXPERIMENTS (make exp)", cfg->tuning.experiment);
         return SN_ERR_UNSUPPORTED;
     }
-    const bool use_mfma = mlp_mode != MLP_VALU;
+    r->ws = plan_workspace(cfg, io->N, io->tile_w);
+    plan_final(cfg, io, r);
+    plan_chunks(cfg, io, r);
+    return SN_OK;
+}
 
+// sn_launch_info of one last-stage launch (launches accumulates over the chunks of a call)
+static void note_final(const FinalRoute &f, sn_launch_info *info) {
+    snprintf(info->final_kernel, sizeof(info->final_kernel), "%s", f.name);
+    info->workgroups = f.grid; info->lds_bytes = (uint32_t)f.lds; info->dense_levels = (uint32_t)(f.dense < 0 ? 0 : f.dense);
+    info->gathers_per_wave_sample = f.gathers; info->launches += 1u;
+}
+
+// ---- launching what a route says ----------------------------------------------------------------------------------------------------
+template <typename... P, typename... A>
+static int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &...args) {
+    if (lds) SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    return SN_OK;
+}
+
+using PropKern = void (*)(PropArgs);
+template <typename TT, int K> static PropKern prop_kernel_of(const PropRoute &p) {
+    if (p.sp) {
+        if (p.lanes == 8u) return k_prop_stage_sp<TT, 5, 2, 16, K, 8>;
+        if (p.lanes == 16u) return k_prop_stage_sp<TT, 5, 2, 16, K, 16>;
+        return k_prop_stage_sp<TT, 5, 2, 16, K, 32>;
+    }
+    if (p.pair) return k_prop_stage<TT, 5, 2, 16, K, 2>;
+    return k_prop_stage<TT, 5, 2, 16, K>;
+}
+static PropKern prop_kernel(const PropRoute &p) {
+    switch (p.K) {
+        case 3: return p.f16 ? prop_kernel_of<__half, 3>(p) : prop_kernel_of<float, 3>(p);
+        case 2: return p.f16 ? prop_kernel_of<__half, 2>(p) : prop_kernel_of<float, 2>(p);
+        default: return p.f16 ? prop_kernel_of<__half, -1>(p) : prop_kernel_of<float, -1>(p);
+    }
+}
+
+using FinalKern = void (*)(FinalArgs);
+// k_final_stage at the reference network's sizes
+template <typename TT, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3>
+static FinalKern fs() { return k_final_stage<TT, 16, 2, 64, 64, 16, 32, MODE, K, AUX, LT, L0L, EO, NP>; }
+template <typename TT> static FinalKern final_kernel_of(const FinalRoute &f) {
+    constexpr bool half = std::is_same<TT, __half>::value;
+    switch (f.family) {
+        case FinalRoute::CMP: return k_final_stage_cmp<TT, 5>;
+#ifdef SN_EXPERIMENTS
+        case FinalRoute::RS: return k_final_stage_rs<TT, 5>;
+        case FinalRoute::LT_L0:
+            if constexpr (half) return f.aux ? fs<__half, MLP_F16X3, 5, true, true, true>() : fs<__half, MLP_F16X3, 5, false, true, true>();
+            return nullptr;
+#endif
+        case FinalRoute::LT:
+            if constexpr (half) {
+                if (f.np == 1) return f.K == 7 ? fs<__half, MLP_F16X3, 7, false, true, false, false, 1>() : fs<__half, MLP_F16X3, 5, false, true, false, false, 1>();
+            }
+            if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, false, true, false, true>() : fs<TT, MLP_F16X3, 7, false, true, false, false>();
+            if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, true, true, false, true>() : fs<TT, MLP_F16X3, 5, true, true, false, false>();
+            return f.eo ? fs<TT, MLP_F16X3, 5, false, true, false, true>() : fs<TT, MLP_F16X3, 5, false, true, false, false>();
+        case FinalRoute::PER_SAMPLE:      // the plain instantiation unless the extras are on
+            if (f.K == 5) return f.aux ? fs<TT, MLP_F16X3, 5, true>() : fs<TT, MLP_F16X3, 5, false>();
+            return f.aux ? fs<TT, MLP_F16X3, -1, true>() : fs<TT, MLP_F16X3, -1, false>();
+        case FinalRoute::MFMA32: return fs<TT, MLP_F32, -1, true>();
+        case FinalRoute::VALU: return fs<TT, MLP_VALU, -1, true>();
+        default: return nullptr;          // (ANY and SP take further arguments: launch_final names them)
+    }
+}
+
+static int launch_final(const FinalRoute &f, hipStream_t st, const FinalArgs &fa, const AnyShape &any) {
+    const dim3 grid(f.grid), block(f.block);
+    switch (f.family) {
+        case FinalRoute::ANY:
+            return f.f16 ? launch(k_final_stage_any<__half>, grid, block, f.lds, st, fa, any) : launch(k_final_stage_any<float>, grid, block, f.lds, st, fa, any);
+        case FinalRoute::SP:
+            if (f.K == 5) return f.f16 ? launch(k_final_stage_sp<__half, 5>, grid, block, f.lds, st, fa, f.lpr_log2, f.spl_log2) : launch(k_final_stage_sp<float, 5>, grid, block, f.lds, st, fa, f.lpr_log2, f.spl_log2);
+            return f.f16 ? launch(k_final_stage_sp<__half, -1>, grid, block, f.lds, st, fa, f.lpr_log2, f.spl_log2) : launch(k_final_stage_sp<float, -1>, grid, block, f.lds, st, fa, f.lpr_log2, f.spl_log2);
+        default: {
+            const FinalKern kern = f.f16 ? final_kernel_of<__half>(f) : final_kernel_of<float>(f);
+            if (!kern) { set_error("render_rays: no kernel for the last-stage route %s", f.name); return SN_ERR_UNSUPPORTED; }
+            return launch(kern, grid, block, f.lds, st, fa);
+        }
+    }
+}
+
+using FeatKern = void (*)(FeatArgs);
+template <typename TT, int C> static FeatKern feat_kernel_of(uint32_t lg, bool patch) {
+    if (patch) {
+        if (lg == 4u) return k_feat_stage<TT, C, 4, true>;
+        if (lg == 2u) return k_feat_stage<TT, C, 2, true>;
+        return k_feat_stage<TT, C, 1, true>;
+    }
+    if (lg == 4u) return k_feat_stage<TT, C, 4>;
+    if (lg == 2u) return k_feat_stage<TT, C, 2>;
+    return k_feat_stage<TT, C, 1>;
+}
+static FeatKern feat_kernel(const FeatRoute &ft, bool patch) {
+    switch (ft.C) {
+        case 8: return ft.f16 ? feat_kernel_of<__half, 8>(ft.lg, patch) : feat_kernel_of<float, 8>(ft.lg, patch);
+        case 4: return ft.f16 ? feat_kernel_of<__half, 4>(ft.lg, patch) : feat_kernel_of<float, 4>(ft.lg, patch);
+        default: return ft.f16 ? feat_kernel_of<__half, 2>(ft.lg, patch) : feat_kernel_of<float, 2>(ft.lg, patch);
+    }
+}
+}  // namespace sn
+
+extern "C" {
+
+size_t sn_rm_render_workspace_bytes(const sn_render_cfg *cfg, uint32_t N, uint32_t tile_w) {
+    if (!cfg || N == 0 || cfg->num_stages < 1 || cfg->num_stages > SN_MAX_STAGES) return (size_t)PACK_FLOATS * sizeof(float);   // (sn_rm_render_rays refuses such a schedule)
+    return plan_workspace(cfg, N, tile_w).bytes();
+}
+
+int sn_rm_render_route_info(const sn_render_cfg *cfg, const sn_render_io *io, sn_launch_info *out) {
+    SN_REQUIRE(cfg && io && out, "render_route_info: cfg/io/out is NULL");
+    *out = sn_launch_info{};
+    if (io->N == 0) return SN_OK;
+    int rc = check_io_pointers(cfg, io);
+    if (rc) return rc;
+    RenderRoute route;
+    rc = plan_render(cfg, io, &route);
+    if (rc) return rc;
+    if (io->skip_final) return SN_OK;
+    note_final(route.last.fin, out);
+    out->launches = route.chunks;
+    return SN_OK;
+}
+
+int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_stream_t stream) {
+    SN_REQUIRE(cfg && io, "render_rays: cfg/io is NULL");
+    if (io->N == 0) return SN_OK;   // empty batch: nothing to launch, pointers may be NULL
+    g_launch = sn_launch_info{};
+    // ---- 1. pointers, 2. the route ----
+    int rc = check_io_pointers(cfg, io);
+    if (rc) return rc;
+    RenderRoute route;
+    rc = plan_render(cfg, io, &route);
+    if (rc) return rc;
     SN_REQUIRE(io->workspace != nullptr, "render_rays: workspace is NULL");
     SN_REQUIRE(table_aligned(io->workspace), "render_rays: workspace must be 16-byte aligned");
+    // Checked before anything is written to the workspace, for what sn_rm_render_workspace_bytes states: the packs' region too (a single-stage
+    // call has no scratch behind it), and both band slots even if the side stream should turn out not to be available below.
+    if (io->workspace_bytes / sizeof(float) < route.ws.bytes() / sizeof(float)) {
+        set_error("render_rays: workspace too small (%zu bytes, need %zu)", io->workspace_bytes, route.ws.bytes());
+        return SN_ERR_WORKSPACE;
+    }
+    const uint32_t S = cfg->num_stages, W = io->tile_w;
+    const hipStream_t st_main = (hipStream_t)stream;
+    const GridLevels &gl_main = route.gl_main;
     float *pack = reinterpret_cast<float *>(io->workspace);
-    const uint64_t main_samples = (uint64_t)io->N * cfg->num_steps[S - 1];
-    const size_t pair_floats = pair_region_floats(cfg, main_samples);       // (as sn_rm_render_workspace_bytes sized it)
-    // will the last stage run as the plain linear-tail kernel?  Only that one has the instantiation that reads densified levels.
-    const bool plain_lt = mlp_mode == MLP_F16X3 && lt_enabled(cfg) && !rs_enabled(cfg) && !cfg->with_feat && !cfg->compact_live && !io->skip_final &&
-                          !(cfg->early_stop_eps > 0.0f && cfg->early_stop_eps < 1.0f) && dense_prefix(gl_main) == 5 &&
-                          !(io->bins[S - 1] || io->weights[S - 1] || io->sigmas[S - 1] || io->xyzs_last || io->geo_feat_last);
-    const int Kv_main = plain_lt ? densify_levels(gl_main, 5, main_samples, cfg->grid.table_dtype == SN_F16, cfg->tuning.densify) : dense_prefix(gl_main);
     float *pair_mem = pack + PACK_FLOATS;
-    float *scratch = pair_mem + pair_floats;
-    const size_t head_floats = (size_t)PACK_FLOATS + pair_floats;
-    const size_t scratch_floats_avail = io->workspace_bytes / sizeof(float) > head_floats ? io->workspace_bytes / sizeof(float) - head_floats : 0;
-    PairTab pairs;
-    pairs.base = nullptr;
-    for (int l = 0; l < 8; ++l) pairs.off[l] = 0;
-    if (use_mfma && !is_any) {
-        ProfScope ps(st, PK_PACK);
-        if (mlp_mode == MLP_F16X3)
-            hipLaunchKernelGGL(k_pack_grid_mlp_f16, dim3(PACK16_VECS * 64 / 256), dim3(256), 0, st, cfg->grid_mlp.weight[0],
-                               cfg->grid_mlp.weight[1], cfg->grid_mlp.weight[2], reinterpret_cast<uint4 *>(pack));
+    float *scratch = pair_mem + route.ws.pair_floats;
+
+    // ---- 3. weights and pair rows, packed on the caller's stream ----
+    if (route.mlp_mode != MLP_VALU && !route.is_any) {
+        ProfScope ps(st_main, PK_PACK);
+        if (route.mlp_mode == MLP_F16X3)
+            rc = launch(k_pack_grid_mlp_f16, dim3(PACK16_VECS * 64 / 256), dim3(256), 0, st_main, cfg->grid_mlp.weight[0], cfg->grid_mlp.weight[1],
+                        cfg->grid_mlp.weight[2], reinterpret_cast<uint4 *>(pack));
         else
-            hipLaunchKernelGGL(k_pack_grid_mlp, dim3(PACK_FLOATS / 256), dim3(256), 0, st, cfg->grid_mlp.weight[0], cfg->grid_mlp.weight[1], cfg->grid_mlp.weight[2], pack);
+            rc = launch(k_pack_grid_mlp, dim3(PACK_FLOATS / 256), dim3(256), 0, st_main, cfg->grid_mlp.weight[0], cfg->grid_mlp.weight[1], cfg->grid_mlp.weight[2], pack);
+        if (rc) return rc;
         SN_LAUNCH_CHECK("k_pack_grid_mlp");
     }
     // aligned x-pair rows of every grid's dense levels (PairTab), re-packed on every call: the call stays stateless
-    PairTab prop_pairs[SN_MAX_STAGES];
+    PairTab pairs, prop_pairs[SN_MAX_STAGES];
     {
         float *cursor = pair_mem;
         auto pack_pairs = [&](const sn_grid_desc *d, const GridLevels &gl, PairTab &pt, int Kp, size_t fl) -> int {
@@ -3518,83 +3863,68 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
             uint32_t max_rows = 0;
             for (int l = 0; l < Kp; ++l) { const uint32_t r3 = gl.res[l] * gl.res[l] * gl.res[l]; if (r3 > max_rows) max_rows = r3; }
             const dim3 gp(div_up(max_rows, 256), (uint32_t)Kp);
-            if (d->table_dtype == SN_F16) hipLaunchKernelGGL(k_pack_pairs<__half>, gp, dim3(256), 0, st, (const __half *)d->embeddings, gl, pt, (uint32_t)Kp);
-            else hipLaunchKernelGGL(k_pack_pairs<float>, gp, dim3(256), 0, st, (const float *)d->embeddings, gl, pt, (uint32_t)Kp);
+            const int rcl = d->table_dtype == SN_F16 ? launch(k_pack_pairs<__half>, gp, dim3(256), 0, st_main, (const __half *)d->embeddings, gl, pt, (uint32_t)Kp)
+                                                     : launch(k_pack_pairs<float>, gp, dim3(256), 0, st_main, (const float *)d->embeddings, gl, pt, (uint32_t)Kp);
+            if (rcl) return rcl;
             SN_LAUNCH_CHECK("k_pack_pairs");
             return SN_OK;
         };
-        ProfScope ps(st, PK_PACK);
+        ProfScope ps(st_main, PK_PACK);
         // (the main grid's region is sized for the densified layout whenever the sample count allows it; levels 5-6 are packed only
         //  when the kernel that reads them will run)
-        int rcp = pack_pairs(&cfg->grid, gl_main, pairs, is_any ? 0 : Kv_main, pair_floats_of(&cfg->grid, main_samples, cfg->tuning.densify));
-        if (rcp) return rcp;
+        rc = pack_pairs(&cfg->grid, gl_main, pairs, route.Kv_main, route.ws.pair_main);
+        if (rc) return rc;
         for (uint32_t k = 0; k + 1 < S; ++k) {
-            rcp = pack_pairs(&cfg->prop_grid[k], gl_prop[k], prop_pairs[k], dense_prefix(gl_prop[k]), pair_floats_of(&cfg->prop_grid[k]));
-            if (rcp) return rcp;
+            rc = pack_pairs(&cfg->prop_grid[k], route.gl_prop[k], prop_pairs[k], dense_prefix(route.gl_prop[k]), route.ws.pair_prop[k]);
+            if (rc) return rc;
         }
     }
 
-    // opt-in compaction: k_final_stage_cmp replaces the last stage when nothing per-sample leaves the call (those tensors
-    // must be complete) and the table has the FinalLv shape; the proposal stages then drop waves of missed rays as well
-    bool use_cmp = false;
-    if (cfg->compact_live && mlp_mode == MLP_F16X3 && !cfg->with_feat && !io->xyzs_last && !io->geo_feat_last && !io->skip_final &&
-        io->bins0_ray_stride == 0) {
-        bool any_dbg = false;
-        for (uint32_t k = 1; k < S; ++k) any_dbg = any_dbg || io->u_ray_stride[k] != 0;      // per-ray jitter tables: the default kernels
-        for (uint32_t k = 0; k < S; ++k) any_dbg = any_dbg || io->bins[k] || io->weights[k] || io->sigmas[k] || io->inds[k];
-        FinalLv probe;
-        use_cmp = !any_dbg && dense_prefix(gl_main) == 5 &&
-                  build_final_lv(gl_main, 5, pairs, cfg->grid.embeddings, 2u * (cfg->grid.table_dtype == SN_F16 ? 2u : 4u), probe);
-    }
-    const uint32_t W = io->tile_w;
-    const BandPlan bplan = band_plan(cfg, io->N, W);
-    const uint32_t chunk = bplan.chunk;
+    // ---- 4. the chunks ----
     // two bands on two streams: everything above (weight and pair packs) is on the caller's stream, the fork waits for it
-    BandFork fork(st_main, bplan.slots == 2u && chunk < io->N);
-    uint32_t chunk_index = 0;
-    for (uint32_t first = 0; first < io->N; first += chunk, ++chunk_index) {
-        const uint32_t n = (io->N - first) < chunk ? (io->N - first) : chunk;
-        const uint32_t nblk = blocks_for(n, W, tile_log2w(cfg));
-        const uint32_t Npad = nblk * 256u;
-        const uint32_t slot = fork.side ? (chunk_index & 1u) : 0u;
-        hipStream_t st = slot ? fork.side : st_main;                        // shadows the function-level `st`: this chunk's kernels and profile spans
-        const size_t slot_floats = stage_scratch_floats(cfg, blocks_for(chunk < io->N ? chunk : io->N, W, tile_log2w(cfg)) * 256u);
-        if ((size_t)(fork.side ? 2u : 1u) * slot_floats > scratch_floats_avail || stage_scratch_floats(cfg, Npad) > slot_floats) {
-            set_error("render_rays: workspace too small (%zu bytes, need %zu)", io->workspace_bytes,
-                      ((size_t)bplan.slots * slot_floats + head_floats) * sizeof(float));
-            return SN_ERR_WORKSPACE;
-        }
-        RayCommon rc;
-        rc.rays_o = io->rays_o + (size_t)first * 3; rc.rays_d = io->rays_d + (size_t)first * 3;
-        rc.cnf = io->cam_near_far ? io->cam_near_far + (size_t)first * 2 : nullptr;
-        rc.N = n; rc.W = W; rc.rows = W ? n / W : 0; rc.Npad = Npad;
-        for (int i = 0; i < 6; ++i) rc.aabb[i] = cfg->aabb[i];
-        rc.min_near = cfg->min_near; rc.bound = cfg->bound; rc.contract = cfg->contract;
-        rc.last_opaque = cfg->last_sample_opaque; rc.bg = cfg->bg_color;
+    BandFork fork(st_main, route.ws.bands.slots == 2u);
+    if (route.ws.bands.slots == 2u && !fork.side) {      // no side stream: the bands run one after the other in one slot, which the proposal routes count on
+        route.ws.bands.slots = 1u;
+        plan_chunks(cfg, io, &route);
+    }
+    const uint32_t chunk = route.ws.bands.chunk;
+    for (uint32_t ci = 0; ci < route.chunks; ++ci) {
+        const uint32_t first = ci * chunk;
+        const ChunkRoute &cr = ci + 1u < route.chunks ? route.full : route.last;
+        const uint32_t n = cr.n, Npad = cr.Npad;
+        const uint32_t slot = fork.side ? (ci & 1u) : 0u;
+        const hipStream_t st = slot ? fork.side : st_main;                  // this chunk's kernels and profile spans
+        RayCommon rays;
+        rays.rays_o = io->rays_o + (size_t)first * 3; rays.rays_d = io->rays_d + (size_t)first * 3;
+        rays.cnf = io->cam_near_far ? io->cam_near_far + (size_t)first * 2 : nullptr;
+        rays.N = n; rays.W = W; rays.rows = W ? n / W : 0; rays.Npad = Npad;
+        for (int i = 0; i < 6; ++i) rays.aabb[i] = cfg->aabb[i];
+        rays.min_near = cfg->min_near; rays.bound = cfg->bound; rays.contract = cfg->contract;
+        rays.last_opaque = cfg->last_sample_opaque; rays.bg = cfg->bg_color;
         {
             int e = 0;
             const float m = frexpf(2.0f * cfg->bound, &e);
-            rc.inv_den = (m == 0.5f && e > -100 && e < 100) ? 1.0f / (2.0f * cfg->bound) : 0.0f;
+            rays.inv_den = (m == 0.5f && e > -100 && e < 100) ? 1.0f / (2.0f * cfg->bound) : 0.0f;
         }
         {   // tuning.linear_tile_order disables the XCD-aware tile order (A/B switch)
-            rc.xcd_swizzle = cfg->tuning.linear_tile_order == 0;
-            rc.tlw = tile_log2w(cfg);
+            rays.xcd_swizzle = cfg->tuning.linear_tile_order == 0;
+            rays.tlw = tile_log2w(cfg);
             // compaction: workgroups differ in cost by the number of live rays of their tile; a contiguous tile range per
             // XCD would leave the XCDs that own empty image bands idle (measured on the small-aabb scene: 4.4 instead of
             // 3.0 ms), so tiles go round-robin over the XCDs in dispatch order
-            if (use_cmp) rc.xcd_swizzle = 0;
+            if (route.use_cmp) rays.xcd_swizzle = 0;
         }
 
         // scratch carve-up
         float *w_scr[SN_MAX_STAGES] = {nullptr}, *b_scr[SN_MAX_STAGES] = {nullptr};
-        float *cur = scratch + (size_t)slot * slot_floats;                    // (bands in flight on two streams: a scratch region each)
+        float *cur = scratch + (size_t)slot * route.ws.slot_floats;           // (bands in flight on two streams: a scratch region each)
         for (uint32_t k = 0; k + 1 < S; ++k) { w_scr[k] = cur; cur += (size_t)cfg->num_steps[k] * Npad; }
         for (uint32_t k = 1; k < S; ++k) { b_scr[k] = cur; cur += (size_t)(cfg->num_steps[k] + 1) * Npad; }
         if (cfg->with_feat) { w_scr[S - 1] = cur; cur += (size_t)cfg->num_steps[S - 1] * Npad; }
 
         for (uint32_t k = 0; k + 1 < S; ++k) {
             PropArgs pa;
-            pa.rc = rc; pa.g = gl_prop[k]; pa.table = cfg->prop_grid[k].embeddings;
+            pa.rc = rays; pa.g = route.gl_prop[k]; pa.table = cfg->prop_grid[k].embeddings;
             pa.w0 = cfg->prop_mlp[k].weight[0]; pa.w1 = cfg->prop_mlp[k].weight[1];
             pa.T = cfg->num_steps[k]; pa.Tn = cfg->num_steps[k + 1];
             pa.bins_in = b_scr[k];
@@ -3608,48 +3938,20 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
             pa.dbg_sigma = io->sigmas[k] ? io->sigmas[k] + (size_t)first * pa.T : nullptr;
             pa.dbg_inds = io->inds[k + 1] ? io->inds[k + 1] + (size_t)first * (pa.Tn + 1) : nullptr;
             pa.pairs = prop_pairs[k];
-            pa.skip_miss = use_cmp ? 1 : 0;
+            pa.skip_miss = route.use_cmp ? 1 : 0;
             {
                 ProfScope ps(st, PK_PROP0 + (int)k);
-                const int K = dense_prefix(gl_prop[k]);
-                const bool h16 = cfg->prop_grid[k].table_dtype != SN_F32;
-                // few rays in linear order (training batches): 8 lanes per ray instead of one (k_prop_stage_sp)
-                const bool sp = W == 0 && n <= prop_sp_max_rays(cfg) && pa.T <= SP_MAX_T;
-                // lanes per ray of the small-batch kernel: the fewest that still give >= 512 workgroups (tuning.prop_sp_lanes forces 8 / 16 / 32)
-                uint32_t lpr = 32u;      // (measured, profiles/r06/prop_sp_lanes_ab.json: 32 lanes are the fastest from 1024 to 32768 rays)
-                if (cfg->tuning.prop_sp_lanes == 8 || cfg->tuning.prop_sp_lanes == 16 || cfg->tuning.prop_sp_lanes == 32) lpr = (uint32_t)cfg->tuning.prop_sp_lanes;
-                const uint32_t nblk_sp = Npad / (256u / lpr);   // every scratch column, like the one-lane-per-ray launch
-                // two samples of a ray at once (k_prop_stage<..., UN = 2>): tuning.prop_pair 2 = always, 1 = never, 0 = automatic
-                const bool pair = cfg->tuning.prop_pair == 2 ||
-                                  (cfg->tuning.prop_pair == 0 && prop_pair_auto(fork.side ? blocks_for(io->N, W, tile_log2w(cfg)) : nblk));   // (two bands run side by side)
-#define SN_LAUNCH_PROP_SP(TT_, KK)                                                                                     \
-                do {                                                                                               \
-                    if (lpr == 8u) hipLaunchKernelGGL((k_prop_stage_sp<TT_, 5, 2, 16, KK, 8>), dim3(nblk_sp), dim3(256), 0, st, pa);        \
-                    else if (lpr == 16u) hipLaunchKernelGGL((k_prop_stage_sp<TT_, 5, 2, 16, KK, 16>), dim3(nblk_sp), dim3(256), 0, st, pa); \
-                    else hipLaunchKernelGGL((k_prop_stage_sp<TT_, 5, 2, 16, KK, 32>), dim3(nblk_sp), dim3(256), 0, st, pa);                 \
-                } while (0)
-#define SN_LAUNCH_PROP(KK)                                                                                         \
-                do {                                                                                               \
-                    if (sp && h16) SN_LAUNCH_PROP_SP(__half, KK);                                                  \
-                    else if (sp) SN_LAUNCH_PROP_SP(float, KK);                                                     \
-                    else if (h16 && pair) hipLaunchKernelGGL((k_prop_stage<__half, 5, 2, 16, KK, 2>), dim3(nblk), dim3(256), 0, st, pa); \
-                    else if (pair) hipLaunchKernelGGL((k_prop_stage<float, 5, 2, 16, KK, 2>), dim3(nblk), dim3(256), 0, st, pa); \
-                    else if (h16) hipLaunchKernelGGL((k_prop_stage<__half, 5, 2, 16, KK>), dim3(nblk), dim3(256), 0, st, pa); \
-                    else hipLaunchKernelGGL((k_prop_stage<float, 5, 2, 16, KK>), dim3(nblk), dim3(256), 0, st, pa);     \
-                } while (0)
-                if (K == 3) SN_LAUNCH_PROP(3);          // prop0: res 16, 27, 46 dense (network.py:135)
-                else if (K == 2) SN_LAUNCH_PROP(2);     // prop1: res 16, 32 dense (network.py:140)
-                else SN_LAUNCH_PROP(-1);
-#undef SN_LAUNCH_PROP_SP
-#undef SN_LAUNCH_PROP
+                rc = launch(prop_kernel(cr.prop[k]), dim3(cr.prop[k].grid), dim3(256), 0, st, pa);
+                if (rc) return rc;
             }
             SN_LAUNCH_CHECK("k_prop_stage");
         }
+        if (io->skip_final) continue;                      // proposal stages only: their last resampled bins went to io->bins[S-1]
+        const FinalRoute &fr = cr.fin;
         FinalArgs fa;
-        fa.rc = rc; fa.g = gl_main; fa.table = cfg->grid.embeddings; fa.mlp_pack = pack;
+        fa.rc = rays; fa.g = gl_main; fa.table = cfg->grid.embeddings; fa.mlp_pack = pack;
         for (int l = 0; l < 3; ++l) { fa.w[l] = cfg->grid_mlp.weight[l]; fa.vw[l] = cfg->view_mlp.weight[l]; }
         fa.T = cfg->num_steps[S - 1];
-        if (io->skip_final) continue;                      // proposal stages only: their last resampled bins went to io->bins[S-1]
         fa.bins_in = b_scr[S - 1]; fa.bins0_stride = io->bins0_ray_stride;
         fa.bins0_tab = (S == 1 && io->bins0_table) ? io->bins0_table + (size_t)first * fa.bins0_stride : nullptr;
         fa.sh_degree = cfg->sh_degree;
@@ -3659,239 +3961,43 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
         fa.dbg_w = io->weights[S - 1] ? io->weights[S - 1] + (size_t)first * fa.T : nullptr;
         fa.dbg_sigma = io->sigmas[S - 1] ? io->sigmas[S - 1] + (size_t)first * fa.T : nullptr;
         fa.dbg_xyz = io->xyzs_last ? io->xyzs_last + (size_t)first * fa.T * 3 : nullptr;
-        fa.dbg_geo = io->geo_feat_last ? io->geo_feat_last + (size_t)first * fa.T * 15 : nullptr;
-        fa.fimg_stride = io->head_stride ? io->head_stride : 31u;
+        const uint32_t geo = route.is_any ? route.any.dg[route.any.ng] - 1u : 15u;      // geometry channels
+        fa.dbg_geo = io->geo_feat_last ? io->geo_feat_last + (size_t)first * fa.T * geo : nullptr;
+        fa.fimg_stride = io->head_stride ? io->head_stride : geo + 16u;
         fa.dbg_fimg = io->f_image ? io->f_image + (size_t)first * fa.fimg_stride : nullptr;
-        fa.head_rgbd = (io->head_stride && io->f_image) ? fa.dbg_fimg + 31 : nullptr;
+        fa.head_rgbd = (io->head_stride && io->f_image && !route.is_any) ? fa.dbg_fimg + 31 : nullptr;
         fa.pairs = pairs;
-        const bool lv_ok = build_final_lv(gl_main, dense_prefix(gl_main), pairs, cfg->grid.embeddings,
-                                          2u * (cfg->grid.table_dtype == SN_F16 ? 2u : 4u), fa.lv);
+        build_final_lv(gl_main, fr.K == 7 ? 7 : dense_prefix(gl_main), pairs, cfg->grid.embeddings, 2u * (fr.f16 ? 2u : 4u), fa.lv);
         fa.w_out = cfg->with_feat ? w_scr[S - 1] : nullptr;
-        // early termination is honoured only when nothing per-sample leaves the kernel (those tensors would be left
-        // unwritten past the stop)
-        const bool per_sample_out = fa.dbg_bins || fa.dbg_w || fa.dbg_sigma || fa.dbg_xyz || fa.dbg_geo || fa.w_out;
-        fa.stop_cum = (cfg->early_stop_eps > 0.0f && cfg->early_stop_eps < 1.0f && !per_sample_out) ? -logf(cfg->early_stop_eps) : 0.0f;
-        const bool f16 = cfg->grid.table_dtype == SN_F16;
-        // what runs as the last stage (sn_rm_last_launch_info): gather instructions of one wave-sample = dense levels as packed rows
-        // (fp32 tables: pair rows, 4 loads; fp16: quad rows, 2 loads) + 8 corners per hashed level
-        auto lv_gathers = [&](int kd) -> uint32_t { return (uint32_t)kd * (f16 ? 2u : 4u) + (uint32_t)(16 - kd) * 8u; };
-        auto note = [&](const char *name, uint32_t wgs, size_t lds, int dense, uint32_t gpw) {
-            snprintf(g_launch.final_kernel, sizeof(g_launch.final_kernel), "%s", name);
-            g_launch.workgroups = wgs; g_launch.lds_bytes = (uint32_t)lds; g_launch.dense_levels = (uint32_t)(dense < 0 ? 0 : dense);
-            g_launch.gathers_per_wave_sample = gpw; g_launch.launches += 1u;
-        };
-        if (is_any) {     // sizes at run time
-            ProfScope ps_final(st, PK_FINAL);
-            note("k_final_stage_any", nblk, (size_t)(2u * any_shape.rows + (any_shape.dg[any_shape.ng] - 1u)) * 256u * sizeof(float), 0, cfg->grid.L * 8u);
-            const uint32_t geo = any_shape.dg[any_shape.ng] - 1u;
-            fa.dbg_geo = io->geo_feat_last ? io->geo_feat_last + (size_t)first * fa.T * geo : nullptr;
-            fa.fimg_stride = io->head_stride ? io->head_stride : geo + 16u;
-            fa.dbg_fimg = io->f_image ? io->f_image + (size_t)first * fa.fimg_stride : nullptr;
-            fa.head_rgbd = nullptr;
-            const size_t lds_bytes = (size_t)(2u * any_shape.rows + geo) * 256u * sizeof(float);
-            if (f16) {
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage_any<__half>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                hipLaunchKernelGGL(k_final_stage_any<__half>, dim3(nblk), dim3(256), lds_bytes, st, fa, any_shape);
-            } else {
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage_any<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                hipLaunchKernelGGL(k_final_stage_any<float>, dim3(nblk), dim3(256), lds_bytes, st, fa, any_shape);
-            }
-            SN_LAUNCH_CHECK("k_final_stage_any");
-            continue;
-        }
+        fa.stop_cum = route.stop_cum;
         {
-        ProfScope ps_final(st, PK_FINAL);
-#define SN_LAUNCH_FINAL_T(TT_, MODE_, KK, AUX_, LDS_FLOATS)                                                                      \
-        do {                                                                                                                 \
-            const size_t lds_bytes = (size_t)(LDS_FLOATS) * sizeof(float);                                                   \
-            SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage<TT_, 16, 2, 64, 64, 16, 32, MODE_, KK, AUX_>), \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                      \
-            hipLaunchKernelGGL((k_final_stage<TT_, 16, 2, 64, 64, 16, 32, MODE_, KK, AUX_>), dim3(nblk), dim3(256), lds_bytes, st, fa); \
-        } while (0)
-#define SN_LAUNCH_FINAL(MODE_, KK, LDS_FLOATS)                                                                                  \
-        do {                                                                                                                 \
-            if (f16) SN_LAUNCH_FINAL_T(__half, MODE_, KK, true, LDS_FLOATS); else SN_LAUNCH_FINAL_T(float, MODE_, KK, true, LDS_FLOATS); \
-        } while (0)
-#define SN_LAUNCH_FINAL_AUX(MODE_, KK, LDS_FLOATS)   /* default mode only: plain instantiation unless the extras are on */ \
-        do {                                                                                                                 \
-            if (aux) SN_LAUNCH_FINAL(MODE_, KK, LDS_FLOATS);                                                                   \
-            else if (f16) SN_LAUNCH_FINAL_T(__half, MODE_, KK, false, LDS_FLOATS);                                             \
-            else SN_LAUNCH_FINAL_T(float, MODE_, KK, false, LDS_FLOATS);                                                       \
-        } while (0)
-        const bool aux = fa.w_out != nullptr || fa.stop_cum > 0.0f;
-        // exact early-out of the LAST stage (linear-tail instantiations): opt-in (tuning.exact_early_out = 2).  Measured on the opaque field
-        // (profiles/r04/bench_configs.json): behind proposal stages the last stage's 32 samples sit around the surface and the test buys nothing
-        // (1.953 vs 1.952 ms -- the proposal stages' own early-out, always on, is what takes that render from 3.19 to 1.95 ms) while it costs a
-        // semi-transparent scene 0.2-0.3 %; a single-stage schedule gains (6.07 -> 4.43 ms) but its kernel is the bench line's (0.5-1 % cost).
-        const bool eo = cfg->tuning.exact_early_out == 2;
-#ifdef SN_EXPERIMENTS
-        // SN_EXP_FINAL_ONE_WG (round 6): the last stage asks for 84 KiB of LDS, so only ONE of its workgroups fits a CU and half of every SIMD's
-        // registers stay free for the proposal-stage workgroups of the OTHER row band (tuning.band_streams): vector-ALU-bound waves beside
-        // texture-bound ones on the same SIMD instead of on different CUs
-        const size_t lds_pad_exp = cfg->tuning.experiment == SN_EXP_FINAL_ONE_WG ? (size_t)(84 * 1024) - (size_t)(PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE) * sizeof(float) : 0u;
-#else
-        const size_t lds_pad_exp = 0u;
-#endif
-        constexpr int VIEW_W = 32 * 32 + 32 * 32 + 3 * 32;     // padded view_mlp rows
-        static_assert(VIEW_W <= PACK_FLOATS, "view weights overlay the packed MLP weights");
-        const int Kmain = !lv_ok ? -1 : dense_prefix(gl_main);   // the K = 5 instantiations read FinalLv
-        // few rays in linear order: lanes share rays (k_final_stage_sp); fewer samples per lane while CUs would idle
-        const bool final_sp = W == 0 && mlp_mode == MLP_F16X3 && fa.stop_cum == 0.0f && !use_cmp && n <= final_sp_max_rays(cfg) &&
-                              fa.T <= 64u * FSP_MAX_SPL;
-        if (final_sp) {
-            auto lpr_log2_of = [&](uint32_t sl) { const uint32_t need = div_up(fa.T, 1u << sl); uint32_t l2 = 0; while ((1u << l2) < need) ++l2; return l2; };
-            uint32_t spl_log2 = 2;
-            while (spl_log2 > 0 && div_up(fa.T, 1u << (spl_log2 - 1)) <= 64u && (((size_t)Npad << lpr_log2_of(spl_log2)) >> 8) < SN_FINAL_SP_MIN_BLOCKS) --spl_log2;
-            const uint32_t lpr_log2 = lpr_log2_of(spl_log2);
-            const uint32_t blocks = (uint32_t)(((size_t)Npad << lpr_log2) >> 8);
-            const size_t lds_bytes = final_sp_lds_floats(1u << spl_log2) * sizeof(float);
-#define SN_LAUNCH_FINAL_SP(TT_, KK)                                                                                              \
-            do {                                                                                                             \
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage_sp<TT_, KK>),                    \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                  \
-                hipLaunchKernelGGL((k_final_stage_sp<TT_, KK>), dim3(blocks), dim3(256), lds_bytes, st, fa, lpr_log2, spl_log2); \
-            } while (0)
-            if (Kmain == 5) { if (f16) SN_LAUNCH_FINAL_SP(__half, 5); else SN_LAUNCH_FINAL_SP(float, 5); }
-            else { if (f16) SN_LAUNCH_FINAL_SP(__half, -1); else SN_LAUNCH_FINAL_SP(float, -1); }
-#undef SN_LAUNCH_FINAL_SP
-            note("k_final_stage_sp", blocks, lds_bytes, Kmain, Kmain == 5 ? lv_gathers(5) : 16u * 8u);
-        } else if (use_cmp) {
-            // per-ray termination + live-sample compaction (k_final_stage_cmp); f_image stays available
-            const size_t lds_bytes = (size_t)(PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE) * sizeof(float);
-            note("k_final_stage_cmp", nblk, lds_bytes, 5, lv_gathers(5));
-            if (f16) {
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage_cmp<__half, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                hipLaunchKernelGGL((k_final_stage_cmp<__half, 5>), dim3(nblk), dim3(256), lds_bytes, st, fa);
-            } else {
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage_cmp<float, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                hipLaunchKernelGGL((k_final_stage_cmp<float, 5>), dim3(nblk), dim3(256), lds_bytes, st, fa);
-            }
-#ifdef SN_EXPERIMENTS
-        } else if (mlp_mode == MLP_F16X3 && Kmain == 5 && !aux && !per_sample_out && rs_enabled(cfg)) {
-            // role-split waves (k_final_stage_rs): 768-thread workgroups over 32x16-pixel tiles (512 rays in linear order)
-            const uint32_t nblk_rs = W ? ((W + 31u) >> 5) * ((rc.rows + 15u) >> 4) : div_up(n, (uint32_t)(RS_PROD * 64));
-            const size_t lds_bytes = (size_t)RS_LDS_FLOATS * sizeof(float);
-            note("k_final_stage_rs", nblk_rs, lds_bytes, 5, lv_gathers(5));
-            if (f16) {
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage_rs<__half, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                hipLaunchKernelGGL((k_final_stage_rs<__half, 5>), dim3(nblk_rs), dim3(RS_THREADS), lds_bytes, st, fa);
-            } else {
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage_rs<float, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                hipLaunchKernelGGL((k_final_stage_rs<float, 5>), dim3(nblk_rs), dim3(RS_THREADS), lds_bytes, st, fa);
-            }
-#endif
-        } else if (mlp_mode == MLP_F16X3 && Kmain == 5 && !(fa.dbg_bins || fa.dbg_w || fa.dbg_sigma || fa.dbg_xyz || fa.dbg_geo) && lt_enabled(cfg)) {
-            // linear tail: layer 3 off the matrix cores (per-sample geometry features are not available in this form)
-#define SN_LAUNCH_FINAL_LT_E(TT_, AUX_, EO_)                                                                                  \
-            do {                                                                                                             \
-                const size_t lds_bytes = (size_t)(PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE) * sizeof(float) + lds_pad_exp;     \
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage<TT_, 16, 2, 64, 64, 16, 32, MLP_F16X3, 5, AUX_, true, false, EO_>), \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                  \
-                hipLaunchKernelGGL((k_final_stage<TT_, 16, 2, 64, 64, 16, 32, MLP_F16X3, 5, AUX_, true, false, EO_>), dim3(nblk), dim3(256), lds_bytes, st, fa); \
-            } while (0)
-#define SN_LAUNCH_FINAL_LT(TT_, AUX_) do { if (eo) SN_LAUNCH_FINAL_LT_E(TT_, AUX_, true); else SN_LAUNCH_FINAL_LT_E(TT_, AUX_, false); } while (0)
-            // SN_RENDER_L0=1 (opt-in): fp16 tables whose level 0 fits 16 KiB keep that level LDS-resident.  Bit-identical and measured
-            // SLOWER than the texture path (800x800 [128]: 6.44 -> 6.58 ms, profiles/r03/ab_round3_experiments.txt): with fp16 tables the
-            // kernel is not bound by the texture addressers, and the 8 ds_read_b32 + swizzled slab addressing cost more than 2 gathers save
-            const uint64_t rows0 = (uint64_t)gl_main.res[0] * gl_main.res[0] * gl_main.res[0];
-#ifdef SN_EXPERIMENTS
-            const bool l0 = f16 && rows0 <= (uint64_t)L0_MAX_ROWS && cfg->tuning.experiment == SN_EXP_LDS_LEVEL0;
-#else
-            const bool l0 = false;
-            (void)rows0;
-#endif
-#ifdef SN_EXPERIMENTS
-#define SN_LAUNCH_FINAL_LT_L0(AUX_)                                                                                            \
-            do {                                                                                                             \
-                const size_t lds_bytes = (size_t)(PACK_FLOATS + 4 * 2 * 64 * 16 + L0_MAX_ROWS) * sizeof(float);              \
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage<__half, 16, 2, 64, 64, 16, 32, MLP_F16X3, 5, AUX_, true, true>), \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                  \
-                hipLaunchKernelGGL((k_final_stage<__half, 16, 2, 64, 64, 16, 32, MLP_F16X3, 5, AUX_, true, true>), dim3(nblk), dim3(256), lds_bytes, st, fa); \
-            } while (0)
-#endif
-            FinalArgs fa7 = fa;
-            const bool dens = Kv_main == 7 && !aux && !l0 && !final_sp &&
-                              build_final_lv(gl_main, 7, pairs, cfg->grid.embeddings, 2u * (f16 ? 2u : 4u), fa7.lv);
-            if (!l0) note(dens ? "k_final_stage<lt,K=7>" : aux ? "k_final_stage<lt,K=5,aux>" : "k_final_stage<lt,K=5>", nblk,
-                          (size_t)(PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE) * sizeof(float), dens ? 7 : 5, lv_gathers(dens ? 7 : 5));
-            if (dens) {     // levels 5 and 6 densified for this call (densify_levels)
-                const size_t lds_bytes = (size_t)(PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE) * sizeof(float);
-#define SN_LAUNCH_FINAL_K7_NP(TT_, EO_, NP_)                                                                                   \
-                do {                                                                                                         \
-                    SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage<TT_, 16, 2, 64, 64, 16, 32, MLP_F16X3, 7, false, true, false, EO_, NP_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-                    hipLaunchKernelGGL((k_final_stage<TT_, 16, 2, 64, 64, 16, 32, MLP_F16X3, 7, false, true, false, EO_, NP_>), dim3(nblk), dim3(256), lds_bytes, st, fa7); \
-                } while (0)
-#define SN_LAUNCH_FINAL_K7(TT_, EO_) SN_LAUNCH_FINAL_K7_NP(TT_, EO_, 3)
-                if (f16 && !eo && mlp_np == 1) SN_LAUNCH_FINAL_K7_NP(__half, false, 1);
-                else if (f16) { if (eo) SN_LAUNCH_FINAL_K7(__half, true); else SN_LAUNCH_FINAL_K7(__half, false); }
-                else { if (eo) SN_LAUNCH_FINAL_K7(float, true); else SN_LAUNCH_FINAL_K7(float, false); }
-#undef SN_LAUNCH_FINAL_K7
-#undef SN_LAUNCH_FINAL_K7_NP
-            }
-#ifdef SN_EXPERIMENTS
-            else if (l0) { note("k_final_stage<lt,K=5,lds-level0>", nblk, (size_t)(PACK_FLOATS + 4 * 2 * 64 * 16 + L0_MAX_ROWS) * sizeof(float), 5, lv_gathers(5) - 2u);
-                           if (aux) SN_LAUNCH_FINAL_LT_L0(true); else SN_LAUNCH_FINAL_LT_L0(false); }
-#endif
-            else if (aux) { if (f16) SN_LAUNCH_FINAL_LT(__half, true); else SN_LAUNCH_FINAL_LT(float, true); }
-            else if (f16 && !eo && mlp_np < 3) {
-                const size_t lds_bytes = (size_t)(PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE) * sizeof(float);
-                SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_final_stage<__half, 16, 2, 64, 64, 16, 32, MLP_F16X3, 5, false, true, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                hipLaunchKernelGGL((k_final_stage<__half, 16, 2, 64, 64, 16, 32, MLP_F16X3, 5, false, true, false, false, 1>), dim3(nblk), dim3(256), lds_bytes, st, fa);
-            }
-            else { if (f16) SN_LAUNCH_FINAL_LT(__half, false); else SN_LAUNCH_FINAL_LT(float, false); }
-#ifdef SN_EXPERIMENTS
-#undef SN_LAUNCH_FINAL_LT_L0
-#endif
-#undef SN_LAUNCH_FINAL_LT
-#undef SN_LAUNCH_FINAL_LT_E
-        } else if (mlp_mode == MLP_F16X3) {
-            note(Kmain == 5 ? "k_final_stage<per-sample,K=5>" : "k_final_stage<per-sample,generic>", nblk, (size_t)(PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE) * sizeof(float),
-                 Kmain, Kmain == 5 ? lv_gathers(5) : (uint32_t)dense_prefix(gl_main) * 4u + (16u - (uint32_t)dense_prefix(gl_main)) * 8u);
-            if (Kmain == 5) SN_LAUNCH_FINAL_AUX(MLP_F16X3, 5, PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE);     // 72 KiB; main grid: levels 0-4 dense
-            else SN_LAUNCH_FINAL_AUX(MLP_F16X3, -1, PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE);
-        } else if (mlp_mode == MLP_F32) { note("k_final_stage<mfma32>", nblk, (size_t)(PACK_FLOATS + 4 * 32 * 64) * sizeof(float), -1, 16u * 8u);
-                                          SN_LAUNCH_FINAL(MLP_F32, -1, PACK_FLOATS + 4 * 32 * 64); }   // 64 KiB
-        else { note("k_final_stage<valu>", nblk, (size_t)(2 * 64 * 256 + VIEW_W) * sizeof(float), -1, 16u * 8u);
-               SN_LAUNCH_FINAL(MLP_VALU, -1, 2 * 64 * 256 + VIEW_W); }                                  // 136 KiB
-#undef SN_LAUNCH_FINAL_AUX
-#undef SN_LAUNCH_FINAL
-#undef SN_LAUNCH_FINAL_T
-        SN_LAUNCH_CHECK("k_final_stage");
+            ProfScope ps_final(st, PK_FINAL);
+            note_final(fr, &g_launch);
+            rc = launch_final(fr, st, fa, route.any);
+            if (rc) return rc;
+            SN_LAUNCH_CHECK(fr.family == FinalRoute::ANY ? "k_final_stage_any" : "k_final_stage");
         }
         if (cfg->with_feat) {
+            const GridLevels &gf = route.gl_feat;
+            const FeatRoute &feat = route.feat;
             FeatArgs ft;
-            ft.rc = rc; ft.g = gl_feat; ft.table = cfg->feat_grid.embeddings; ft.T = cfg->num_steps[S - 1];
+            ft.rc = rays; ft.g = gf; ft.table = cfg->feat_grid.embeddings; ft.T = cfg->num_steps[S - 1];
             ft.bins_in = b_scr[S - 1]; ft.bins0_stride = io->bins0_ray_stride;
             ft.bins0_tab = (S == 1 && io->bins0_table) ? io->bins0_table + (size_t)first * ft.bins0_stride : nullptr;
             ft.w_in = w_scr[S - 1];
-            ft.out_stride = io->head_stride ? io->head_stride : gl_feat.L * gl_feat.C;
+            ft.out_stride = io->head_stride ? io->head_stride : gf.L * gf.C;
             ft.out = io->f_feat + (size_t)first * ft.out_stride;
-            const bool h16 = cfg->feat_grid.table_dtype == SN_F16;
             ProfScope ps_feat(st, PK_FEAT);
-            // dense prefix of the feature grid: its passes run the LDS-patch instantiation (k_feat_stage<..., PATCH = true>), the hashed rest the plain one
-            uint32_t n_dense = 0;
-            while (n_dense < gl_feat.L && (gl_feat.mode[n_dense] & 1u) == 0u) ++n_dense;
-            const uint32_t lg_u = (uint32_t)feat_lg;
-            const uint32_t patch_levels = cfg->tuning.feat_patch != 1 ? 0u : ((n_dense + lg_u - 1u) / lg_u) * lg_u > gl_feat.L ? gl_feat.L : ((n_dense + lg_u - 1u) / lg_u) * lg_u;
-#define SN_LAUNCH_FEAT(CC, LGG)                                                                                       \
-            do {                                                                                                      \
-                if (patch_levels) {                                                                                   \
-                    ft.level0 = 0;                                                                                    \
-                    const dim3 fg(nblk, patch_levels / LGG);                                                          \
-                    if (h16) hipLaunchKernelGGL((k_feat_stage<__half, CC, LGG, true>), fg, dim3(256), 0, st, ft);      \
-                    else hipLaunchKernelGGL((k_feat_stage<float, CC, LGG, true>), fg, dim3(256), 0, st, ft);           \
-                }                                                                                                     \
-                if (patch_levels < gl_feat.L) {                                                                       \
-                    ft.level0 = patch_levels;                                                                         \
-                    const dim3 fg(nblk, (gl_feat.L - patch_levels) / LGG);                                            \
-                    if (h16) hipLaunchKernelGGL((k_feat_stage<__half, CC, LGG>), fg, dim3(256), 0, st, ft);            \
-                    else hipLaunchKernelGGL((k_feat_stage<float, CC, LGG>), fg, dim3(256), 0, st, ft);                 \
-                }                                                                                                     \
-            } while (0)
-            if (gl_feat.C == 8) { if (feat_lg == 4) SN_LAUNCH_FEAT(8, 4); else if (feat_lg == 2) SN_LAUNCH_FEAT(8, 2); else SN_LAUNCH_FEAT(8, 1); }
-            else if (gl_feat.C == 4) { if (feat_lg == 4) SN_LAUNCH_FEAT(4, 4); else if (feat_lg == 2) SN_LAUNCH_FEAT(4, 2); else SN_LAUNCH_FEAT(4, 1); }
-            else { if (feat_lg == 4) SN_LAUNCH_FEAT(2, 4); else if (feat_lg == 2) SN_LAUNCH_FEAT(2, 2); else SN_LAUNCH_FEAT(2, 1); }
-#undef SN_LAUNCH_FEAT
+            if (feat.patch_levels) {
+                ft.level0 = 0;
+                rc = launch(feat_kernel(feat, true), dim3(cr.nblk, feat.patch_levels / feat.lg), dim3(256), 0, st, ft);
+                if (rc) return rc;
+            }
+            if (feat.patch_levels < gf.L) {
+                ft.level0 = feat.patch_levels;
+                rc = launch(feat_kernel(feat, false), dim3(cr.nblk, (gf.L - feat.patch_levels) / feat.lg), dim3(256), 0, st, ft);
+                if (rc) return rc;
+            }
             SN_LAUNCH_CHECK("k_feat_stage");
         }
     }

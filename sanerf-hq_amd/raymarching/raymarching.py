@@ -1138,6 +1138,86 @@ class RenderPlan:
         return self._ws
 
 
+def _fill_io(plan: RenderPlan, io, N: int, tile_w: int, want, u_tables, bins0_table, skip_final: bool, packed, head_input: bool, tuning, buf, table):
+    """What render_rays and route_info share: the call's sn_render_io (but for the rays and the workspace) and the tuning written into the
+    plan's config.  buf(name, shape, dtype) -> the device pointer of that output; table(t) -> (tensor as the call reads it, its pointer)."""
+    io.N, io.tile_w = N, int(tile_w)
+    if bins0_table is not None:      # [T0+1]: one table for all rays; [N, T0+1]: per ray (a training step's perturbed bins)
+        b0, io.bins0_table = table(bins0_table)
+        if b0.dim() == 2:
+            if b0.shape != (N, plan.num_steps[0] + 1):
+                raise RuntimeError(f"bins0_table: expected [{N}, {plan.num_steps[0] + 1}] per-ray bins, got {tuple(b0.shape)}")
+            io.bins0_ray_stride = b0.shape[1]
+    if u_tables:
+        for k, u in u_tables.items():
+            u, io.u_table[k] = table(u)
+            if u.dim() == 2:
+                if u.shape != (N, plan.num_steps[k] + 1):
+                    raise RuntimeError(f"u_tables[{k}]: expected [{N}, {plan.num_steps[k] + 1}] per-ray values, got {tuple(u.shape)}")
+                io.u_ray_stride[k] = u.shape[1]
+    S = plan.cfg.num_stages
+    want = set(want)
+    if skip_final:                   # proposal stages only: the last stage's resampled bins [N, T_last+1] are the result
+        if S < 2:
+            raise RuntimeError("render_rays(skip_final=True) needs a schedule with proposal stages")
+        io.skip_final = 1
+        want = set()
+        io.bins[S - 1] = buf(f"bins{S - 1}", (N, plan.num_steps[S - 1] + 1))
+    else:
+        plan.check_range()           # fp16 range guard of the final stage's MLP: a no-op unless a parameter version moved
+        if packed is not None:
+            base = packed.data_ptr()
+            io.image, io.depth, io.weights_sum, io.out_stride = base, base + 12, base + 16, packed.shape[1]
+        else:
+            io.image = buf("image", (N, 3))
+            io.depth = buf("depth", (N,))
+            io.weights_sum = buf("weights_sum", (N,))
+    for k in range(S):
+        T = plan.num_steps[k]
+        if "bins" in want:
+            io.bins[k] = buf(f"bins{k}", (N, T + 1))
+        if "weights" in want or (k == S - 1 and "weights_last" in want):
+            io.weights[k] = buf(f"weights{k}", (N, T))
+        if "sigmas" in want:
+            io.sigmas[k] = buf(f"sigmas{k}", (N, T))
+        if "inds" in want and k >= 1:
+            io.inds[k] = buf(f"inds{k}", (N, T + 1), torch.int32)
+    Tl = plan.num_steps[S - 1]
+    if "xyzs_last" in want:
+        io.xyzs_last = buf("xyzs_last", (N, Tl, 3))
+    if "geo_feat_last" in want:
+        io.geo_feat_last = buf("geo_feat_last", (N, Tl, plan.geo))
+    if head_input and plan.cfg.with_feat and not skip_final:
+        io.f_feat = buf("head_input", (N, plan.feat_dim + plan.ncol + 4))
+        io.f_image, io.head_stride = io.f_feat + 4 * plan.feat_dim, plan.feat_dim + plan.ncol + 4
+    else:
+        if "f_image" in want:
+            io.f_image = buf("f_image", (N, plan.ncol))
+        if plan.cfg.with_feat and not skip_final:
+            io.f_feat = buf("f_feat", (N, plan.feat_dim))
+    eff = tuning or plan.tuning or globals()["tuning"]           # per call > per plan > process default
+    eff.write(plan.cfg.tuning)
+    return eff
+
+
+def route_info(plan: RenderPlan, N: int, tile_w: int = 0, want: Sequence[str] = (), u_tables: Optional[Dict[int, torch.Tensor]] = None,
+               bins0_table: Optional[torch.Tensor] = None, skip_final: bool = False, tuning: Optional["Tuning"] = None,
+               packed: Optional[torch.Tensor] = None, head_input: bool = False) -> dict:
+    """What last_launch_info() would report after render_rays(plan, <N rays>, ...) with the same arguments, without rendering
+    (sn_rm_render_route_info: the same validation and route planning on the host; no render kernel is launched and no output is
+    allocated).  Like render_rays it writes the effective tuning into plan.cfg.tuning and, unless skip_final, consults the plan's fp16
+    range guard (plan.check_range(): device reductions and one sync when a parameter version moved) -- the guard decides the route."""
+    io = _lib.RenderIO()
+    stand_in = 64                                                  # an aligned non-NULL address: the dry run dereferences nothing
+    io.rays_o = io.rays_d = stand_in
+    _fill_io(plan, io, int(N), tile_w, want, u_tables, bins0_table, skip_final, packed, head_input, tuning,
+             lambda name, shape, dtype=torch.float32: stand_in, lambda t: (t, stand_in))
+    info = _lib.LaunchInfo()
+    _lib.check(_lib.lib().sn_rm_render_route_info(C.byref(plan.cfg), C.byref(io), C.byref(info)), "route_info")
+    return dict(final_kernel=info.final_kernel.decode(), workgroups=int(info.workgroups), lds_bytes=int(info.lds_bytes),
+                dense_levels=int(info.dense_levels), gathers_per_wave_sample=int(info.gathers_per_wave_sample), launches=int(info.launches))
+
+
 def render_rays(plan: RenderPlan, rays_o, rays_d, cam_near_far=None, bg_color: float = 1.0, tile_w: int = 0,
                 want: Sequence[str] = (), u_tables: Optional[Dict[int, torch.Tensor]] = None,
                 bins0_table: Optional[torch.Tensor] = None, out: Optional[Dict[str, torch.Tensor]] = None,
@@ -1163,7 +1243,12 @@ def render_rays(plan: RenderPlan, rays_o, rays_d, cam_near_far=None, bg_color: f
         if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
             t = torch.empty(shape, device=device, dtype=dtype)     # (a strided view left by an earlier packed= call is not reused)
             res[name] = t
-        return t
+        return _lib.dev(t, name, dtype)
+
+    def table(t):
+        t = t.to(device).contiguous().float()
+        keep.append(t)
+        return t, t.data_ptr()
 
     io.rays_o, io.rays_d = _lib.dev(rays_o, "rays_o"), _lib.dev(rays_d, "rays_d")
     if cam_near_far is not None:
@@ -1173,68 +1258,16 @@ def render_rays(plan: RenderPlan, rays_o, rays_d, cam_near_far=None, bg_color: f
         cnf = cnf.contiguous()
         keep.append(cnf)
         io.cam_near_far = _lib.dev(cnf, "cam_near_far")
-    io.N, io.tile_w = N, int(tile_w)
-    if bins0_table is not None:      # [T0+1]: one table for all rays; [N, T0+1]: per ray (a training step's perturbed bins)
-        b0 = bins0_table.to(device).contiguous().float(); keep.append(b0); io.bins0_table = b0.data_ptr()
-        if b0.dim() == 2:
-            if b0.shape != (N, plan.num_steps[0] + 1):
-                raise RuntimeError(f"bins0_table: expected [{N}, {plan.num_steps[0] + 1}] per-ray bins, got {tuple(b0.shape)}")
-            io.bins0_ray_stride = b0.shape[1]
-    if u_tables:
-        for k, u in u_tables.items():
-            u = u.to(device).contiguous().float(); keep.append(u); io.u_table[k] = u.data_ptr()
-            if u.dim() == 2:
-                if u.shape != (N, plan.num_steps[k] + 1):
-                    raise RuntimeError(f"u_tables[{k}]: expected [{N}, {plan.num_steps[k] + 1}] per-ray values, got {tuple(u.shape)}")
-                io.u_ray_stride[k] = u.shape[1]
+    if packed is not None and not skip_final:
+        if not (packed.is_cuda and packed.dtype == torch.float32 and packed.dim() == 2 and packed.shape[0] == N and packed.shape[1] >= 5
+                and packed.is_contiguous() and packed.device == device):
+            raise RuntimeError(f"render_rays: packed must be a contiguous fp32 [{N}, >=5] tensor on {device}, got {tuple(packed.shape)} {packed.dtype}")
+        res["image"], res["depth"], res["weights_sum"] = packed[:, :3], packed[:, 3], packed[:, 4]
+    eff = _fill_io(plan, io, N, tile_w, want, u_tables, bins0_table, skip_final, packed, head_input, tuning, buf, table)
     S = plan.cfg.num_stages
-    want = set(want)
-    if skip_final:                   # proposal stages only: the last stage's resampled bins [N, T_last+1] are the result
-        if S < 2:
-            raise RuntimeError("render_rays(skip_final=True) needs a schedule with proposal stages")
-        io.skip_final = 1
-        want = set()
-        io.bins[S - 1] = buf(f"bins{S - 1}", (N, plan.num_steps[S - 1] + 1)).data_ptr()
-    else:
-        plan.check_range()           # fp16 range guard of the final stage's MLP: a no-op unless a parameter version moved
-        if packed is not None:
-            if not (packed.is_cuda and packed.dtype == torch.float32 and packed.dim() == 2 and packed.shape[0] == N and packed.shape[1] >= 5
-                    and packed.is_contiguous() and packed.device == device):
-                raise RuntimeError(f"render_rays: packed must be a contiguous fp32 [{N}, >=5] tensor on {device}, got {tuple(packed.shape)} {packed.dtype}")
-            base = packed.data_ptr()
-            io.image, io.depth, io.weights_sum, io.out_stride = base, base + 12, base + 16, packed.shape[1]
-            res["image"], res["depth"], res["weights_sum"] = packed[:, :3], packed[:, 3], packed[:, 4]
-        else:
-            io.image = _lib.dev(buf("image", (N, 3)), "image")
-            io.depth = _lib.dev(buf("depth", (N,)), "depth")
-            io.weights_sum = _lib.dev(buf("weights_sum", (N,)), "weights_sum")
-    for k in range(S):
-        T = plan.num_steps[k]
-        if "bins" in want:
-            io.bins[k] = buf(f"bins{k}", (N, T + 1)).data_ptr()
-        if "weights" in want or (k == S - 1 and "weights_last" in want):
-            io.weights[k] = buf(f"weights{k}", (N, T)).data_ptr()
-        if "sigmas" in want:
-            io.sigmas[k] = buf(f"sigmas{k}", (N, T)).data_ptr()
-        if "inds" in want and k >= 1:
-            io.inds[k] = buf(f"inds{k}", (N, T + 1), torch.int32).data_ptr()
-    Tl = plan.num_steps[S - 1]
-    if "xyzs_last" in want:
-        io.xyzs_last = buf("xyzs_last", (N, Tl, 3)).data_ptr()
-    if "geo_feat_last" in want:
-        io.geo_feat_last = buf("geo_feat_last", (N, Tl, plan.geo)).data_ptr()
-    if head_input and plan.cfg.with_feat and not skip_final:
-        S_head = plan.feat_dim + plan.ncol + 4
-        hb = buf("head_input", (N, S_head))
-        io.f_feat, io.f_image, io.head_stride = hb.data_ptr(), hb.data_ptr() + 4 * plan.feat_dim, S_head
+    if io.head_stride:
+        hb = res["head_input"]
         res["f_feat"], res["f_image"] = hb[:, :plan.feat_dim], hb[:, plan.feat_dim:plan.feat_dim + plan.ncol]
-    else:
-        if "f_image" in want:
-            io.f_image = buf("f_image", (N, plan.ncol)).data_ptr()
-        if plan.cfg.with_feat and not skip_final:
-            io.f_feat = buf("f_feat", (N, plan.feat_dim)).data_ptr()
-    eff = tuning or plan.tuning or globals()["tuning"]           # per call > per plan > process default
-    eff.write(plan.cfg.tuning)
     need = int(_lib.lib().sn_rm_render_workspace_bytes(C.byref(plan.cfg), N, int(tile_w)))
     ws = plan.workspace(N, int(tile_w), device)
     if ws.numel() < need:                                          # (a per-call tuning that needs more than the plan's own)
@@ -1243,6 +1276,6 @@ def render_rays(plan: RenderPlan, rays_o, rays_d, cam_near_far=None, bg_color: f
     io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
     plan.cfg.bg_color = float(bg_color)
     _lib.check(_lib.lib().sn_rm_render_rays(C.byref(plan.cfg), C.byref(io), _lib.stream()), "render_rays")
-    if "weights_last" in want:
+    if "weights_last" in set(want) and not skip_final:
         res["weights_last"] = res[f"weights{S - 1}"]
     return res

@@ -513,3 +513,44 @@ def test_render_writes_straight_into_a_packed_band(gpu, orc):
         lin_dense = {k: v.clone() for k, v in rm.render_rays(plan, T(ro, gpu), T(rd, gpu), tile_w=0, out={}).items()}      # linear ray order: the several-lanes-per-ray kernels
         lin = rm.render_rays(plan, T(ro, gpu), T(rd, gpu), tile_w=0, packed=torch.empty(H * W, 5, device=gpu), out={})
         assert torch.equal(lin["image"], lin_dense["image"]) and torch.equal(lin["depth"], lin_dense["depth"]) and torch.equal(lin["weights_sum"], lin_dense["weights_sum"])
+
+
+def test_route_info_reports_what_a_render_launches(gpu):
+    """sn_rm_render_route_info is the dry run of the planner sn_rm_render_rays launches from: for every last-stage route reachable at small
+    size -- 40x24 rays in image order (960 rays: partial tiles, a partial workgroup) and 1000 rays in linear order, [16] and [16,8,8], both
+    table precisions, the routes forced through Tuning (the experiments on an experiments build) -- last_launch_info() after the render
+    equals route_info() for the same arguments, field by field."""
+    from sanerf_hq_amd import _lib, raymarching as rm, synth
+    exp = bool(_lib.lib().sn_build_flags() & _lib.BUILD_EXPERIMENTS)
+    tunings = [dict(), dict(densify=2), dict(band_streams=2), dict(per_sample_form=1), dict(exact_early_out=2), dict(final_sp_max_rays=-1),
+               dict(prop_sp_max_rays=-1, final_sp_max_rays=-1), dict(mlp_mode=_lib.MLP_MFMA32), dict(mlp_mode=_lib.MLP_VALU), dict(mlp_mode=_lib.MLP_F16X1),
+               dict(densify=2, mlp_mode=_lib.MLP_F16X1), dict(densify=2, exact_early_out=2)]
+    if exp:
+        tunings += [dict(experiment=_lib.EXP_ROLE_SPLIT), dict(experiment=_lib.EXP_LDS_LEVEL0), dict(experiment=_lib.EXP_FINAL_ONE_WG, band_streams=2)]
+    pose = synth.orbit_pose(1.0, 20.0, 30.0)
+    ro_img, rd_img = rm.generate_rays(pose, synth.pinhole_intrinsics(24, 40), 24, 40, device=gpu)
+    ro_lin, rd_lin = rm.generate_rays(pose, synth.pinhole_intrinsics(25, 40), 25, 40, device=gpu)
+    kernels = set()
+    for steps in ([16], [16, 8, 8]):
+        model = product_model(synthetic_params(steps, seed=29), steps, False, gpu)
+        for tdt in (torch.float32, torch.float16):
+            plans = [(rm.RenderPlan(model, steps, tdt), dict()), (rm.RenderPlan(model, steps, tdt, compact_live=True), dict()),
+                     (rm.RenderPlan(model, steps, tdt, early_stop_eps=1e-3), dict()), (rm.RenderPlan(model, steps, tdt), dict(want=("weights_last",))),
+                     (rm.RenderPlan(model, steps, tdt), dict(want=("geo_feat_last", "f_image")))]
+            if len(steps) > 1:
+                plans.append((rm.RenderPlan(model, steps, tdt), dict(skip_final=True)))
+            for plan, kw in plans:
+                for tn in tunings:
+                    for (ro, rd, tile) in ((ro_img, rd_img, 40), (ro_lin[:1000], rd_lin[:1000], 0)):
+                        t = rm.Tuning(**tn)
+                        rm.render_rays(plan, ro, rd, tile_w=tile, tuning=t, **kw)
+                        ran = rm.last_launch_info()
+                        dry = rm.route_info(plan, ro.shape[0], tile, tuning=t, **kw)
+                        assert ran == dry, (steps, tdt, kw, tn, tile, ran, dry)
+                        kernels.add(ran["final_kernel"])
+    torch.cuda.synchronize()
+    want = {"", "k_final_stage<lt,K=5>", "k_final_stage<lt,K=7>", "k_final_stage<lt,K=5,aux>", "k_final_stage<per-sample,K=5>", "k_final_stage_sp",
+            "k_final_stage_cmp", "k_final_stage<mfma32>", "k_final_stage<valu>"}
+    if exp:
+        want |= {"k_final_stage_rs", "k_final_stage<lt,K=5,lds-level0>"}
+    assert want <= kernels, sorted(want - kernels)
