@@ -112,7 +112,8 @@ int sn_grid_encode_backward_binned(const float *grad, const float *inputs, const
                                    uint32_t B, uint32_t D, uint32_t C, uint32_t L, uint32_t max_level,
                                    float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp,
                                    int layout, void *workspace, size_t workspace_bytes, sn_stream_t stream);
-/* gridencoder.h:15 / grid.py:170-191 */
+/* gridencoder.h:15 / grid.py:170-191.  D, C, L and the offsets are checked first (SN_ERR_INVALID); B = 0 on a valid grid then returns
+ * SN_OK without looking at the device pointers, which may be NULL (an empty tensor's data pointer is). */
 int sn_grad_total_variation(const float *inputs, const float *embeddings, float *grad,
                             const int32_t *offsets_host, float weight,
                             uint32_t B, uint32_t D, uint32_t C, uint32_t L,

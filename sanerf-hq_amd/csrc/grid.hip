@@ -544,11 +544,11 @@ int sn_grad_total_variation(const float *inputs, const float *embeddings, float 
                             uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                             float S, uint32_t H, uint32_t gridtype, int align_corners,
                             sn_stream_t stream) {
-    SN_REQUIRE(inputs && embeddings && grad, "grad_total_variation: NULL device pointer");
     GridLevels g;
     int rc = build_grid_levels(&g, offsets_host, D, C, L, S, H, gridtype, align_corners, 0);
     if (rc) return rc;
-    if (B == 0) return SN_OK;
+    if (B == 0) return SN_OK;   // empty batch of a valid grid: nothing to launch, the pointers may be NULL (an empty tensor's data pointer is)
+    SN_REQUIRE(inputs && embeddings && grad, "grad_total_variation: NULL device pointer");
     const dim3 grid(div_up(B, 256), L), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define CALL_TV(DD, CC) hipLaunchKernelGGL((k_grid_tv<DD, CC>), grid, block, 0, st, inputs, embeddings, grad, weight, B, g)

@@ -21,6 +21,9 @@ Bounds (u = 2^-24, first-order count of the fp32 roundings, factor 2 of margin):
   dy_dx           2 (2^(D-1) + 2 D + 2 + s) u sum|w (v_r - v_l) deriv|
   input gradient  the dy_dx count + L C further terms, on sum |g| * (dy_dx mass)
 s = 0 for linear interpolation.  Smoothstep: s = 3 D, and the masses use widened weights -- see _factors().
+
+The two regularisers that act on the table's gradient in place are stated here too: tv_gradient() (gridencoder.cu:525-631) with
+tv_bound(), weight_decay() (gridencoder.cu:670-703) with weight_decay_bound(); their counts are derived in those docstrings.
 """
 import math
 
@@ -245,6 +248,84 @@ def backward_input(grid, grad, fwd):
     return dict(grad_inputs=(g * fwd["dy_dx"]).sum(dim=(1, 3)), mass=(g.abs() * fwd["dy_dx_mass"]).sum(dim=(1, 3)))
 
 
+# ---- the regularisers on the table gradient ---------------------------------------------------------------------------------------
+TV_EPS = float(torch.tensor(1e-9, dtype=torch.float32))                                  # the literal 1e-9f of gridencoder.cu:628, widened
+
+
+def tv_cells(grid, x, l):
+    """Centre vertex [B, D] int64 of the samples x (all in range) on level l: gridencoder.cu:566-576, the same fp32 position and floor
+    as the encoder's (_locate) -- min(floor, res - 2) with align_corners, else the floor of the clamped position, which reaches res - 1."""
+    return _locate(grid, x, l)[0]
+
+
+def tv_gradient(grid, x, table, weight):
+    """What kernel_grad_tv ADDS to the table gradient (gridencoder.cu:525-631), in float64.  x [B, D] fp32 in [0, 1] (samples outside
+    contribute nothing, :547-557), table [rows, C] read exactly, weight a Python float -> dict:
+      grad [rows, C] float64   sum over samples and levels of  w * results / sqrt(idelta + eps)  at the row of the sample's centre vertex,
+                               results = sum of (centre - neighbour) over the neighbours, idelta = sum of their squares (:588-629)
+      n    [rows]    int64     contributions per row
+      mass [rows, C] float64   M = sum |w| * (sum over the neighbours of |centre - neighbour|) / sqrt(idelta + eps)
+    Neighbours: per dimension the vertex at +1 ALWAYS -- the guard `cur_d < resolution` (:595) cannot fail, so a centre at res - 1 asks
+    for the vertex res, one past the last, which get_grid_index folds back by its unconditional `% hashmap_size` (:78; _rows does the
+    same) -- and the vertex at -1 where the centre is not 0 (:608).
+    w = weight / (2 D) is rounded to fp32 (:586: a float), eps is the fp32 literal 1e-9f.
+
+    Departures of the HIP kernel from the reference's text that this statement is indifferent to, and that are deliberate: it spells the
+    accumulation idelta += gv * gv as an fmaf (nvcc contracts the reference's line to one), 1 / sqrtf for rsqrtf (IEEE-rounded both, where
+    rsqrtf is an approximation), and it forces the generic modulo on every level, because the level's own addressing mode (none on a dense
+    level, a mask on a power of two) does not cover the vertex res."""
+    D, C = grid.D, grid.C
+    dev = x.device
+    xs = x[in_range(x)]
+    T = table.double()
+    w = float(torch.tensor(weight, dtype=torch.float32) / torch.tensor(float(2 * D), dtype=torch.float32))
+    gt = torch.zeros(grid.rows, C, dtype=torch.float64, device=dev)
+    mass = torch.zeros_like(gt)
+    n = torch.zeros(grid.rows, dtype=torch.int64, device=dev)
+    for l in range(grid.L):
+        cell = tv_cells(grid, xs, l)
+        p = [cell[:, d] for d in range(D)]
+        centre = _rows(grid, l, p)
+        c = T[centre]
+        results, idelta, absum = torch.zeros_like(c), torch.zeros_like(c), torch.zeros_like(c)
+        for d in range(D):
+            q = list(p)
+            q[d] = p[d] + 1                                                              # up to and including the vertex `res`
+            gv = c - T[_rows(grid, l, q)]
+            results += gv; idelta += gv * gv; absum += gv.abs()
+            has_left = (p[d] > 0).double()[:, None]
+            q[d] = torch.clamp(p[d] - 1, min=0)
+            gv = (c - T[_rows(grid, l, q)]) * has_left
+            results += gv; idelta += gv * gv; absum += gv.abs()
+        inv = 1.0 / torch.sqrt(idelta + TV_EPS)
+        gt.index_add_(0, centre, w * results * inv)
+        mass.index_add_(0, centre, abs(w) * absum * inv)
+        n += torch.bincount(centre, minlength=grid.rows)
+    return dict(grad=gt, n=n, mass=mass)
+
+
+def level_of_rows(grid, device=None):
+    """[rows] int64: the level whose [offsets[l], offsets[l+1]) holds the row -- what the binary search of gridencoder.cu:686-699 finds."""
+    sizes = torch.tensor([grid.size(l) for l in range(grid.L)], dtype=torch.int64, device=device)
+    return torch.repeat_interleave(torch.arange(grid.L, dtype=torch.int64, device=device), sizes)
+
+
+def weight_decay(grid, table, weight):
+    """What kernel_grad_wd ADDS (gridencoder.cu:670-703): 2 * weight * table / size(level of the row), float64 [rows, C]; weight is
+    rounded to fp32 (the kernel's argument is a float)."""
+    w = float(torch.tensor(weight, dtype=torch.float32))
+    sizes = torch.tensor([float(grid.size(l)) for l in range(grid.L)], dtype=torch.float64, device=table.device)
+    return 2.0 * w * table.double() / sizes[level_of_rows(grid, table.device)][:, None]
+
+
+def weight_decay_exact_levels(grid, device=None):
+    """[rows, C] fp32: 1.0f / size(level of the row) -- what a table of ones, a zero gradient and weight 0.5 must give to the bit
+    (2 * 0.5 * 1 = 1 exactly, one correctly rounded division, 0 + v = v)."""
+    sizes = torch.tensor([float(grid.size(l)) for l in range(grid.L)], dtype=torch.float32, device=device)
+    one = torch.ones((), dtype=torch.float32, device=device)
+    return (one / sizes)[level_of_rows(grid, device)][:, None].expand(grid.rows, grid.C).contiguous()
+
+
 # ---- bounds: every count in one place ---------------------------------------------------------------------------------------------
 def forward_bound(grid, y_mass):
     return 2.0 * ((1 << grid.D) + 2 * grid.D + _extra(grid)) * U * y_mass
@@ -266,6 +347,45 @@ def input_grad_bound(grid, mass):
 def table_grad_bound(grid, n, mass):
     """[rows, C]; rows with n = 0 get a bound of exactly 0."""
     return 2.0 * (n.double() + 2 * grid.D + _extra(grid))[:, None] * U * mass
+
+
+def tv_terms(grid):
+    """fp32 roundings behind ONE contribution t = w * r * q, r = results, q = 1 / sqrt(idelta + eps), counted in units of
+    u * m with m = |w| * A * q and A = sum over the k <= 2 D neighbours of |gv| (so |t| <= m), to first order:
+      1      every difference gv = centre - neighbour is rounded once: each |gv| is off by <= u |gv|, r by <= u A;
+      2 D    the (at most 2 D) additions into `results`: each rounds a partial sum that is <= A in magnitude.  This is an ABSOLUTE
+             error <= 2 D u A on r, however small |r| is after cancellation -- which is why the mass is built on A, not on |r|;
+      D + 1  idelta: a sum of non-negative terms, so relative errors add: 2 u from the two roundings inside gv * gv (the rounded
+             difference enters squared), and one rounding per fused multiply-add, 2 D of them: (2 D + 2) u on idelta; the square root
+             halves it;
+      1/2    the addition of eps rounds once, halved by the root as well;
+      2      sqrtf: 1 ulp, which is up to 2 u relative, in the HIP math API's table of single-precision functions (the product library
+             builds it correctly rounded, 1/2 ulp; the documented figure is what is counted);
+      1      the division 1 / sqrt: correctly rounded;
+      2      the two products w * r and (w * r) * q.
+    Sum: 3 D + 7.5, taken as 3 D + 8.  (rsqrtf, the reference's own spelling, is 1 ulp in the same table and saves the division:
+    a kernel written that way fits the same count.)"""
+    return 3 * grid.D + 8
+
+
+def tv_bound(grid, n, mass, g0=None):
+    """[rows, C] bound on |(got - g0) - tv_gradient()["grad"]|:  2 u ((n + 3 D + 8) M + n |g0|).
+    The n contributions of a row are added to the gradient that is already there, g0, by atomics in any order: n additions, each rounding a
+    partial sum that is at most |g0| + M in magnitude, which is n u (|g0| + M); without g0 the gradient is taken to start at zero.
+    The contributions themselves carry tv_terms() roundings each, relative to their masses, which sum to M.  Factor 2 of margin as
+    everywhere in this module.  Rows with n = 0 get a bound of exactly 0: they must keep g0 bit for bit."""
+    nd = n.double()[:, None]
+    b = (nd + tv_terms(grid)) * mass
+    if g0 is not None:
+        b = b + nd * g0.double().abs()
+    return 2.0 * U * b
+
+
+def weight_decay_bound(grid, g0, term):
+    """|got - (g0 + term)| <= 2 * 4 u (|g0| + |term|): 2 * weight is exact; the product with the table value, the division by the size and the
+    final addition round once each (the first two relative to |term|, the last to |g0 + term|), and the conversion of a size above 2^24 to
+    fp32 would be a fourth."""
+    return 2.0 * 4 * U * (g0.double().abs() + term.abs())
 
 
 def worst_ratio(got, ref, bound):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import grid_ref64 as R
 from helpers import camera_rays, product_model, synthetic_params
 
 pytestmark = pytest.mark.gpu
@@ -134,11 +135,20 @@ def test_grid_tv_and_weight_decay(gpu, orc):
     enc.grad_weight_decay(0.1)
     want = orc.grad_weight_decay(emb, g0.copy(), enc.offsets.cpu().numpy(), 0.1)
     np.testing.assert_allclose(enc.embeddings.grad.cpu().numpy(), want, rtol=1e-6, atol=1e-7)
+    # ... and the fp64 statement with its derived round-off bound (tests/grid_ref64.py), which is the tighter of the two
+    grid = R.Grid(3, 6, 2, 12, 16, desired=256)
+    assert grid.offsets == enc.offsets.tolist()
+    term = R.weight_decay(grid, T(emb, gpu), 0.1)
+    ratio, _ = R.worst_ratio(enc.embeddings.grad, T(g0, gpu).double() + term, R.weight_decay_bound(grid, T(g0, gpu), term))
+    assert ratio <= 1.0, ratio
     x = rng.uniform(-1, 1, (5000, 3)).astype(np.float32)
     enc.embeddings.grad = T(g0, gpu)
     enc.grad_total_variation(1e-3, T(x, gpu), bound=1)
     want = orc.grad_total_variation((x + 1) / 2, emb, g0.copy(), enc.offsets.cpu().numpy(), 1e-3, enc.per_level_scale, 16)
     np.testing.assert_allclose(enc.embeddings.grad.cpu().numpy(), want, rtol=1e-4, atol=1e-6)
+    ref = R.tv_gradient(grid, (T(x, gpu) + 1) / (2 * 1), T(emb, gpu), 1e-3)
+    ratio, exact = R.worst_ratio(enc.embeddings.grad.double() - T(g0, gpu).double(), ref["grad"], R.tv_bound(grid, ref["n"], ref["mass"], T(g0, gpu)))
+    assert exact and ratio <= 1.0, ratio
     enc.embeddings.grad = T(g0, gpu)
     enc.grad_total_variation(1e-7)                       # default: 1e6 random points (grid.py:172)
     assert torch.isfinite(enc.embeddings.grad).all()
