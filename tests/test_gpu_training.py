@@ -154,9 +154,10 @@ def test_mlp_module_takes_the_fused_route_and_keeps_the_torch_route(gpu):
 
 def test_ray_composite_forward_backward_vs_torch(gpu):
     """sn_rm_ray_composite[_backward] against the reference's expressions (renderer.py:327-347, network.py:164-170: per-sample colour =
-    cat([geo_feat, SH(d)]) composited with the weights) in fp64 torch with the package's SH encoder."""
+    cat([geo_feat, SH(d)]) composited with the weights) in fp64 torch; the SH is the fp64 statement of tests/encoders_ref64.py on the
+    direction normalised in fp64, not the package's own encoder (which shares its polynomials with the kernel under test)."""
+    import encoders_ref64
     from sanerf_hq_amd import raymarching as rm
-    from sanerf_hq_amd.shencoder import SHEncoder
     N, T = 777, 32
     g = torch.Generator(device=gpu).manual_seed(4)
     w = torch.rand(N, T, device=gpu, generator=g).requires_grad_(True)
@@ -168,7 +169,7 @@ def test_ray_composite_forward_backward_vs_torch(gpu):
     ((ws * gws).sum() + (depth * gd).sum() + (f * gf).sum()).backward()
     got = (w.grad.clone(), raw.grad.clone())
     w.grad = raw.grad = None
-    sh = SHEncoder(degree=4)(d / d.norm(dim=-1, keepdim=True)).double()
+    sh = encoders_ref64.sh_values(d.double() / d.double().norm(dim=-1, keepdim=True), 4)
     w64, raw64 = w.detach().double().requires_grad_(True), raw.detach().double().requires_grad_(True)
     color = torch.cat([raw64[..., 1:], sh.unsqueeze(1).expand(N, T, 16)], dim=-1)
     ws2, depth2, f2 = w64.sum(-1), (w64 * tm.double()).sum(-1), (w64.unsqueeze(-1) * color).sum(1)
