@@ -366,6 +366,78 @@ int sn_rm_feature_distill_loss(const float *feat, uint32_t feat_stride, uint32_t
 int sn_rm_feature_map(const float *feat, uint32_t feat_stride, uint32_t h, uint32_t w, uint32_t C, uint32_t Ho, uint32_t Wo, float *out,
                       sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Propagation of 3D point prompts across views and the decode overlays (prompts.hip): what the reference does between a click and the
+ * SAM decoder's prompt, and between the decoder's masks and the picture it returns.  Labels, crucial flags, counts and states are int32
+ * on the device, coordinates are int32 (x, y) pairs.  Nothing synchronises, no atomics, every output has one writer: two calls on the
+ * same inputs give the same bits.  An empty problem returns SN_OK and touches nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_PROMPT_MAX_POINTS 1024   /* capacity of a point store; points of one sn_rm_prompt_overlay call */
+
+/* test_step's "remember new point_3d" (nerf/trainer.py:803-809): pixels [M,2] (x, y) on the device, rays_o / rays_d [H*W,3], depth: H*W
+ * values depth_stride floats apart (1: a plain [H,W] image; 5: the depth column of the packed [N,5] render buffer, read in place):
+ *   point_3d[m] = o + d * depth at pixel (x, y), evaluated as fl(o + fl(d * depth)).
+ * The clicks are on the device, so one outside the image cannot be refused: it writes NaN, and nothing is read out of bounds. */
+int sn_rm_points_lift(const int32_t *pixels, uint32_t M, const float *rays_o, const float *rays_d, const float *depth, uint32_t depth_stride,
+                      uint32_t H, uint32_t W, float *point_3d, sn_stream_t stream);
+
+/* The add-or-remove rule of the remembered points (trainer.py:812-834) for ONE new point (what the reference's broadcast supports) on a
+ * fixed-capacity store on the device: xyz [cap,3], labels [cap], crucial [cap], count [1]; point [3] and label [1] on the device too.
+ *   dist_i = sqrt(sum_j (xyz[i,j] - point[j])^2) in fp32 over the stored points;
+ *   count == 0:                      the point becomes entry 0;
+ *   every dist_i > dist_thresh:      appended with crucial 0; with count == cap nothing changes and status[3] is set to 1;
+ *   otherwise:                       every stored point with dist_i <= dist_thresh (or a NaN distance) is removed, the others keep their
+ *                                    order; none left: the store is empty.
+ * Extension: the reference never touches crucial_point_label on this path (its flags and its points part ways after the first click);
+ * here crucial is compacted alongside and a new point is not crucial.
+ * status [4] int32 on the device: {what happened (0 first entry, 1 appended, 2 removed, 3 full), count before, count after, overflow}.
+ * The overflow word is only ever set: clear it once, look at it after any number of updates.  Entries behind count keep stale values.
+ * One workgroup, one launch, the count is not read on the host.  cap in 1 .. SN_PROMPT_MAX_POINTS (beyond: SN_ERR_UNSUPPORTED). */
+int sn_rm_point_store_update(float *xyz, int32_t *labels, int32_t *crucial, int32_t *count, uint32_t cap, const float *point, const int32_t *label,
+                             float dist_thresh, int32_t *status, sn_stream_t stream);
+
+/* The remembered points in V views (trainer.py:838-875 for test_step, :931-976 for decode_step; V > 1 scores every training view against
+ * the depth stack of update_depth, :1388-1402), one wave per view:
+ *   points [N,3], labels [N], crucial [N] or NULL; n_points: int32 on the device or NULL (= N), clamped to 0 .. N;
+ *   poses [V,16]: row-major cam2world, taken as affine -- the fourth row is NOT read; intrinsics [n_intr,4] (fx, fy, cx, cy), n_intr 1 or V;
+ *   depth: V images of H*W values, depth_stride floats apart (image v starts at v * H * W * depth_stride).
+ * Per view and point: the pose's upper 3 x 4 is inverted in fp64 (adjugate over determinant: the error of the reference's fp32
+ * torch.inverse is removed, not imitated) and the point transformed in fp64, the camera coordinates rounded to fp32; from there fp32 in
+ * the reference's order: px = W - ((fx * x) / z + cx), py = (fy * y) / z + cy.  With equal camera coordinates these equal torch's bits.
+ *   on screen iff px > -1 && px < W && py > -1 && py < H, tested in float: the reference's .long() truncates toward zero, so (-1, 0) is
+ *   pixel 0; a non-finite coordinate (z == 0) is off screen, where .long() is undefined.  The pixel is ((int)px, (int)py);
+ *   kept iff |(-z) - depth[py, px]| <= depth_tol (a NaN depth rejects the point).
+ * Compacted outputs, original order kept: coords [V,N,2], labels_out [V,N], kept_index [V,N] (index into points); with resize_ratio > 0
+ * (1024 / max(H, W) in the reference) also sam_coords = (int)((float)c * (float)ratio) and overlay_coords = (int)((double)sam / ratio),
+ * which are numpy's (c.astype(float32) * r).astype(int32) and (pc / r).astype(int32) of trainer.py:872-875.  Behind the kept points the
+ * rows are always filled: coordinates 0, labels -1 (SAM's padding label), index -1 -- a fixed-shape prompt needs no count.
+ * Uncompacted outputs, each may be NULL: cam [V,N,3], uv [V,N,2] (px, py), state [V,N] (0 off screen or not a point, 1 occluded, 2 kept).
+ * counts [V,4] = {on screen, kept, crucial kept (0 without crucial), is_valid}; is_valid = kept > 0 && crucial kept >= crucial_count &&
+ * kept >= valid_threshold (trainer.py:969-971). */
+int sn_rm_points_project(const float *points, const int32_t *labels, const int32_t *crucial, uint32_t N, const int32_t *n_points, const float *poses,
+                         uint32_t V, const float *intrinsics, uint32_t n_intr, const float *depth, uint32_t depth_stride, uint32_t H, uint32_t W,
+                         float depth_tol, int32_t crucial_count, int32_t valid_threshold, double resize_ratio /* 0: no sam / overlay coords */,
+                         int32_t *coords, int32_t *labels_out, int32_t *kept_index, int32_t *sam_coords, int32_t *overlay_coords, float *cam,
+                         float *uv, int32_t *state, int32_t *counts, sn_stream_t stream);
+
+/* decode_step's tail (trainer.py:979-991; test_step's :881-884) with overlay_mask and overlay_point (nerf/utils.py:23-29, 80-98), one launch:
+ *   image: H*W rows of image_stride >= 3 floats (3: packed; 5: the render buffer read in place); masks [M,H,W] uint8 or NULL (points only);
+ *   scores [M] on the device, or NULL with a fixed mask_index; coords [N,2], labels [N]; count: int32 on the device or NULL (= N).
+ *   selected = the first j whose score exceeds the running maximum, which starts at 0 with index 0: all scores <= 0 select mask 0, a NaN
+ *   is never selected;
+ *   count == 0: rgb = image, pred_mask = 0, selected = -1 (decode_step's else branch);
+ *   otherwise rgb = fl(fl(image * a) + fl(over * b)), a = (float)alpha, b = (float)(1.0 - alpha), over = (1,0,0) under the selected mask
+ *   and image elsewhere (masks NULL: rgb = image, as test_step draws the points without a decoder); on top the LAST point whose rectangle covers the pixel: green (0,1,0) for label 0, red otherwise.  The rectangle
+ *   is Python's slice [c - radius : c + radius] per axis: a negative start counts from the end (start += len), both bounds are clamped
+ *   to [0, len], start >= stop is empty -- a point closer than radius to the top or left edge is not drawn, one near the bottom or right
+ *   edge is clipped and drawn.
+ * Outputs: rgb [H,W,3] f32, rgb8 [H,W,3] uint8 (sn_rm_mask_output's conversion; 4-byte aligned), pred_mask [H,W] uint8 (the selected
+ * mask), each may be NULL (at least one is given); selected [1] int32 (-1 also without masks).
+ * N <= SN_PROMPT_MAX_POINTS, H and W <= 32767 (beyond: SN_ERR_UNSUPPORTED). */
+int sn_rm_prompt_overlay(const float *image, uint32_t image_stride, uint32_t H, uint32_t W, const uint8_t *masks, uint32_t M, const float *scores,
+                         int32_t mask_index, const int32_t *coords, const int32_t *labels, uint32_t N, const int32_t *count, int32_t radius, double alpha,
+                         float *rgb, uint8_t *rgb8, uint8_t *pred_mask, int32_t *selected, sn_stream_t stream);
+
 /* One stage's sample geometry (renderer.py:277-285): bins [N,T+1] in [0,1] -> real_bins [N,T+1] (distances along the
  * ray through the Mip-360 spacing of nears/fars [N]), rays_t [N,T] (mid-points), xyzs [N,T,3] (positions, contracted
  * into [-2,2]^3 like sn_rm_contract if `contract`).  Nothing here is differentiated by the reference. */

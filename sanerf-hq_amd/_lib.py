@@ -43,6 +43,7 @@ MASK_MAX_CLASSES, MASK_EVAL_WORKSPACE_BYTES = 32, 8192               # sn_rm_mas
 MASK_OUT_MODES = {"none": 0, "heatmap": 1, "composition": 2, "mask": 3}
 SSIM_WORKSPACE_BYTES, SSIM_MAX_STRIDE, SSIM_WINDOW = 8192, 64, 11     # sn_rm_image_ssim_accumulate
 DISTILL_WORKSPACE_FIXED_BYTES = 8256                                  # sn_rm_feature_distill_loss: the zero-at-rest part of its workspace
+PROMPT_MAX_POINTS = 1024                                              # sn_rm_point_store_update (capacity) / sn_rm_prompt_overlay (points)
 
 
 class AdamTensor(C.Structure):
@@ -176,6 +177,11 @@ _SIGNATURES = {
     "sn_rm_feature_distill_workspace_bytes": (C.c_size_t, [_u32, _u32, _u32, _u32, _u32]),
     "sn_rm_feature_distill_loss": (_int, [_vp, _u32, _u32, _u32, _u32, _vp, _u32, _u32, _f32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "sn_rm_feature_map": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "sn_rm_points_lift": (_int, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "sn_rm_point_store_update": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _f32, _vp, _vp]),
+    "sn_rm_points_project": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _f32, _i32, _i32, C.c_double,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sn_rm_prompt_overlay": (_int, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _i32, _vp, _vp, _u32, _vp, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "sn_rm_debug_occupancy": (_int, [_vp, _vp, _int]),
     "sn_rm_last_launch_info": (_int, [_vp]),
     "sn_rm_render_route_info": (_int, [C.POINTER(RenderCfg), C.POINTER(RenderIO), _vp]),

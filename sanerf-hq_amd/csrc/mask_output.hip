@@ -206,8 +206,7 @@ __global__ __launch_bounds__(256) void k_mask_output(const MaskOutArgs a) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         s_rgb[tid * 3 + j] = c[j];
-        const float v = fminf(fmaxf(c[j] * 255.0f, 0.0f), 255.0f);        // NaN -> 0 (fmaxf drops it)
-        s_bytes[tid * 3 + j] = (uint8_t)(uint32_t)v;
+        s_bytes[tid * 3 + j] = rgb8_of(c[j]);
     }
     __syncthreads();
     if (a.rgb) {

@@ -180,6 +180,9 @@ static inline bool table_aligned(const void *p) { return (reinterpret_cast<uintp
 
 __device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
+// The 8-bit value of a colour channel: trunc(clamp(255 x, 0, 255)), NaN -> 0 (fmaxf drops it).  On [0,1] the reference's (x * 255).astype(np.uint8).
+__device__ __forceinline__ uint8_t rgb8_of(float x) { return (uint8_t)(uint32_t)fminf(fmaxf(x * 255.0f, 0.0f), 255.0f); }
+
 // gridencoder.cu:45-79 — row of a grid vertex inside its level.
 template <uint32_t D>
 __device__ __forceinline__ uint32_t grid_row(const uint32_t (&p)[D], uint32_t res, uint32_t size, uint32_t mode) {
