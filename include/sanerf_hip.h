@@ -438,6 +438,76 @@ int sn_rm_prompt_overlay(const float *image, uint32_t image_stride, uint32_t H, 
                          int32_t mask_index, const int32_t *coords, const int32_t *labels, uint32_t N, const int32_t *count, int32_t radius, double alpha,
                          float *rgb, uint8_t *rgb8, uint8_t *pred_mask, int32_t *selected, sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A training batch drawn on the device (collate.hip): the device-side core of NeRFDataset.collate (provider.py:894-1114) as one gather
+ * launch plus one draw launch per part that draws cells, with all randomness in tensors the caller fills (torch.rand, Tensor.exponential_(): both capturable), so that
+ * collate -> render -> loss -> Adam can be one HIP graph and a batch is a pure function of (dataset, random tensors).  Division is
+ * IEEE-rounded, no float atomics, nothing synchronises, nothing is read on the host: two calls on the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+#define SN_DRAW_MAX_CELLS 65536     /* cells of one row of sn_rm_weighted_draw */
+
+/* Weighted sampling without replacement -- torch.multinomial's own exponential race (utils.py:218, :248): the same distribution, other bits.
+ *   expo [R,C]: standard exponential variates from the caller; out [R,n] int64; status: one int32 on the device, only ever set.
+ *   Row r draws from weights row r of weights [R,C] (row_u NULL), or -- the centres of the local patches, provider.py:982-993, whose
+ *   cameras are drawn on the device -- from row min((int)(row_u[r] * M), M - 1) of weights [M,C]: the row-index table is the table of
+ *   uniform variates that sn_rm_collate_gather turns into the patches' cameras with the same formula, so no row is gathered beforehand;
+ *   or (row_index [R] int64 on the device, clamped to 0 .. M-1: the loader's image index of a single-image batch) from that row.
+ * Per row the n smallest of (key, cell) in lexicographic order, key = expo / weights as an fp32 IEEE division, in ASCENDING CELL INDEX
+ * (torch returns them in key order; nothing downstream depends on the order of a ray batch, inds_coarse stays aligned with its rays).
+ * A cell is never selected if its weight is <= 0 or NaN, or if its key is not finite (or negative, which no exponential variate gives; -0
+ * is 0).  A row with fewer than n selectable cells (the reference raises there) gets -1 in the tail of its row and *status = 1 -- the
+ * choice of sn_rm_ray_pair_select.  One workgroup per row: n == 1 a (key, cell) minimum through a fixed butterfly; n > 1 a radix select
+ * on the key bits (four 8-bit passes over a 256-bin LDS histogram, ties at the threshold to the smaller cell) and one order-preserving
+ * compaction pass.  1 <= n <= C <= SN_DRAW_MAX_CELLS (a longer row: SN_ERR_UNSUPPORTED). */
+int sn_rm_weighted_draw(const float *weights, const float *expo, uint32_t R, uint32_t C, uint32_t n, const float *row_u, const int64_t *row_index,
+                        uint32_t M, int64_t *out, int32_t *status, sn_stream_t stream);
+
+/* Draw -> rays + supervision, one lane per ray, one launch (the first ceil(N / 256) workgroups: the main part; the rest: the patches).
+ * Dataset tensors, read in place: poses [M,16] row-major cam2world, intrinsics [n_intrinsics,4] (1 or M), images [M,H,W,3|4] uint8,
+ * masks [M,H,W,mask_channels] of 1-, 4- or 8-byte elements copied as raw bytes (uint8, float32, int64 alike), error_map [M,S*S],
+ * cam_near_far [M,2]; the last four may be NULL.  With pick(u, n) = min((int)(u * n), n - 1), the product in fp32 (the min guards the
+ * upper end; a u outside [0,1) or a NaN is clamped into the range rather than indexing out of bounds):
+ *   main part, N rays, mode SN_COLLATE_UNIFORM (random_image_batch, provider.py:910, utils.py:260): u [N,3];
+ *     cam = pick(u0, M), row = pick(u1, H), col = pick(u2, W);
+ *   mode SN_COLLATE_ERROR_MAP (one image: index, or *index_dev when given, clamped to 0 .. M-1; utils.py:247-256): cells [N] from
+ *     sn_rm_weighted_draw and u [N,2]; gx = cell / S, gy = cell % S, row = min((int)(fl(fl(gx * sx) + fl(u0 * sx))), H - 1) with
+ *     sx = (float)((double)H / S), col likewise from gy, u1 and sy = (float)((double)W / S);
+ *   local part, L patches of p x p rays appended after the main part (provider.py:982-993, utils.py:217-244): patch k has camera
+ *     pick(ul[k], M) and centre cell centres[k] (sn_rm_weighted_draw with n = 1 and row_u = ul); its corner is
+ *     trunc(clamp(fl(fl(cx * sx) - p / 2), 0, H - p - 1)) with cx = cell / S and the integer p / 2, likewise for W with cell % S and sy (what
+ *     the reference does); offsets in meshgrid(indexing="ij") order.  p < H and p < W.
+ * A cell outside 0 .. S*S-1 (the -1 of a short draw) gives rays and float supervision of NaN, -1 in i / j / inds_coarse, zero mask bytes;
+ * index, cam_near_far and poses still describe the ray's camera.
+ * Outputs, rows N + L*p*p unless noted, each with its own row stride in ELEMENTS and each may be NULL: rays_o / rays_d (3 floats; the exact
+ * operation sequence of sn_rm_rays_from_pixels: equal bits), index_out / i_out (column) / j_out (row) / inds_coarse int64 (utils.py:294-300:
+ * the cell in error-map mode, else (int)(row * (float)(coarse_size / H)) * coarse_size + (int)(col * (float)(coarse_size / W))), images_out
+ * [N only, 3|4] = (float)byte / 255.0f, masks_out, error_maps_out = error_map[cam, (int)(row * (float)(S / H)) * S + (int)(col * (float)(S / W))]
+ * (the column scale S / W of nerf.utils.collate_rays), cam_near_far_out (2), poses_out (16), intrinsics_out (4: the camera's fx, fy, cx, cy). */
+enum { SN_COLLATE_UNIFORM = 0, SN_COLLATE_ERROR_MAP = 1 };
+typedef struct sn_collate_desc {
+    const float   *poses, *intrinsics;
+    const uint8_t *images;
+    const void    *masks;
+    const float   *error_map, *cam_near_far;
+    uint32_t       M, n_intrinsics, H, W, image_channels, mask_channels, mask_elem_bytes, S, coarse_size;
+    uint32_t       N;
+    int32_t        mode, index;
+    const int64_t *index_dev;
+    const float   *u;
+    const int64_t *cells;
+    uint32_t       L, p;
+    const float   *ul;
+    const int64_t *centres;
+    float         *rays_o, *rays_d;
+    int64_t       *index_out, *i_out, *j_out, *inds_coarse;
+    float         *images_out;
+    void          *masks_out;
+    float         *error_maps_out, *cam_near_far_out, *poses_out, *intrinsics_out;
+    uint32_t       rays_o_stride, rays_d_stride, index_stride, i_stride, j_stride, inds_coarse_stride, images_stride, masks_stride,
+                   error_maps_stride, cam_near_far_stride, poses_stride, intrinsics_stride;
+} sn_collate_desc;
+int sn_rm_collate_gather(const sn_collate_desc *desc, sn_stream_t stream);
+
 /* One stage's sample geometry (renderer.py:277-285): bins [N,T+1] in [0,1] -> real_bins [N,T+1] (distances along the
  * ray through the Mip-360 spacing of nears/fars [N]), rays_t [N,T] (mid-points), xyzs [N,T,3] (positions, contracted
  * into [-2,2]^3 like sn_rm_contract if `contract`).  Nothing here is differentiated by the reference. */

@@ -44,6 +44,8 @@ MASK_OUT_MODES = {"none": 0, "heatmap": 1, "composition": 2, "mask": 3}
 SSIM_WORKSPACE_BYTES, SSIM_MAX_STRIDE, SSIM_WINDOW = 8192, 64, 11     # sn_rm_image_ssim_accumulate
 DISTILL_WORKSPACE_FIXED_BYTES = 8256                                  # sn_rm_feature_distill_loss: the zero-at-rest part of its workspace
 PROMPT_MAX_POINTS = 1024                                              # sn_rm_point_store_update (capacity) / sn_rm_prompt_overlay (points)
+DRAW_MAX_CELLS = 65536                                                # sn_rm_weighted_draw: cells of one row
+COLLATE_UNIFORM, COLLATE_ERROR_MAP = 0, 1                             # sn_collate_desc.mode
 
 
 class AdamTensor(C.Structure):
@@ -66,6 +68,18 @@ class EvalRecord(C.Structure):
 class SsimRecord(C.Structure):
     """sn_ssim_record: what raymarching.image_ssim_accumulate has accumulated (SSIMMeter's V and N, and the last image's value)."""
     _fields_ = [("ssim_sum", C.c_double), ("last", C.c_double), ("images", C.c_uint64)]
+
+
+class CollateDesc(C.Structure):
+    """sn_collate_desc: the dataset tensors, the draws and the outputs (each with its row stride in elements) of sn_rm_collate_gather."""
+    _fields_ = ([(n, C.c_void_p) for n in ("poses", "intrinsics", "images", "masks", "error_map", "cam_near_far")]
+                + [(n, C.c_uint32) for n in ("M", "n_intrinsics", "H", "W", "image_channels", "mask_channels", "mask_elem_bytes", "S", "coarse_size", "N")]
+                + [("mode", C.c_int32), ("index", C.c_int32), ("index_dev", C.c_void_p), ("u", C.c_void_p), ("cells", C.c_void_p),
+                   ("L", C.c_uint32), ("p", C.c_uint32), ("ul", C.c_void_p), ("centres", C.c_void_p)]
+                + [(n, C.c_void_p) for n in ("rays_o", "rays_d", "index_out", "i_out", "j_out", "inds_coarse", "images_out", "masks_out",
+                                             "error_maps_out", "cam_near_far_out", "poses_out", "intrinsics_out")]
+                + [(n + "_stride", C.c_uint32) for n in ("rays_o", "rays_d", "index", "i", "j", "inds_coarse", "images", "masks", "error_maps",
+                                                         "cam_near_far", "poses", "intrinsics")])
 
 
 class RenderTuning(C.Structure):
@@ -182,6 +196,8 @@ _SIGNATURES = {
     "sn_rm_points_project": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _f32, _i32, _i32, C.c_double,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sn_rm_prompt_overlay": (_int, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _i32, _vp, _vp, _u32, _vp, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "sn_rm_weighted_draw": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "sn_rm_collate_gather": (_int, [C.POINTER(CollateDesc), _vp]),
     "sn_rm_debug_occupancy": (_int, [_vp, _vp, _int]),
     "sn_rm_last_launch_info": (_int, [_vp]),
     "sn_rm_render_route_info": (_int, [C.POINTER(RenderCfg), C.POINTER(RenderIO), _vp]),

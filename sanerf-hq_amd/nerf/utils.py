@@ -162,6 +162,110 @@ def collate_rays(poses, intrinsics, H, W, num_rays, index=None, images=None, mas
     return res
 
 
+class DeviceCollate:
+    """`collate_rays` as launches that a HIP graph can hold: the batch is drawn by `raymarching.weighted_draw` and
+    `raymarching.collate_gather` straight into static tensors this object owns, and all randomness comes from static tensors that
+    `draw()` fills with torch.rand / Tensor.exponential_() (both capturable).  A batch is a pure function of (dataset, randoms).
+
+    Built once with the preloaded dataset tensors (read in place, never copied) and the batch geometry, which has collate_rays's meaning:
+    random_image_batch: one camera and one pixel per ray (u [N,3]); otherwise the N pixels come from image `index`'s error-map row
+    (use_error_map; expo [1,S*S] and u [N,2]).  num_local_sample patches of local_patch_size^2 rays around cells drawn from their own
+    cameras' error maps follow (ul [L], expo_local [L,S*S]).  Launches per draw(): the gather, plus one weighted draw per part that draws
+    cells -- two for the object-field script's settings (uniform main part + local patches), three when both parts draw cells.
+
+    draw() returns collate_rays's keys as views of the static tensors (the next draw() overwrites them): rays_o, rays_d, poses,
+    masks, error_maps, cam_near_far over all N + L p^2 rays; index, intrinsics, i, j, inds_coarse, images over the N main rays.
+    Two stated deviations from the torch route: drawn cells come in ascending cell order, not key order, and a row of the error map with
+    too few positive cells gives rays of NaN and sets `status` (sticky, on the device) where torch.multinomial raises."""
+
+    def __init__(self, poses, intrinsics, H, W, num_rays, images=None, masks=None, error_map=None, cam_near_far=None, random_image_batch=True,
+                 use_error_map=False, error_map_size=128, num_local_sample=0, local_patch_size=1, index=0):
+        dev = poses.device
+        if isinstance(intrinsics, np.ndarray):
+            intrinsics = torch.as_tensor(intrinsics.reshape(-1, 4).astype(np.float32), device=dev)
+        self.data = dict(poses=poses.reshape(-1, 4, 4), intrinsics=intrinsics.reshape(-1, 4), images=images, masks=masks, error_map=error_map,
+                         cam_near_far=cam_near_far)
+        self.H, self.W, self.N, self.S = int(H), int(W), int(num_rays), int(error_map_size)
+        self.L, self.p = int(num_local_sample), int(local_patch_size)
+        self.cells_mode = not random_image_batch
+        if self.cells_mode and not use_error_map:
+            raise RuntimeError("DeviceCollate: a single-image batch draws its pixels from the error map (use_error_map); uniform draws are per-ray cameras")
+        if (self.cells_mode or self.L > 0) and error_map is None:
+            raise RuntimeError("DeviceCollate: drawing cells needs the error map")
+        M, C, f32 = self.data["poses"].shape[0], self.S * self.S, torch.float32
+        self.randoms = {"u": torch.zeros(self.N, 2 if self.cells_mode else 3, device=dev, dtype=f32)}
+        self.cells = self.centres = None
+        if self.cells_mode:
+            self.randoms["expo"] = torch.ones(1, C, device=dev, dtype=f32)
+            self.cells = torch.full((1, self.N), -1, device=dev, dtype=torch.int64)
+            self.index = torch.zeros(1, device=dev, dtype=torch.int64)
+            self.set_index(index)
+        if self.L > 0:
+            self.randoms["ul"] = torch.zeros(self.L, device=dev, dtype=f32)
+            self.randoms["expo_local"] = torch.ones(self.L, C, device=dev, dtype=f32)
+            self.centres = torch.full((self.L, 1), -1, device=dev, dtype=torch.int64)
+        self.status = torch.zeros(1, device=dev, dtype=torch.int32)
+        # with the error map the coarse cells are the map's (provider.py:959-968); without one collate_rays passes H
+        self.coarse_size = self.S if error_map is not None else self.H
+        total = self.N + self.L * self.p * self.p
+        z = lambda *s, dt=f32: torch.zeros(*s, device=dev, dtype=dt)
+        self.out = {"rays_o": z(total, 3), "rays_d": z(total, 3), "poses": z(total, 16), "intrinsics": z(total, 4)}
+        for k in ("index", "i", "j", "inds_coarse"):
+            self.out[k] = z(total, dt=torch.int64)
+        if images is not None:
+            self.out["images"] = z(self.N, images.shape[-1])
+        if masks is not None:
+            self.out["masks"] = z(total, masks.shape[-1], dt=masks.dtype)
+        if error_map is not None:
+            self.out["error_maps"] = z(total)
+        if cam_near_far is not None:
+            self.out["cam_near_far"] = z(total, 2)
+        self.M = M
+
+    def set_index(self, index) -> None:
+        """The image a single-image batch draws from (the loader's index): an int, or a one-element tensor copied on the device."""
+        if torch.is_tensor(index):
+            self.index.copy_(index.reshape(-1)[:1])
+        else:
+            self.index.fill_(int(index))
+
+    def fill_randoms(self) -> None:
+        for k, t in self.randoms.items():
+            if k.startswith("expo"):
+                t.exponential_()
+            else:
+                torch.rand(t.shape, out=t)
+
+    def draw(self, randoms=None, index=None):
+        from ..raymarching import collate_gather, weighted_draw
+        if randoms is None:
+            self.fill_randoms()
+        else:
+            if set(randoms) != set(self.randoms):
+                raise RuntimeError(f"DeviceCollate.draw: randoms must hold {sorted(self.randoms)}, got {sorted(randoms)}")
+            for k, t in self.randoms.items():
+                t.copy_(randoms[k].reshape(t.shape))
+        if index is not None and self.cells_mode:
+            self.set_index(index)
+        d, r = self.data, self.randoms
+        if self.cells_mode:
+            weighted_draw(d["error_map"].reshape(-1, self.S * self.S), r["expo"], self.N, out=self.cells, status=self.status, row_index=self.index)
+        if self.L > 0:
+            weighted_draw(d["error_map"].reshape(-1, self.S * self.S), r["expo_local"], 1, out=self.centres, status=self.status, row_u=r["ul"])
+        collate_gather(d["poses"], d["intrinsics"], self.H, self.W, u=r["u"], cells=self.cells, index=self.index if self.cells_mode else 0,
+                       images=d["images"], masks=d["masks"], error_map=d["error_map"], cam_near_far=d["cam_near_far"],
+                       error_map_size=self.S if d["error_map"] is not None else 0, coarse_size=self.coarse_size, ul=r.get("ul"),
+                       centres=self.centres, patch_size=self.p, out=self.out)
+        o, N = self.out, self.N
+        res = {"H": self.H, "W": self.W, "index": o["index"][:N], "poses": o["poses"].view(-1, 4, 4),
+               "intrinsics": o["intrinsics"][:N] if d["intrinsics"].shape[0] > 1 else d["intrinsics"], "rays_o": o["rays_o"], "rays_d": o["rays_d"],
+               "i": o["i"][:N], "j": o["j"][:N], "inds_coarse": o["inds_coarse"][:N], "error_maps": o.get("error_maps")}
+        for k in ("images", "masks", "cam_near_far"):
+            if k in o:
+                res[k] = o[k]
+        return res
+
+
 # ---------------------------------------------------------------------------------------------
 # checkpoints in the reference's format (nerf/trainer.py:1685-1741 save, :1779-1800 load)
 # ---------------------------------------------------------------------------------------------
