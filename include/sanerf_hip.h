@@ -888,6 +888,34 @@ typedef struct sn_adam_group {
 int sn_adam_step_multi(const sn_adam_tensor *tensors, uint32_t n_tensors, const sn_adam_group *groups, uint32_t n_groups,
                        const float *lr_scale_device, uint32_t *ticket, sn_stream_t stream);
 
+/* Exponential moving average of MANY parameter tensors in ONE launch: the update of torch_ema.ExponentialMovingAverage, which the
+ * reference's trainer runs after every optimiser step (main.py:302 ema_decay=0.95; nerf/trainer.py:1231-1232).  Per element, exactly
+ *     shadow = shadow - (shadow - param) * omd
+ * in three separately rounded fp32 operations (tmp = s - p; tmp.mul_(omd); s.sub_(tmp)); `param` is only read.  The results have the
+ * bit patterns of that statement as torch evaluates it on an x86 host, denormals kept; a NaN result is encoded as the host encodes it
+ * (the first NaN operand, quieted; 0xffc00000 where inf - inf or inf * 0 produced it), which IEEE 754 leaves open.  The records travel
+ * in the kernel arguments like sn_adam_step_multi's, at most SN_EMA_MULTI_MAX_TENSORS per call (more is an error: several calls on
+ * one stream); every tensor is cut into chunks of 4096 floats that the workgroups walk in a grid-stride loop; n = 0 is fine.
+ * num_updates_device == NULL: omd = (float)(1.0 - decay), formed on the host.
+ * num_updates_device != NULL: torch_ema's warm-up, with the count on the device.  The kernel reads n = *num_updates_device + 1 when
+ *     it RUNS and forms d = min(decay, (1.0 + n) / (10.0 + n)), omd = (float)(1.0 - d) in double -- the operations Python performs
+ *     on the host, hence the same bits -- so that a launch captured in a HIP graph follows the warm-up when it is replayed.
+ * flags & SN_EMA_ADVANCE: the call ALSO advances the count.  The workgroup that finishes last stores n; `ticket` is a device word,
+ *     zero before its first use and left zero by every call; nobody spins or waits on it.  A model of more than
+ *     SN_EMA_MULTI_MAX_TENSORS tensors is several calls that all read count + 1; only the last one carries SN_EMA_ADVANCE.  A call
+ *     with nothing to update but SN_EMA_ADVANCE set still advances the count.
+ * decay lies in [0, 1]; shadow and param are 16-byte aligned and distinct; the count is 8-byte, the ticket 4-byte aligned.
+ * All arguments are checked on the host before anything touches the device. */
+#define SN_EMA_MULTI_MAX_TENSORS 32
+#define SN_EMA_ADVANCE 1
+typedef struct sn_ema_tensor {
+    float *shadow;
+    const float *param;
+    uint64_t n;
+} sn_ema_tensor;
+int sn_ema_update_multi(const sn_ema_tensor *tensors, uint32_t n_tensors, double decay, uint64_t *num_updates_device,
+                        uint32_t *ticket, int flags, sn_stream_t stream);
+
 /* Measurement hook (bench.py): bracket every kernel sn_rm_render_rays launches with hipEvents on the
  * caller's stream.  Classes: 0 weight pack, 1..3 proposal stage k, 4 final stage.  profile_read
  * synchronises, returns summed device milliseconds and launch counts per class, and resets. */

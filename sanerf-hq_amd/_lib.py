@@ -39,6 +39,7 @@ EXP_NONE, EXP_ROLE_SPLIT, EXP_LDS_LEVEL0, EXP_FINAL_ONE_WG = 0, 1, 2, 3         
 BUILD_EXPERIMENTS, BUILD_POISON_LDS = 1, 2                           # sn_build_flags()
 ADAM_ZERO_GRAD, ADAM_LAZY = 1, 2                                     # sn_adam_step flags
 ADAM_MULTI_MAX_TENSORS, ADAM_MULTI_MAX_GROUPS = 32, 8                # sn_adam_step_multi: per call
+EMA_MULTI_MAX_TENSORS, EMA_ADVANCE = 32, 1                           # sn_ema_update_multi: tensors per call; flags
 MASK_MAX_CLASSES, MASK_EVAL_WORKSPACE_BYTES = 32, 8192               # sn_rm_mask_output / sn_rm_mask_eval_accumulate
 MASK_OUT_MODES = {"none": 0, "heatmap": 1, "composition": 2, "mask": 3}
 SSIM_WORKSPACE_BYTES, SSIM_MAX_STRIDE, SSIM_WINDOW = 8192, 64, 11     # sn_rm_image_ssim_accumulate
@@ -56,6 +57,11 @@ class AdamTensor(C.Structure):
 class AdamGroup(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("maximize", C.c_int32), ("flags", C.c_int32)]
+
+
+class EmaTensor(C.Structure):
+    """sn_ema_tensor: one (shadow, parameter) pair of sn_ema_update_multi."""
+    _fields_ = [("shadow", C.c_void_p), ("param", C.c_void_p), ("n", C.c_uint64)]
 
 
 class EvalRecord(C.Structure):
@@ -172,6 +178,7 @@ _SIGNATURES = {
     "sn_rm_mask_head": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _f32, C.POINTER(GridDesc), C.POINTER(MlpDesc), _vp, _vp, C.c_size_t, _vp]),
     "sn_adam_step": (_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _u32, _vp, _int, _int, _vp]),
     "sn_adam_step_multi": (_int, [C.POINTER(AdamTensor), _u32, C.POINTER(AdamGroup), _u32, _vp, _vp, _vp]),
+    "sn_ema_update_multi": (_int, [C.POINTER(EmaTensor), _u32, C.c_double, _vp, _vp, _int, _vp]),
     "sn_linear_wgrad_workspace_bytes": (C.c_size_t, [_u32, _u32, _u32]),
     "sn_linear_wgrad": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, C.c_size_t, _vp]),
     "sn_rm_render_workspace_bytes": (C.c_size_t, [C.POINTER(RenderCfg), _u32, _u32]),

@@ -179,6 +179,109 @@ __global__ __launch_bounds__(256) void k_adam_multi(const AdamMultiArgs a) {
     }
 }
 
+// ---- parameter average, many tensors, one launch (sn_ema_update_multi) ---------------------------------------------------------
+// torch_ema's update after the optimiser step: shadow = shadow - (shadow - param) * omd, three fp32 roundings (the build's
+// -ffp-contract=off keeps them apart; no fmaf here).  12 bytes per element: two streams read, one written.  The layout is
+// k_adam_multi's -- records in the kernel arguments, chunks of MULTI_CHUNK floats, the same prefix scan from chunk id to tensor, the
+// same grid cap -- restated here and not shared as code: k_adam_multi stays the kernel it was.
+struct EmaMultiTensor {
+    float *s;
+    const float *p;
+    uint64_t n;
+};
+struct EmaMultiArgs {
+    EmaMultiTensor t[SN_EMA_MULTI_MAX_TENSORS];
+    uint32_t first_chunk[SN_EMA_MULTI_MAX_TENSORS + 1];
+    uint32_t n_tensors;
+    float omd;                    // host form: (float)(1 - decay)
+    double decay;
+    uint64_t *count;              // device form: torch_ema's num_updates, read when the kernel runs -- or NULL
+    uint32_t *ticket;             // given: the last workgroup stores count + 1
+};
+static_assert(sizeof(EmaMultiArgs) <= 4096, "the records must fit the kernel-argument block");
+
+__device__ __forceinline__ float ema_one(float s, float p, float omd) {
+    const float tmp = s - p;                                                 // tmp = s_param - param
+    const float scaled = tmp * omd;                                          // tmp.mul_(one_minus_decay)
+    float r = s - scaled;                                                    // s_param.sub_(tmp)
+    // The contract is the bit pattern of that statement as torch evaluates it on the host, and IEEE 754 leaves open WHICH NaN an
+    // operation delivers.  The host's SSE / AVX units deliver the first NaN operand, quieted, and 0xffc00000 where an operation
+    // without a NaN operand is invalid (inf - inf, inf * 0); gfx950 delivers 0x7fc00000 there (measured: the only elements of the
+    // bit-equality test that differed).  So a NaN result is restated as the host forms it; every other result is untouched.
+    if (r != r) {
+        const float first = s != s ? s : p;                                  // (omd is never NaN)
+        r = first != first ? __uint_as_float(__float_as_uint(first) | 0x00400000u) : __uint_as_float(0xffc00000u);
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(256) void k_ema_multi(const EmaMultiArgs a) {
+    SN_POISON_ALL();
+    float omd = a.omd;
+    uint64_t n = 0;
+    if (a.count) {                                                           // decay = min(decay, (1 + n) / (10 + n)), as Python forms it: in double
+        n = __hip_atomic_load(a.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+        const double warm = (1.0 + (double)n) / (10.0 + (double)n);
+        const double d = warm < a.decay ? warm : a.decay;
+        omd = (float)(1.0 - d);
+    }
+    const uint32_t total = a.first_chunk[a.n_tensors];
+    uint32_t ti = 0;
+    for (uint32_t c = blockIdx.x; c < total; c += gridDim.x) {
+        while (c >= a.first_chunk[ti + 1]) ++ti;
+        const EmaMultiTensor &t = a.t[ti];
+        float *s = t.s;
+        const float *p = t.p;
+        const uint64_t nq = t.n >> 2;
+        const uint64_t q0 = (uint64_t)(c - a.first_chunk[ti]) * (MULTI_CHUNK / 4) + threadIdx.x;
+        // all eight loads of the chunk first (the compiler may not move a load of p above a store to s on its own), then the stores
+        constexpr uint32_t Q = MULTI_CHUNK / 4 / 256;
+        float4 sv[Q], pv[Q];
+#pragma unroll
+        for (uint32_t k = 0; k < Q; ++k) {
+            const uint64_t i = q0 + k * 256u;
+            if (i < nq) {
+                sv[k] = reinterpret_cast<const float4 *>(s)[i];
+                pv[k] = reinterpret_cast<const float4 *>(p)[i];
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < Q; ++k) {
+            const uint64_t i = q0 + k * 256u;
+            if (i < nq) {
+                float4 r;
+                r.x = ema_one(sv[k].x, pv[k].x, omd); r.y = ema_one(sv[k].y, pv[k].y, omd);
+                r.z = ema_one(sv[k].z, pv[k].z, omd); r.w = ema_one(sv[k].w, pv[k].w, omd);
+                reinterpret_cast<float4 *>(s)[i] = r;
+            }
+        }
+        // the tensor's last chunk takes the n % 4 elements behind the last whole quad
+        const uint64_t e = (nq << 2) + threadIdx.x;
+        if (c + 1 == a.first_chunk[ti + 1] && e < t.n) s[e] = ema_one(s[e], p[e], omd);
+    }
+    // Advancing the count: k_adam_multi's ticket -- each workgroup draws one after its read of the count, the one that draws the last
+    // knows that all the others are past theirs, stores n and puts the ticket back to zero; nobody waits -- with a lighter draw.
+    // What has to hold is that no USED read of the count comes after the store.  The count is read and stored with relaxed agent-scope
+    // atomic accesses (no data race; neither L1 nor the scalar cache serves them).  A wave that stores a shadow element has its count
+    // by then -- the value is in omd, which every stored element carries -- so it has it before it reaches the barrier, and thread 0
+    // draws behind the barrier.  (A wave with nothing to store never uses what it read.)  The draws are read-modify-writes of one
+    // word, totally ordered where they execute; the store of n depends on the value the last draw returned, so it is issued after
+    // every other workgroup's draw.  Nothing is PUBLISHED through the ticket -- the shadows reach the next launch through the end of
+    // this one -- so the agent-scope release of k_adam_multi's acq_rel draw, a write-back of the XCD's L2 just filled with 16 KiB of
+    // shadow lines per workgroup, is left out: it cost 0.08 ms of the 0.14 ms of an update of the RGB-mode model
+    // (profiles/r07/README.md).
+    if (a.ticket) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t mine = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (mine == gridDim.x - 1) {
+                __hip_atomic_store(a.count, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
 }  // namespace sn
 
 using namespace sn;
@@ -262,5 +365,46 @@ extern "C" int sn_adam_step_multi(const sn_adam_tensor *tensors, uint32_t n_tens
     if (blocks == 0) blocks = 1;                                          // nothing to update, counts to advance
     hipLaunchKernelGGL(k_adam_multi, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, a);
     SN_LAUNCH_CHECK("k_adam_multi");
+    return SN_OK;
+}
+
+extern "C" int sn_ema_update_multi(const sn_ema_tensor *tensors, uint32_t n_tensors, double decay, uint64_t *num_updates_device,
+                                   uint32_t *ticket, int flags, sn_stream_t stream) {
+    const bool advance = (flags & SN_EMA_ADVANCE) != 0;
+    SN_REQUIRE(n_tensors <= SN_EMA_MULTI_MAX_TENSORS, "ema_update_multi: %u tensors, at most %d per call (split the model into several calls)", n_tensors, SN_EMA_MULTI_MAX_TENSORS);
+    SN_REQUIRE((flags & ~SN_EMA_ADVANCE) == 0, "ema_update_multi: unknown flags 0x%x", (unsigned)flags);
+    SN_REQUIRE(decay >= 0.0 && decay <= 1.0, "ema_update_multi: decay must lie in [0, 1]");
+    SN_REQUIRE(!advance || num_updates_device, "ema_update_multi: SN_EMA_ADVANCE needs num_updates_device (there is no count to advance)");
+    SN_REQUIRE(!advance || ticket, "ema_update_multi: SN_EMA_ADVANCE needs a ticket");
+    SN_REQUIRE((reinterpret_cast<uintptr_t>(num_updates_device) & 7u) == 0, "ema_update_multi: num_updates_device must be 8-byte aligned");
+    SN_REQUIRE((reinterpret_cast<uintptr_t>(ticket) & 3u) == 0, "ema_update_multi: ticket must be 4-byte aligned");
+    SN_REQUIRE(tensors || n_tensors == 0, "ema_update_multi: tensors must be a host array");
+    EmaMultiArgs a = {};
+    uint64_t chunks = 0;
+    for (uint32_t i = 0; i < n_tensors; ++i) {
+        const sn_ema_tensor &t = tensors[i];
+        if (t.n) {
+            SN_REQUIRE(t.shadow && t.param, "ema_update_multi: shadow/param must be device pointers (tensor %u)", i);
+            SN_REQUIRE(table_aligned(t.shadow) && table_aligned(t.param), "ema_update_multi: tensors must be 16-byte aligned (tensor %u)", i);
+            SN_REQUIRE(t.shadow != t.param, "ema_update_multi: shadow and param are the same tensor (tensor %u)", i);
+        }
+        EmaMultiTensor &d = a.t[i];
+        d.s = t.shadow; d.p = t.param; d.n = t.n;
+        a.first_chunk[i] = (uint32_t)chunks;
+        chunks += (t.n + MULTI_CHUNK - 1) / MULTI_CHUNK;
+        SN_REQUIRE(chunks < (1ull << 31), "ema_update_multi: more than 2^43 elements in one call");
+    }
+    a.first_chunk[n_tensors] = (uint32_t)chunks;
+    a.n_tensors = n_tensors;
+    a.decay = decay;
+    a.omd = (float)(1.0 - decay);
+    a.count = num_updates_device;
+    a.ticket = advance ? ticket : nullptr;                                // (a ticket without SN_EMA_ADVANCE is not touched)
+    if (chunks == 0 && !advance) return SN_OK;
+    uint64_t blocks = chunks;
+    if (blocks > 256u * 16u) blocks = 256u * 16u;                         // k_adam_multi's cap: 16 workgroups per CU, grid-stride beyond
+    if (blocks == 0) blocks = 1;                                          // nothing to update, a count to advance
+    hipLaunchKernelGGL(k_ema_multi, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    SN_LAUNCH_CHECK("k_ema_multi");
     return SN_OK;
 }

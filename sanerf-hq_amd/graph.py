@@ -9,11 +9,13 @@ cached tensors, every kernel goes to torch's current stream, the binned grid bac
 
     opt = Adam(params, lr=..., eps=1e-15, capturable=True, multi_tensor=True)     # one launch for all parameter tensors, counts advanced in-kernel
     sched = DeviceLRScale(opt, lambda it: 0.1 ** min(it / iters, 1))              # the reference's LambdaLR (main.py:298-303), factor on the device
+    ema = ParamEMA(model.parameters(), decay=0.95, on_write=model.invalidate_render_plan)   # torch_ema's average, update count on the device
     def step():
         opt.zero_grad(set_to_none=True)
         out = model.render(rays_o, rays_d, ...)          # rays_o / rays_d / targets: STATIC tensors, refilled with .copy_() between replays
         loss = ...
         loss.backward(); opt.step()
+        ema.update()                                     # one more launch; its warm-up decay is formed in the kernel, so replays follow it
         return loss
     g = GraphedStep(step, warmup=3)
     for batch in loader:

@@ -269,9 +269,10 @@ class DeviceCollate:
 # ---------------------------------------------------------------------------------------------
 # checkpoints in the reference's format (nerf/trainer.py:1685-1741 save, :1779-1800 load)
 # ---------------------------------------------------------------------------------------------
-def save_checkpoint(model, path, epoch=0, global_step=0, stats=None, optimizer=None, lr_scheduler=None):
-    """{'epoch', 'global_step', 'stats', 'model': state_dict[, 'optimizer', 'lr_scheduler']} -- what the reference's
-    Trainer.save_checkpoint writes (the `full=True` extras only when given), so its load_checkpoint reads it back."""
+def save_checkpoint(model, path, epoch=0, global_step=0, stats=None, optimizer=None, lr_scheduler=None, ema=None):
+    """{'epoch', 'global_step', 'stats', 'model': state_dict[, 'optimizer', 'lr_scheduler', 'ema']} -- what the reference's
+    Trainer.save_checkpoint writes (the `full=True` extras only when given; 'ema': trainer.py:1700-1701, the state_dict of an
+    optim.ParamEMA in torch_ema's layout), so its load_checkpoint reads it back."""
     import torch
     state = {"epoch": int(epoch), "global_step": int(global_step),
              "stats": stats if stats is not None else {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None},
@@ -280,6 +281,8 @@ def save_checkpoint(model, path, epoch=0, global_step=0, stats=None, optimizer=N
         state["optimizer"] = optimizer.state_dict()
     if lr_scheduler is not None:
         state["lr_scheduler"] = lr_scheduler.state_dict()
+    if ema is not None:
+        state["ema"] = ema.state_dict()
     torch.save(state, path)
     return state
 

@@ -23,6 +23,11 @@ a state loaded from elsewhere is packed into that buffer on the next step.
 
 `DeviceLRScale(optimizer, lr_lambda)` is the reference's `LambdaLR` (main.py:298-303) for this route: the factor lives in a device
 float that the kernel reads when it RUNS, so a step captured once in a HIP graph follows the schedule.
+
+`ParamEMA(parameters, decay)` is the reference's `torch_ema.ExponentialMovingAverage` (main.py:302 `ema_decay=0.95`; `ema.update()` after
+every optimiser step, nerf/trainer.py:1231-1232): the average of every tracked tensor in ONE launch (sn_ema_update_multi), with torch_ema's
+warm-up `min(decay, (1 + n) / (10 + n))` formed in the kernel from a count that lives on the device -- so `ema.update()` after
+`opt.step()` belongs to the captured step and follows the warm-up under replay.
 """
 from __future__ import annotations
 
@@ -155,6 +160,140 @@ class Adam(torch.optim.Optimizer):
         _lib.check(lib.sn_adam_step_multi(trec, nt, grec, ng, scale, ticket, stream), "sn_adam_step_multi")
         for _, p, _ in work:
             torch.autograd.graph.increment_version(p)                             # as the per-tensor route: the kernel wrote through raw pointers
+
+
+class ParamEMA:
+    """`torch_ema.ExponentialMovingAverage(parameters, decay, use_num_updates=True)` as the reference's trainer uses it, on the device.
+
+    It tracks exactly the tensors it is given, in order (the reference hands it `model.parameters()`); the shadows are clones.  `update()`
+    is torch_ema's statement per element, bit for bit --
+
+        n += 1;  d = min(decay, (1 + n) / (10 + n));  omd = 1.0 - d          # Python doubles (a warm-up: 170 updates at 0.95)
+        tmp = s - p;  tmp.mul_(omd);  s.sub_(tmp)                            # fp32 tensors
+
+    -- as ceil(T / 32) calls of sn_ema_update_multi on torch's current stream, one launch each, next to torch_ema's three launches per
+    tensor.  `n` is ONE device int64 that the kernel reads when it RUNS and that the last call advances: no host value enters the launch and
+    the host reads nothing, so `update()` can be captured in a HIP graph (graph.GraphedStep) after `opt.step()`.  `num_updates` reads the
+    count (a host read; None with `use_num_updates=False`, where the decay is constant).
+
+    `store()`, `copy_to()` and `restore()` -- evaluation and checkpoints under the averaged weights, once per epoch -- are `Tensor.copy_`.
+    After every write to the parameters (`copy_to`, `restore`) each parameter's version counter is bumped, as `Adam` does, and `on_write()`
+    is called once if it was given: pass `model.invalidate_render_plan`, or a model with `render_tables_static = True` goes on rendering
+    from half-precision tables converted before the write.
+
+    `state_dict()` has torch_ema's layout, so that checkpoints interchange with the reference's (nerf/trainer.py:1700-1701, 1806-1808):
+        {"decay": float, "num_updates": int or None, "shadow_params": [Tensor, ...], "collected_params": None or [Tensor, ...]}
+    `load_state_dict()` copies into the existing shadows and the device count.
+
+    Dense contiguous fp32 CUDA tensors only; anything else raises RuntimeError before an element is written (no CPU fallback)."""
+
+    def __init__(self, parameters, decay, use_num_updates=True, on_write=None):
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError("Decay must be between 0 and 1")
+        self.decay = decay
+        self.on_write = on_write
+        self._params = self._checked(list(parameters))
+        self.shadow_params = [p.detach().clone() for p in self._params]
+        self.collected_params = None
+        device = self._params[0].device if self._params else torch.device("cuda")
+        self._count = torch.zeros((), dtype=torch.int64, device=device)
+        self._ticket = torch.zeros(1, dtype=torch.int32, device=device)           # zero before first use; every launch leaves it zero
+        self._use_count = bool(use_num_updates)
+        self._recs = None
+
+    @staticmethod
+    def _checked(params, like=None):
+        """The tensors an entry point may touch, or RuntimeError: nothing has been written when this raises."""
+        if like is not None and len(params) != len(like):
+            raise ValueError("Number of parameters passed as argument is different from number of shadow parameters maintained by this EMA.")
+        for i, p in enumerate(params):
+            if not torch.is_tensor(p) or p.is_sparse or not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("sanerf_hq_amd.optim.ParamEMA handles dense contiguous fp32 CUDA parameters only")
+            if p.device != params[0].device:
+                raise RuntimeError("sanerf_hq_amd.optim.ParamEMA: all parameters must be on one device")
+            if like is not None and (p.shape != like[i].shape or p.device != like[i].device):
+                raise RuntimeError(f"sanerf_hq_amd.optim.ParamEMA: parameter {i} has shape {tuple(p.shape)} on {p.device}, its shadow {tuple(like[i].shape)} on {like[i].device}")
+        return params
+
+    def _parameters(self, parameters):
+        return self._params if parameters is None else self._checked(list(parameters), self.shadow_params)
+
+    @property
+    def num_updates(self):
+        return int(self._count.item()) if self._use_count else None
+
+    @torch.no_grad()
+    def update(self, parameters=None):
+        params = self._parameters(parameters)
+        lib = _lib.lib()
+        T = _lib.EMA_MULTI_MAX_TENSORS
+        if self._recs is None:
+            self._recs = (_lib.EmaTensor * T)()
+        recs = self._recs
+        count = self._count.data_ptr() if self._use_count else None
+        ticket, stream = self._ticket.data_ptr(), _lib.stream()
+        for head in range(0, max(len(params), 1), T):                            # (nothing tracked: the count still advances)
+            part = range(head, min(head + T, len(params)))
+            for r, i in zip(recs, part):
+                r.shadow, r.param, r.n = self.shadow_params[i].data_ptr(), params[i].data_ptr(), params[i].numel()
+            last = part.stop == len(params)                                       # every call reads count + 1; the last one stores it
+            _lib.check(lib.sn_ema_update_multi(recs, len(part), self.decay, count, ticket,
+                                               _lib.EMA_ADVANCE if last and self._use_count else 0, stream), "sn_ema_update_multi")
+
+    def _wrote(self, params):
+        for p in params:
+            torch.autograd.graph.increment_version(p)                             # as Adam: version-keyed caches see the write
+        if self.on_write is not None:
+            self.on_write()
+
+    @torch.no_grad()
+    def copy_to(self, parameters=None):
+        """The averaged values into the parameters."""
+        params = self._parameters(parameters)
+        for s, p in zip(self.shadow_params, params):
+            p.data.copy_(s)
+        self._wrote(params)
+
+    @torch.no_grad()
+    def store(self, parameters=None):
+        """Keep a copy of the parameters for `restore()`."""
+        self.collected_params = [p.detach().clone() for p in self._parameters(parameters)]
+
+    @torch.no_grad()
+    def restore(self, parameters=None):
+        """The parameters as `store()` kept them."""
+        if self.collected_params is None:
+            raise RuntimeError("This ExponentialMovingAverage has no `store()`ed weights to `restore()`")
+        params = self._parameters(parameters)
+        for c, p in zip(self.collected_params, params):
+            p.data.copy_(c)
+        self._wrote(params)
+
+    def state_dict(self):
+        return {"decay": self.decay, "num_updates": self.num_updates, "shadow_params": self.shadow_params, "collected_params": self.collected_params}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        decay, n = float(state_dict["decay"]), state_dict["num_updates"]
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError("Decay must be between 0 and 1")
+        if n is not None and (not isinstance(n, int) or n < 0):
+            raise ValueError("Invalid num_updates")
+        shadows, collected = state_dict["shadow_params"], state_dict["collected_params"]
+        for name, ts in (("shadow_params", shadows), ("collected_params", collected)):
+            if name == "collected_params" and ts is None:
+                continue
+            if not isinstance(ts, (list, tuple)) or not all(torch.is_tensor(t) for t in ts):
+                raise ValueError(f"{name} must all be Tensors")
+            if len(ts) != len(self.shadow_params) or any(t.shape != s.shape for t, s in zip(ts, self.shadow_params)):
+                raise ValueError(f"{name} does not match the tensors this EMA tracks")
+        self.decay = decay
+        self._use_count = n is not None
+        self._count.fill_(n if n is not None else 0)
+        for s, t in zip(self.shadow_params, shadows):
+            s.copy_(t)
+        self.collected_params = None if collected is None else [t.detach().to(device=s.device, dtype=s.dtype, copy=True) for t, s in zip(collected, self.shadow_params)]
 
 
 class DeviceLRScale:
