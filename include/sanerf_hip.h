@@ -847,7 +847,8 @@ int sn_linear_wgrad(const float *x, const float *dy, uint32_t M, uint32_t K, uin
  * Hyper-parameters are doubles like the Python floats torch derives its scalars from.  step counts from 1.  step_device != NULL
  * (capturable form, like torch.optim.Adam(capturable=True)): the count is read from that device float when the kernel RUNS and `step` is
  * ignored, so that the launch can be captured in a HIP graph and replayed.
- * flags: SN_ADAM_ZERO_GRAD -- the gradient is cleared in the same pass (for callers that accumulate in place);
+ * flags: SN_ADAM_ZERO_GRAD -- the gradient is cleared in the same pass (for callers that accumulate in place): every element is zero
+ *        after the call, those of elements that the step leaves alone included (a raw gradient that maximize / weight decay cancel);
  *        SN_ADAM_LAZY -- opt-in touched-elements-only update (NOT the reference's optimiser): an element whose gradient
  *        is exactly zero in this step is skipped altogether (moments do not decay, the parameter does not move) -- the semantics of
  *        torch.optim.SparseAdam with the non-zeros of the dense gradient as the sparse pattern; requires weight_decay = 0. */

@@ -39,6 +39,10 @@ __device__ __forceinline__ bool adam_one(float &p, float g, float &m, float &v, 
     return true;
 }
 
+// SN_ADAM_ZERO_GRAD clears what is STORED, not what was updated: elements that adam_one leaves alone can still hold a non-zero gradient
+// (maximize / weight decay: -+g + wd p cancelled to exactly 0 on zero moments), and an accumulating caller would add the next step's on top.
+__device__ __forceinline__ bool holds_gradient(const float4 &g) { return g.x != 0.0f || g.y != 0.0f || g.z != 0.0f || g.w != 0.0f; }
+
 __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
     SN_POISON_ALL();
     if (a.step_dev) {
@@ -58,17 +62,19 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
         any |= adam_one(p.w, g.w, m.w, v.w, a);
         if (any) {
             reinterpret_cast<float4 *>(a.p)[i] = p; reinterpret_cast<float4 *>(a.m)[i] = m; reinterpret_cast<float4 *>(a.v)[i] = v;
-            if (a.zero_grad) reinterpret_cast<float4 *>(a.g)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
+        if (a.zero_grad && (any || holds_gradient(g))) reinterpret_cast<float4 *>(a.g)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
     // tail (n not a multiple of 4)
     const uint64_t t = (nq << 2) + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < a.n) {
         float p = a.p[t], m = a.m[t], v = a.v[t];
-        if (adam_one(p, a.g[t], m, v, a)) {
+        const float g = a.g[t];
+        const bool any = adam_one(p, g, m, v, a);
+        if (any) {
             a.p[t] = p; a.m[t] = m; a.v[t] = v;
-            if (a.zero_grad) a.g[t] = 0.0f;
         }
+        if (a.zero_grad && (any || g != 0.0f)) a.g[t] = 0.0f;
     }
 }
 
@@ -143,18 +149,20 @@ __global__ __launch_bounds__(256) void k_adam_multi(const AdamMultiArgs a) {
                 any |= adam_one(p.w, g.w, m.w, v.w, s);
                 if (any) {
                     reinterpret_cast<float4 *>(s.p)[i] = p; reinterpret_cast<float4 *>(s.m)[i] = m; reinterpret_cast<float4 *>(s.v)[i] = v;
-                    if (s.zero_grad) reinterpret_cast<float4 *>(s.g)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 }
+                if (s.zero_grad && (any || holds_gradient(g))) reinterpret_cast<float4 *>(s.g)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
         }
         // the tensor's last chunk takes the n % 4 elements behind the last whole quad
         const uint64_t e = (nq << 2) + threadIdx.x;
         if (c + 1 == a.first_chunk[ti + 1] && e < s.n) {
             float p = s.p[e], m = s.m[e], v = s.v[e];
-            if (adam_one(p, s.g[e], m, v, s)) {
+            const float g = s.g[e];
+            const bool any = adam_one(p, g, m, v, s);
+            if (any) {
                 s.p[e] = p; s.m[e] = m; s.v[e] = v;
-                if (s.zero_grad) s.g[e] = 0.0f;
             }
+            if (s.zero_grad && (any || g != 0.0f)) s.g[e] = 0.0f;
         }
     }
     // Advancing the device counts: nobody may store a new count while a workgroup can still read the old one.  Each workgroup takes
