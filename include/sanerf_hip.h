@@ -366,6 +366,44 @@ int sn_rm_feature_distill_loss(const float *feat, uint32_t feat_stride, uint32_t
 int sn_rm_feature_map(const float *feat, uint32_t feat_stride, uint32_t h, uint32_t w, uint32_t C, uint32_t Ho, uint32_t Wo, float *out,
                       sn_stream_t stream);
 
+/* The loss tail of the RGB training step (nerf/trainer.py:364-392; evaluation :586-595), without a host read, in ONE launch: the RGBA
+ * blend of the ground truth, the background term of the prediction, MSELoss(reduction='none').mean(), the entropy of weights_sum, the
+ * extras (proposal and distortion loss) folded into the total, and the gradients with respect to image and weights_sum.
+ * The quantity, per ray and in fp32 (nothing contracted); b_c is the ray's background: bg_value (bg_rows == 0), bg[c] (bg_rows == 1)
+ * or bg[3 ray + c] (bg_rows == N):
+ *   a      = truth[3]                                  (truth_channels == 4)
+ *   gt_c   = truth_c * a + b_c * (1 - a)               (4 channels; trainer.py:366-368)      gt_c = truth_c   (3 channels)
+ *   pred_c = image_c                                   (image_has_bg)
+ *   pred_c = image_c + (1 - weights_sum) * b_c         (otherwise; renderer.py:353 -- the image was rendered over bg = 0)
+ *   d_c    = pred_c - gt_c
+ *   mse    = sum d_c^2 / (3 N)                         squared and summed in double in a fixed order, stored as a float
+ *   c      = min(max(weights_sum, (float)1e-5), (float)(1 - 1e-5));   e = (-c) log2f(c) - (1 - c) log2f(1 - c)
+ *   entropy = sum e / N                                summed in double in a fixed order (not evaluated, and 0, when lambda_entropy == 0)
+ *   total  = ((mse + lambda_entropy * entropy) + coef0 * *extra0) + coef1 * *extra1          in fp32; a NULL extra contributes nothing
+ *   grad_image_c     = (2 d_c) * (1 / float(3 N))
+ *   grad_weights_sum = (image_has_bg ? 0 : -((g_0 b_0 + g_1 b_1) + g_2 b_2)),  g = grad_image,
+ *                    + (lambda_entropy != 0 and (float)1e-5 <= weights_sum <= (float)(1 - 1e-5) ?
+ *                                                          (lambda_entropy / float(N)) * (log2f(1 - c) - log2f(c)) : 0)
+ * The second term is torch's clamp backward: the bounds are inclusive, a NaN is outside.  No gradient goes to truth or bg.  A NaN or Inf
+ * in image, weights_sum, truth or bg reaches the outputs that torch's chain gives it (the clamp keeps a NaN, as torch.clamp does).
+ * image: N rows of >= 3 floats, image_stride floats apart (3 = packed, 5 = the render buffer read in place); truth: N rows of
+ * truth_channels floats, truth_stride apart; weights_sum [N]; bg: packed [3] or [N,3]; extra0, extra1: device scalars or NULL;
+ * pred_rgb, gt_rgb, grad_image: packed [N,3], grad_weights_sum [N]: each may be NULL and is then not written; record: on the device.
+ * 256 lanes a workgroup, a ray a lane, at most SN_RGB_LOSS_MAX_WORKGROUPS workgroups (a lane loops over rays beyond
+ * SN_RGB_LOSS_MAX_WORKGROUPS * 256: the cap is what the last workgroup's two rows of partials take of its LDS, 2 x 512 doubles = 8 KiB).
+ * Two calls on the same inputs give equal bits.  SN_ERR_INVALID: a NULL image, weights_sum, truth, record or workspace; a stride below
+ * the channel count; truth_channels not 3 or 4; bg_rows not 0, 1 or N, or a NULL bg with bg_rows != 0; N == 0; a workspace that is not
+ * 8-byte aligned.  SN_ERR_UNSUPPORTED: N >= 2^30.
+ * The workspace: on the device, 8-byte aligned, SN_RGB_LOSS_WORKSPACE_BYTES, zeroed ONCE by the caller, left zeroed by every call (calls
+ * that share a workspace must be ordered: one stream). */
+typedef struct sn_rgb_loss_record { float total, mse, entropy, reserved; } sn_rgb_loss_record;
+#define SN_RGB_LOSS_MAX_WORKGROUPS 512
+#define SN_RGB_LOSS_WORKSPACE_BYTES 8256   /* a ticket (64 bytes) and 2 x SN_RGB_LOSS_MAX_WORKGROUPS doubles */
+int sn_rm_rgb_loss(const float *image, uint32_t image_stride, const float *weights_sum, const float *truth, uint32_t truth_stride,
+                   uint32_t truth_channels, uint32_t N, float bg_value, const float *bg, uint32_t bg_rows, int image_has_bg,
+                   float lambda_entropy, const float *extra0, float coef0, const float *extra1, float coef1, float *pred_rgb, float *gt_rgb,
+                   sn_rgb_loss_record *record, float *grad_image, float *grad_weights_sum, void *workspace, sn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Propagation of 3D point prompts across views and the decode overlays (prompts.hip): what the reference does between a click and the
  * SAM decoder's prompt, and between the decoder's masks and the picture it returns.  Labels, crucial flags, counts and states are int32

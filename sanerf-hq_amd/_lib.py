@@ -44,6 +44,7 @@ MASK_MAX_CLASSES, MASK_EVAL_WORKSPACE_BYTES = 32, 8192               # sn_rm_mas
 MASK_OUT_MODES = {"none": 0, "heatmap": 1, "composition": 2, "mask": 3}
 SSIM_WORKSPACE_BYTES, SSIM_MAX_STRIDE, SSIM_WINDOW = 8192, 64, 11     # sn_rm_image_ssim_accumulate
 DISTILL_WORKSPACE_FIXED_BYTES = 8256                                  # sn_rm_feature_distill_loss: the zero-at-rest part of its workspace
+RGB_LOSS_WORKSPACE_BYTES, RGB_LOSS_MAX_WORKGROUPS = 8256, 512          # sn_rm_rgb_loss: its zero-at-rest workspace; the cap of its grid
 PROMPT_MAX_POINTS = 1024                                              # sn_rm_point_store_update (capacity) / sn_rm_prompt_overlay (points)
 DRAW_MAX_CELLS = 65536                                                # sn_rm_weighted_draw: cells of one row
 COLLATE_UNIFORM, COLLATE_ERROR_MAP = 0, 1                             # sn_collate_desc.mode
@@ -198,6 +199,7 @@ _SIGNATURES = {
     "sn_rm_feature_distill_workspace_bytes": (C.c_size_t, [_u32, _u32, _u32, _u32, _u32]),
     "sn_rm_feature_distill_loss": (_int, [_vp, _u32, _u32, _u32, _u32, _vp, _u32, _u32, _f32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "sn_rm_feature_map": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "sn_rm_rgb_loss": (_int, [_vp, _u32, _vp, _vp, _u32, _u32, _u32, _f32, _vp, _u32, _int, _f32, _vp, _f32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sn_rm_points_lift": (_int, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp]),
     "sn_rm_point_store_update": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _f32, _vp, _vp]),
     "sn_rm_points_project": (_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _f32, _i32, _i32, C.c_double,

@@ -93,4 +93,52 @@ __device__ __forceinline__ double sum_partials(double *part_sum, uint32_t *part_
     return total;
 }
 
+// Two sums that travel together (k_rgb_loss: the squared error and the entropy): the same five steps on one ticket, each value with
+// the order of additions stated at the top.  part0 / part1: gridDim.x slots each; s_wave: 8 entries of LDS (4 per value); s_flag: one.
+__device__ __forceinline__ bool publish_and_draw2(double sum0, double sum1, uint32_t *ticket, double *part0, double *part1, double *s_wave,
+                                                  uint32_t *s_flag) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    sum0 = wave_sum(sum0);
+    sum1 = wave_sum(sum1);
+    if (lane == 0) {
+        s_wave[wave] = sum0;
+        s_wave[4u + wave] = sum1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        part0[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+        part1[blockIdx.x] = ((s_wave[4] + s_wave[5]) + s_wave[6]) + s_wave[7];
+    }
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) {
+        const uint32_t mine = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        *s_flag = mine == gridDim.x - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    const bool last = *s_flag != 0u;
+    if (last) __threadfence();
+    return last;
+}
+
+// Step 5 and the last sums of publish_and_draw2, in the last workgroup: s_part0 / s_part1: gridDim.x entries of LDS each; the slots go
+// back to zero.  Thread 0's return value (the first sum) and *second are the ones to use.
+__device__ __forceinline__ double sum_partials2(double *part0, double *part1, double *s_part0, double *s_part1, double *second) {
+    for (uint32_t i = threadIdx.x; i < gridDim.x; i += SN_REDUCE_THREADS) {
+        s_part0[i] = __hip_atomic_load(&part0[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_part1[i] = __hip_atomic_load(&part1[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&part0[i], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&part1[i], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    double t0 = 0.0, t1 = 0.0;
+    if (threadIdx.x == 0)
+        for (uint32_t i = 0; i < gridDim.x; ++i) {
+            t0 += s_part0[i];
+            t1 += s_part1[i];
+        }
+    *second = t1;
+    return t0;
+}
+
 }  // namespace sn
