@@ -633,7 +633,13 @@ typedef struct sn_render_tuning {
                                   * the compacting / several-lanes-per-ray kernels, fp32 round-off away from the default */
     int32_t densify;             /* hashed levels 5-6 of the main grid re-laid out per call like dense levels (bit-neutral): 0 automatic (fp16
                                   * tables and >= 64 M last-stage samples), 1 never, 2 whenever the kernel exists for the call */
-    int32_t linear_tile_order;   /* 1: workgroup b renders tile b (no XCD-aware remap; bit-neutral) */
+    int32_t linear_tile_order;   /* image mode: which tile a workgroup renders (bit-neutral; sn_rm_tile_order_info states each order on the host).
+                                  * 1: workgroup b renders tile b, tiles walked in whole pairs of wave-tile rows (no XCD-aware remap);
+                                  * 2: every XCD owns a contiguous range of tile ids, same walk;
+                                  * 3: the same ranges over tiles walked in 128x128-pixel super-tiles (8x8 workgroup blocks), rows of super-tiles in
+                                  *    alternating direction: the 64 workgroups in flight on one XCD cover a compact square.  6 % fewer L2 requests go
+                                  *    on to the fabric than under 2 -- and the last stage is 2.3 % SLOWER (profiles/r08/): opt-in, for measurements;
+                                  * 4: the same with 48x48-pixel super-tiles (3x3 blocks): 2 % faster than 2 at 800x800; 0: the default (4) */
     int32_t prop_sp_max_rays;    /* linear-order batches up to this many rays run the proposal stages with 8 lanes per ray (bit-neutral):
                                   * 0 default (32768), < 0 never */
     int32_t final_sp_max_rays;   /* the same for the last stage (several lanes per ray, per-sample form): 0 default (16384), < 0 never */
@@ -744,10 +750,18 @@ typedef struct sn_render_io {
                                              * MLP input cat([f_sam, f_image, image, depth]) of renderer.py:366 written in place of a concatenation: rows are s floats
                                              * apart, and rgb | depth of ray n are written once more at f_image + n*s + 31 (4 floats).  The caller points f_feat at
                                              * column 0 and f_image at column L*C, s = L*C + 31 + 4 (163 for the reference network).  Needs f_image. */
+    int32_t      pack_valid;                /* (occupies what was padding: the layout of ABI 12 is unchanged.)  SN_PACK_VALID: the caller vouches that `workspace`
+                                             * still holds the packed MLP weights and pair / quad rows that the PREVIOUS sn_rm_render_rays call on it wrote,
+                                             * that no other call used it since, and that nothing those packs are made from has changed: the same cfg (tables,
+                                             * weights, dtypes, tuning), the same route (N, tile_w, the set of optional outputs) and the same stream.  The
+                                             * call then launches no pack kernel and reads the regions as they are -- a frozen field rendered from many
+                                             * views.  Any other value (0 from a zeroed struct): the call packs, as it always did */
     /* workspace */
     void        *workspace;                 /* device, >= sn_rm_render_workspace_bytes() */
     size_t       workspace_bytes;
 } sn_render_io;
+
+#define SN_PACK_VALID 0x50414b31            /* sn_render_io.pack_valid: a value that uninitialised padding of an older caller will not hold */
 
 /* bytes of device workspace sn_rm_render_rays needs for N rays (tile_w as in sn_render_io).  sn_rm_render_rays checks io->workspace_bytes
  * against this figure before its first launch (SN_ERR_WORKSPACE): for every schedule, single-stage ones included, and for both row-band
@@ -767,6 +781,17 @@ int sn_rm_last_launch_info(sn_launch_info *info);
  * nothing is launched, no pointer is dereferenced, io->workspace is not needed.  Same statuses and messages as sn_rm_render_rays.
  * (lds_bytes is the dynamic LDS of the launch itself, the 84 KiB of SN_EXP_FINAL_ONE_WG included.) */
 int sn_rm_render_route_info(const sn_render_cfg *cfg, const sn_render_io *io, sn_launch_info *out);
+
+/* Which part of a W x rows image (one launch: a whole image, a row band, a row chunk) workgroup `workgroup` (blockIdx.x) of the render stages
+ * takes under tuning.wave_tile / tuning.linear_tile_order = `order`, on the host alone: no HIP call, the same arithmetic the kernels run.
+ * workgroups: the launch's grid; tile_id: the linear tile the workgroup renders (its column block in the stages' scratch: tile_id * 256);
+ * x[w], y[w]: pixel origin of the tile_w x tile_h wave tile of wave w, -1 for the padding of the last workgroup.  Over all workgroups the
+ * wave tiles cover every wave tile of the image exactly once, for every order and shape. */
+typedef struct sn_tile_order_info {
+    uint32_t workgroups, tile_id, tile_w, tile_h;
+    int32_t  x[4], y[4];
+} sn_tile_order_info;
+int sn_rm_tile_order_info(uint32_t W, uint32_t rows, int32_t wave_tile, int32_t order, uint32_t workgroup, sn_tile_order_info *out);
 
 /* Feature-head accumulation, nerf/renderer.py:301-302 + 361: out[n, :] = sum_j weights[n,j] * grid(xyzs[n,j])
  * = composite(weights, s_grid(xyzs, bound)) without materialising the [N*T, L*C] per-sample features.

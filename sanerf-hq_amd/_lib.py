@@ -99,6 +99,15 @@ class LaunchInfo(C.Structure):
                 ("gathers_per_wave_sample", C.c_uint32), ("launches", C.c_uint32)]
 
 
+class TileOrderInfo(C.Structure):
+    """sn_tile_order_info: the image part one workgroup of the render stages takes (raymarching.tile_order_info)."""
+    _fields_ = [("workgroups", C.c_uint32), ("tile_id", C.c_uint32), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32),
+                ("x", C.c_int32 * 4), ("y", C.c_int32 * 4)]
+
+
+PACK_VALID = 0x50414B31                                               # sn_render_io.pack_valid: SN_PACK_VALID
+
+
 class RenderCfg(C.Structure):
     _fields_ = [("num_stages", C.c_uint32), ("num_steps", C.c_uint32 * MAX_STAGES),
                 ("prop_grid", GridDesc * MAX_STAGES), ("prop_mlp", MlpDesc * MAX_STAGES),
@@ -117,7 +126,7 @@ class RenderIO(C.Structure):
                 ("image", C.c_void_p), ("depth", C.c_void_p), ("weights_sum", C.c_void_p), ("out_stride", C.c_uint32),
                 ("bins", C.c_void_p * MAX_STAGES), ("weights", C.c_void_p * MAX_STAGES),
                 ("sigmas", C.c_void_p * MAX_STAGES), ("inds", C.c_void_p * MAX_STAGES),
-                ("xyzs_last", C.c_void_p), ("geo_feat_last", C.c_void_p), ("f_image", C.c_void_p), ("f_feat", C.c_void_p), ("head_stride", C.c_uint32),
+                ("xyzs_last", C.c_void_p), ("geo_feat_last", C.c_void_p), ("f_image", C.c_void_p), ("f_feat", C.c_void_p), ("head_stride", C.c_uint32), ("pack_valid", C.c_int32),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
@@ -210,6 +219,7 @@ _SIGNATURES = {
     "sn_rm_debug_occupancy": (_int, [_vp, _vp, _int]),
     "sn_rm_last_launch_info": (_int, [_vp]),
     "sn_rm_render_route_info": (_int, [C.POINTER(RenderCfg), C.POINTER(RenderIO), _vp]),
+    "sn_rm_tile_order_info": (_int, [_u32, _u32, _i32, _i32, _u32, C.POINTER(TileOrderInfo)]),
     "sn_debug_eval": (_int, [_int, _vp, _vp, _u32, _vp, _vp]),
 }
 

@@ -46,6 +46,7 @@ struct RayCommon {
     int contract, last_opaque;
     float bg;
     int xcd_swizzle;
+    uint32_t st_w, st_h;   // wave tiles walked in super-tiles of st_w units x st_h row pairs (wave_tile_of); st_w = 0: in whole row pairs
     uint32_t tlw;      // log2 of the wave tile's width in pixels (3: 8x8; sn_render_tuning.wave_tile)
     float inv_den;     // 1 / (2*bound) when that is a power of two (exact scaling), else 0
 };
@@ -53,15 +54,41 @@ struct RayCommon {
 // Workgroup id -> tile id.  The dispatcher places workgroup b on XCD b % 8 (observed, not contractual: used
 // for speed only).  Remapping so that each XCD owns a contiguous range of tile ids keeps neighbouring image
 // tiles -- which share fine-level table lines -- behind the same private L2.  Bijective for any grid size.
-__device__ __forceinline__ uint32_t tile_id_x(const RayCommon &rc, uint32_t b, uint32_t nwg) {
-    if (!rc.xcd_swizzle) return b;
+__host__ __device__ __forceinline__ uint32_t xcd_tile_id(uint32_t b, uint32_t nwg) {
     const uint32_t xcd = b & 7u, q = nwg >> 3, r = nwg & 7u;
     return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + (b >> 3);
 }
+__device__ __forceinline__ uint32_t tile_id_x(const RayCommon &rc, uint32_t b, uint32_t nwg) { return rc.xcd_swizzle ? xcd_tile_id(b, nwg) : b; }
 __device__ __forceinline__ uint32_t tile_id(const RayCommon &rc) { return tile_id_x(rc, blockIdx.x, gridDim.x); }
 
+// Wave-tile id -> wave tile (wx, wy) of an image of tx8 x ty8 wave tiles.  Wave-tile rows go in pairs; a "unit" is one column of a pair
+// (two wave tiles, one above the other), so that the four consecutive ids of a workgroup are a 2x2 block wherever the image has one.  An
+// odd last wave-tile row comes after all pairs, left to right.
+//   sw = 0: the units of a row pair left to right, pair after pair: 64 consecutive workgroups are a strip the width of the image.
+//   sw > 0: the units in super-tiles sw units wide and up to sh row pairs high (the row pairs are dealt evenly to ceil(P / sh)
+//           super-tile rows).  Super-tile rows alternate direction (odd ones are walked mirrored), a super-tile is row-major inside, edge
+//           super-tiles are narrower: a contiguous range of ids -- what one XCD has in flight, xcd_tile_id -- is a connected region a few
+//           super-tiles long.  Closed form, evaluated once per lane before the march.  Bijective on the units for every shape.
+__host__ __device__ __forceinline__ void wave_tile_of(uint32_t g, uint32_t tx8, uint32_t ty8, uint32_t sw, uint32_t sh, uint32_t &wx, uint32_t &wy) {
+    const uint32_t P = ty8 >> 1, pair = 2u * tx8, paired = P * pair;
+    if (g >= paired) { wx = g - paired; wy = ty8 & ~1u; return; }          // the odd last row
+    if (sw == 0u) { const uint32_t p = g / pair, i = g - p * pair; wx = i >> 1; wy = 2u * p + (i & 1u); return; }
+    const uint32_t u = g >> 1;
+    const uint32_t nsy = (P + sh - 1u) / sh, base = P / nsy, extra = P - base * nsy;    // the first `extra` super-tile rows are base + 1 high
+    const uint32_t big = (base + 1u) * tx8;                                                         // units of such a row
+    uint32_t sy, r0, h, y0;
+    if (u < extra * big) { sy = u / big; r0 = u - sy * big; h = base + 1u; y0 = sy * h; }
+    else { const uint32_t v = u - extra * big, row = base * tx8, s = v / row; r0 = v - s * row; sy = extra + s; h = base; y0 = extra * (base + 1u) + s * base; }
+    const uint32_t full = sw * h, sx = r0 / full, r1 = r0 - sx * full;
+    const uint32_t left = tx8 - sx * sw, w = left < sw ? left : sw;
+    const uint32_t ry = r1 / w, rx = r1 - ry * w;
+    const uint32_t x = sx * sw + rx;
+    wx = (sy & 1u) ? tx8 - 1u - x : x;
+    wy = 2u * (y0 + ry) + (g & 1u);
+}
+
 // lane -> ray.  Tile mode: wave = 8x8 pixels; a workgroup takes four CONSECUTIVE wave tiles of this order: wave-tile rows go in
-// pairs, column-major inside a pair ((0,0) (0,1) (1,0) (1,1) (2,0) ...), so that a workgroup is a 16x16-pixel block wherever the
+// pairs, column-major inside a pair ((0,0) (0,1) (1,0) (1,1) (2,0) ...; wave_tile_of, which also states the super-tile order), so that a workgroup is a 16x16-pixel block wherever the
 // image has one, and an odd last wave-tile row is walked left to right (32x8 pixels per workgroup).  The launch has
 // ceil(wave tiles / 4) workgroups whatever the shape -- a 200-row band of a 1600-wide image (BASELINE configs[3] on 8 GPUs) is 1250
 // workgroups, not the 1300 of whole 16x16 tiles: tools/staircase.py shows the stages' time stepping at multiples of 256 workgroups
@@ -72,12 +99,10 @@ __device__ __forceinline__ bool ray_of_lane(const RayCommon &rc, uint32_t wg, ui
         // wave tile = 2^tlw x 2^(6 - tlw) pixels (8x8 unless sn_render_tuning.wave_tile says otherwise; tx8 / ty8 keep their round-1 names)
         const uint32_t tlw = rc.tlw, tlh = 6u - tlw, tw = 1u << tlw, th = 1u << tlh;
         const uint32_t tx8 = (rc.W + tw - 1u) >> tlw, ty8 = (rc.rows + th - 1u) >> tlh;
-        const uint32_t wave = tid >> 6, lane = tid & 63u;
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63u;      // (the wave tile is the same for all lanes: scalar arithmetic)
         const uint32_t g = wg * 4u + wave;                       // wave tile
-        const uint32_t pair = 2u * tx8, paired = (ty8 >> 1) * pair;
         uint32_t wx, wy;
-        if (g < paired) { const uint32_t p = g / pair, i = g - p * pair; wx = i >> 1; wy = 2u * p + (i & 1u); }
-        else { wx = g - paired; wy = ty8 & ~1u; }                // the odd last row (wx >= tx8: padding of the last workgroup)
+        wave_tile_of(g, tx8, ty8, rc.st_w, rc.st_h, wx, wy);   // (wx >= tx8: padding of the last workgroup)
         const uint32_t py = (wy << tlh) + (lane >> tlw);
         const uint32_t px = (wx << tlw) + (lane & (tw - 1u));
         const bool ok = wx < tx8 && px < rc.W && py < rc.rows;
@@ -3129,6 +3154,20 @@ static uint32_t final_sp_max_rays(const sn_render_cfg *cfg) {
 static bool lt_enabled(const sn_render_cfg *cfg) { return cfg->tuning.per_sample_form == 0; }
 
 static uint32_t tile_log2w(const sn_render_cfg *cfg) { return (cfg && cfg->tuning.wave_tile >= 1 && cfg->tuning.wave_tile <= 5) ? (uint32_t)cfg->tuning.wave_tile : 3u; }
+// tuning.linear_tile_order -> the switches of RayCommon.  1: workgroup b renders tile b, tiles in row pairs (the order of rounds 1-2);
+// 2: each XCD owns a contiguous range of tile ids (xcd_tile_id), tiles in row pairs (rounds 3-7); 3 and 4: the same ranges over super-tiles
+// (wave_tile_of) of 128 x 128 pixels (8 x 8 workgroup blocks: the 64 workgroups an XCD holds are one compact square) and of 48 x 48 pixels
+// (3 x 3 blocks); 0: the default, SN_DEFAULT_TILE_ORDER.  Every order launches blocks_for() workgroups.  Measured at 800x800 [128] with fp16
+// tables (profiles/r08/): 3 sends 6 % fewer L2 requests on to the fabric than 2 and is 2.3 % SLOWER; 4 is 2 % faster than 2.
+#define SN_DEFAULT_TILE_ORDER 4
+struct TileOrder { int xcd; uint32_t st_w, st_h; };
+static TileOrder tile_order_of(int32_t v, uint32_t tlw) {
+    if (v == 0) v = SN_DEFAULT_TILE_ORDER;
+    // a unit is 2^tlw x 2^(7 - tlw) pixels
+    const uint32_t px = v == 3 ? 128u : v == 4 ? 48u : 0u;
+    const uint32_t w = px >> tlw, h = px >> (7u - tlw);
+    return TileOrder{v >= 2 && v <= 4, px ? (w ? w : 1u) : 0u, px ? (h ? h : 1u) : 0u};      // (any other value: 1)
+}
 static uint32_t blocks_for(uint32_t n, uint32_t W, uint32_t tlw) {
     if (W) {                                                      // four wave tiles of 2^tlw x 2^(6 - tlw) pixels each (ray_of_lane)
         const uint32_t rows = (n + W - 1) / W, tw = 1u << tlw, th = 64u >> tlw;
@@ -3813,6 +3852,32 @@ int sn_rm_render_route_info(const sn_render_cfg *cfg, const sn_render_io *io, sn
     return SN_OK;
 }
 
+static_assert(sizeof(sn_render_io) == 312 && offsetof(sn_render_io, pack_valid) == 292 && offsetof(sn_render_io, workspace) == 296,
+              "sn_render_io.pack_valid sits in the padding after head_stride: the struct's layout is ABI 12's");
+
+int sn_rm_tile_order_info(uint32_t W, uint32_t rows, int32_t wave_tile, int32_t order, uint32_t workgroup, sn_tile_order_info *out) {
+    SN_REQUIRE(out, "tile_order_info: out is NULL");
+    SN_REQUIRE(W >= 1u && rows >= 1u && (uint64_t)W * rows <= 0xffffffffull, "tile_order_info: W=%u rows=%u is not an image of 1..2^32-1 rays", W, rows);
+    SN_REQUIRE(wave_tile >= 0 && wave_tile <= 5, "tile_order_info: wave_tile %d outside 0..5", wave_tile);
+    const uint32_t tlw = wave_tile ? (uint32_t)wave_tile : 3u, tlh = 6u - tlw, tw = 1u << tlw, th = 1u << tlh;
+    const uint32_t nwg = blocks_for(W * rows, W, tlw);
+    SN_REQUIRE(workgroup < nwg, "tile_order_info: workgroup %u outside the launch of %u", workgroup, nwg);
+    const TileOrder to = tile_order_of(order, tlw);
+    const uint32_t tx8 = (W + tw - 1u) >> tlw, ty8 = (rows + th - 1u) >> tlh;
+    *out = sn_tile_order_info{};
+    out->workgroups = nwg;
+    out->tile_id = to.xcd ? xcd_tile_id(workgroup, nwg) : workgroup;
+    out->tile_w = tw; out->tile_h = th;
+    for (uint32_t wave = 0; wave < 4u; ++wave) {       // ray_of_lane, lane 0
+        uint32_t wx, wy;
+        wave_tile_of(out->tile_id * 4u + wave, tx8, ty8, to.st_w, to.st_h, wx, wy);
+        const bool ok = wx < tx8 && (wy << tlh) < rows;
+        out->x[wave] = ok ? (int32_t)(wx << tlw) : -1;
+        out->y[wave] = ok ? (int32_t)(wy << tlh) : -1;
+    }
+    return SN_OK;
+}
+
 int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_stream_t stream) {
     SN_REQUIRE(cfg && io, "render_rays: cfg/io is NULL");
     if (io->N == 0) return SN_OK;   // empty batch: nothing to launch, pointers may be NULL
@@ -3839,7 +3904,10 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
     float *scratch = pair_mem + route.ws.pair_floats;
 
     // ---- 3. weights and pair rows, packed on the caller's stream ----
-    if (route.mlp_mode != MLP_VALU && !route.is_any) {
+    // io->pack_valid == SN_PACK_VALID: the caller vouches that this workspace still holds what the previous call with the same cfg packed
+    // (same tables, weights, dtypes, tuning and route): the regions are laid out as always and read as they are, nothing is launched here
+    const bool packed_before = io->pack_valid == SN_PACK_VALID;
+    if (route.mlp_mode != MLP_VALU && !route.is_any && !packed_before) {
         ProfScope ps(st_main, PK_PACK);
         if (route.mlp_mode == MLP_F16X3)
             rc = launch(k_pack_grid_mlp_f16, dim3(PACK16_VECS * 64 / 256), dim3(256), 0, st_main, cfg->grid_mlp.weight[0], cfg->grid_mlp.weight[1],
@@ -3849,7 +3917,7 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
         if (rc) return rc;
         SN_LAUNCH_CHECK("k_pack_grid_mlp");
     }
-    // aligned x-pair rows of every grid's dense levels (PairTab), re-packed on every call: the call stays stateless
+    // aligned x-pair rows of every grid's dense levels (PairTab), re-packed on every call unless the caller vouches for them: the library stays stateless
     PairTab pairs, prop_pairs[SN_MAX_STAGES];
     {
         float *cursor = pair_mem;
@@ -3860,6 +3928,7 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
             pair_layout(gl, Kp, pt.off);
             pt.base = cursor;
             cursor += fl;
+            if (packed_before) return SN_OK;
             uint32_t max_rows = 0;
             for (int l = 0; l < Kp; ++l) { const uint32_t r3 = gl.res[l] * gl.res[l] * gl.res[l]; if (r3 > max_rows) max_rows = r3; }
             const dim3 gp(div_up(max_rows, 256), (uint32_t)Kp);
@@ -3906,13 +3975,16 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
             const float m = frexpf(2.0f * cfg->bound, &e);
             rays.inv_den = (m == 0.5f && e > -100 && e < 100) ? 1.0f / (2.0f * cfg->bound) : 0.0f;
         }
-        {   // tuning.linear_tile_order disables the XCD-aware tile order (A/B switch)
-            rays.xcd_swizzle = cfg->tuning.linear_tile_order == 0;
+        {   // tuning.linear_tile_order: which image tile a workgroup renders (tile_order_of; bit-neutral)
             rays.tlw = tile_log2w(cfg);
+            const TileOrder to = tile_order_of(cfg->tuning.linear_tile_order, rays.tlw);
+            rays.xcd_swizzle = to.xcd; rays.st_w = to.st_w; rays.st_h = to.st_h;
             // compaction: workgroups differ in cost by the number of live rays of their tile; a contiguous tile range per
             // XCD would leave the XCDs that own empty image bands idle (measured on the small-aabb scene: 4.4 instead of
             // 3.0 ms), so tiles go round-robin over the XCDs in dispatch order
             if (route.use_cmp) rays.xcd_swizzle = 0;
+            // the role-split experiment's own tiling states the scratch columns of the row-pair order (rs_ray_of_lane)
+            if (cr.fin.family == FinalRoute::RS) rays.st_w = rays.st_h = 0;
         }
 
         // scratch carve-up

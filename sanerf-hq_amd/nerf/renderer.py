@@ -87,6 +87,8 @@ class NeRFRenderer(nn.Module):
         self._plan_key = None
         self.render_table_dtype = torch.float32             # torch.float16: render from half-precision table copies
         self.render_tables_static = False                   # True: skip the per-call refresh of those copies (frozen field)
+        self.render_keep_packs = False                      # True (frozen field, eval mode): the fused render keeps its packed weights / pair rows
+                                                            # between calls (RenderPlan.keep_packs; invalidate_render_plan() after a write through .data)
         self.unstaged_cam_near_far = False                  # True: honour cam_near_far when staged=False (the reference ignores it)
 
     def forward(self, x, d, **kwargs):
@@ -174,6 +176,7 @@ class NeRFRenderer(nn.Module):
             self._plan_key = key
         elif not getattr(self, "render_tables_static", False):
             self._plan.refresh_tables()        # (the fp16 range guard is re-checked by render_rays before a final-stage launch)
+        self._plan.keep_packs = bool(getattr(self, "render_keep_packs", False)) and not self.training
         ab = rm._host_values(self.aabb_train if self.training else self.aabb_infer)
         for i in range(6):
             self._plan.cfg.aabb[i] = ab[i]

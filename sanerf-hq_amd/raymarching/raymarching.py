@@ -38,7 +38,8 @@ class Tuning:
         per_sample_form    the last stage evaluates the third MLP layer per sample everywhere (bit-identical to the compacting and
                            several-lanes-per-ray kernels; the default "linear tail" differs by fp32 round-off)
         densify            0 automatic, 1 never, 2 whenever the kernel exists (levels 5-6 of the main grid re-laid out per call)
-        linear_tile_order  no XCD-aware workgroup -> tile remap
+        linear_tile_order  workgroup -> image tile (bit-neutral): 1 linear ids, 2 one contiguous id range per XCD over whole row pairs, 3 / 4 the same
+                           ranges over 128x128- / 48x48-pixel super-tiles, 0 the default (4); tile_order_info() states each on the host
         prop_sp_max_rays / final_sp_max_rays   ray-count thresholds of the several-lanes-per-ray kernels (0 default, < 0 never)
         feat_levels        levels per pass of the feature stage (0 default)
         wave_tile          image mode: a wave covers 2^w x 2^(6-w) pixels (0 default = 8x8; 1..5)
@@ -75,6 +76,16 @@ def last_launch_info() -> dict:
     _lib.check(_lib.lib().sn_rm_last_launch_info(C.byref(info)), "last_launch_info")
     return dict(final_kernel=info.final_kernel.decode(), workgroups=int(info.workgroups), lds_bytes=int(info.lds_bytes),
                 dense_levels=int(info.dense_levels), gathers_per_wave_sample=int(info.gathers_per_wave_sample), launches=int(info.launches))
+
+
+def tile_order_info(W: int, rows: int, workgroup: int, wave_tile: int = 0, order: int = 0) -> dict:
+    """The part of a W x rows image that workgroup `workgroup` of the render stages takes under Tuning.wave_tile / linear_tile_order = order
+    (sn_rm_tile_order_info: host arithmetic only, no device needed): workgroups of the launch, tile_id, the wave tile's size and the pixel
+    origins [(x, y)] * 4 of its four wave tiles (None: padding of the last workgroup)."""
+    info = _lib.TileOrderInfo()
+    _lib.check(_lib.lib().sn_rm_tile_order_info(int(W), int(rows), int(wave_tile), int(order), int(workgroup), C.byref(info)), "tile_order_info")
+    return dict(workgroups=int(info.workgroups), tile_id=int(info.tile_id), tile_w=int(info.tile_w), tile_h=int(info.tile_h),
+                tiles=[(int(info.x[w]), int(info.y[w])) if info.x[w] >= 0 else None for w in range(4)])
 
 
 def _flat3(t: torch.Tensor) -> torch.Tensor:
@@ -1511,8 +1522,15 @@ class RenderPlan:
     the module keeps its fp32 parameters); arithmetic stays fp32 either way."""
 
     def __init__(self, model, num_steps: Sequence[int], table_dtype=torch.float32, feat_encoder=None,
-                 early_stop_eps: float = 0.0, compact_live: bool = False, tuning: Optional["Tuning"] = None):
+                 early_stop_eps: float = 0.0, compact_live: bool = False, tuning: Optional["Tuning"] = None, keep_packs: bool = False):
         self.keep: list = []
+        # opt-in for a FROZEN field (inference, evaluation of many views): the packed MLP weights and pair / quad rows that a call leaves in the
+        # plan's workspace are read again by the next call instead of being re-made (sn_render_io.pack_valid), as long as the call is the
+        # same in everything the packs depend on (_pack_key).  A writer that changes tables or weights without moving their version counters
+        # (`.data.copy_()`, raw pointers) must call invalidate_packs() / invalidate_range(), as for the range guard.  May be set at any time.
+        self.keep_packs = bool(keep_packs)
+        self._pack_key = None            # what the packs in self._ws were made from; None: nothing to reuse
+        self.pack_reuses = 0             # calls that ran on kept packs (tests, measurements)
         self.tuning = tuning            # None: the module default `raymarching.tuning` at call time
         cfg = _lib.RenderCfg()
         S = len(num_steps)
@@ -1607,6 +1625,20 @@ class RenderPlan:
         moving their version counters -- `param.data.copy_()` (torch_ema's copy_to / restore around an evaluation, as the reference's trainer
         uses it), raw-pointer writers, a load_state_dict into .data -- which check_range's (data_ptr, _version) key cannot see."""
         self._range_versions = None
+        self._pack_key = None
+
+    def invalidate_packs(self) -> None:
+        """Forget the packs kept in the workspace (keep_packs): the next render makes them again."""
+        self._pack_key = None
+
+    def _pack_key_of(self, io, stream: int):
+        """Everything the pack kernels' output and its place in the workspace depend on: the whole config (table / weight pointers, dtypes,
+        level offsets, tuning: densify; mlp_exact_fp32), the versions of the tensors it points to, and what decides the call's route (N,
+        tile_w, which optional inputs / outputs are present), the workspace and the stream the packs were ordered on."""
+        present = tuple(bool(v) for v in (io.cam_near_far, io.bins0_table, *io.u_table, io.image, *io.bins, *io.weights, *io.sigmas, *io.inds,
+                                          io.xyzs_last, io.geo_feat_last, io.f_image, io.f_feat))
+        shape = (io.N, io.tile_w, io.bins0_ray_stride, tuple(io.u_ray_stride), io.skip_final, io.out_stride, io.head_stride, present)
+        return (bytes(self.cfg), tuple((t.data_ptr(), t._version) for t in self.keep), shape, io.workspace, io.workspace_bytes, stream)
 
     @torch.no_grad()
     def refresh_tables(self) -> None:
@@ -1621,6 +1653,7 @@ class RenderPlan:
         need = int(_lib.lib().sn_rm_render_workspace_bytes(C.byref(self.cfg), N, tile_w))
         if self._ws is None or self._ws.numel() < need or self._ws.device != torch.device(device):
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+            self._pack_key = None
         return self._ws
 
 
@@ -1758,10 +1791,18 @@ def render_rays(plan: RenderPlan, rays_o, rays_d, cam_near_far=None, bg_color: f
     ws = plan.workspace(N, int(tile_w), device)
     if ws.numel() < need:                                          # (a per-call tuning that needs more than the plan's own)
         plan._ws = ws = torch.empty(need, dtype=torch.uint8, device=device)
+        plan._pack_key = None
     eff.write(plan.cfg.tuning)
     io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
     plan.cfg.bg_color = float(bg_color)
-    _lib.check(_lib.lib().sn_rm_render_rays(C.byref(plan.cfg), C.byref(io), _lib.stream()), "render_rays")
+    stream = _lib.stream()
+    key = plan._pack_key_of(io, stream) if plan.keep_packs else None
+    reuse = key is not None and key == plan._pack_key
+    io.pack_valid = _lib.PACK_VALID if reuse else 0
+    plan._pack_key = None                                          # (a call that fails leaves nothing to vouch for)
+    _lib.check(_lib.lib().sn_rm_render_rays(C.byref(plan.cfg), C.byref(io), stream), "render_rays")
+    plan._pack_key = key
+    plan.pack_reuses += int(reuse)
     if "weights_last" in set(want) and not skip_final:
         res["weights_last"] = res[f"weights{S - 1}"]
     return res
