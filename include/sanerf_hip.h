@@ -564,6 +564,25 @@ int sn_rm_sample_positions_ex(const float *rays_o, const float *rays_d, const fl
  * out [N,T].  The reference draws torch.rand_like per stage; one draw for all stages, sliced, is statistically the same. */
 int sn_rm_jitter(const float *uniform, uint32_t N, uint32_t T, int kind, float *out, sn_stream_t stream);
 
+/* The jitter tables of every stage of a schedule in ONE table launch, from a counter-based generator whose state lives on the device
+ * (csrc/jitter.hip): what sn_render_io takes as per-ray bins0_table / u_table[k], without a torch generator or a uniform scratch buffer.
+ *   state      device [4], 16-byte aligned: seed, draw, ticket (zero at rest; unused), reserved
+ *   N          rows written; ray_base: the global index of row 0 (ray_base + N <= 2^32)
+ *   num_steps  host [num_stages], 1..SN_MAX_STAGES stages, 1 <= num_steps[k] and num_steps[k] + 1 <= 2^26 (else SN_ERR_INVALID)
+ *   bins0      device [N, num_steps[0]+1] or NULL (not written)
+ *   u          host array [num_stages] (or NULL: no u table); u[0] is ignored; u[k] device [N, num_steps[k]+1] or NULL (not written)
+ * Element j of row n of stage k, with g = ray_base + n:
+ *   w = philox4x32_10(counter = (g, (k << 24) | (j >> 2), draw_lo, draw_hi), key = (seed_lo, seed_hi))[j & 3]     (Salmon et al., SC'11)
+ *   uniform = float(w >> 8) * 2^-24;   entry = what sn_rm_jitter makes of that uniform (kind 0 for k = 0, kind 1 for k >= 1), bit for bit.
+ * A value depends on (seed, draw, k, g, j) only: not on N, the launch grid or how an image is cut into chunks (give chunk [head, tail) the
+ * ray_base head).  advance != 0: `draw` goes up by one, once per call, in a one-thread launch behind the table launch (the kernel boundary
+ * puts every workgroup's read of the state in front of the write; a ticket on state[2] was measured and dropped: csrc/jitter.hip), so a
+ * replayed graph draws fresh jitter on every replay; with every table NULL the call only advances.  advance == 0: the state is left as
+ * it was (all chunks of one image but the last).  state[2] and state[3] are never written.  N == 0: SN_OK, nothing is launched and the
+ * state stays.  Tables need 4-byte alignment only; a 16-byte aligned table is written with 16-byte stores. */
+int sn_rm_jitter_tables(uint64_t *state, uint32_t N, uint32_t ray_base, uint32_t num_stages, const uint32_t *num_steps, float *bins0,
+                        float *const *u, int32_t advance, sn_stream_t stream);
+
 /* Per-ray sums of the training path in one pass (renderer.py:327-347 with network.py:164-170's colour = cat([geo_feat, SH(d)])):
  *   weights_sum[n] = sum_t w;  depth[n] = sum_t w rays_t;  f_image[n, 0:15] = sum_t w raw[n,t,1:16];  f_image[n, 15:31] = SH4(d/|d|) weights_sum
  * raw [N,T,16] = grid_mlp's output ([sigma_raw | 15 geometry channels], network.py:94,151-153), rays_d [N,3] un-normalised.

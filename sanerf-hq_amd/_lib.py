@@ -163,6 +163,7 @@ _SIGNATURES = {
     "sn_rm_sample_positions": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _vp, _vp, _vp]),
     "sn_rm_sample_positions_ex": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _f32, _vp, _vp, _vp, _vp]),
     "sn_rm_jitter": (_int, [_vp, _u32, _u32, _int, _vp, _vp]),
+    "sn_rm_jitter_tables": (_int, [_vp, _u32, _u32, _u32, C.POINTER(_u32), _vp, C.POINTER(_vp), _i32, _vp]),
     "sn_rm_ray_composite": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "sn_rm_ray_composite_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "sn_rm_proposal_loss_scaled": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp, _vp]),

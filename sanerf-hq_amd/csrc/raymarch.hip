@@ -405,19 +405,7 @@ __global__ __launch_bounds__(256) void k_jitter(const float *__restrict__ r, uin
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (uint64_t)N * T) return;
     const uint32_t i = (uint32_t)(t % T);
-    const float u = r ? r[t] - 0.5f : 0.0f;
-    if (kind == 0) {
-        const float step = T > 1u ? 1.0f / (float)(T - 1u) : 0.0f;
-        float v = linspace_at(0.0f, 1.0f, step, T, i);
-        if (r) { v = v + u / (float)(T - 1u); v = fminf(fmaxf(v, 0.0f), 1.0f); }
-        out[t] = v;
-    } else {
-        const float lo = (float)(0.5 / T), hi = (float)(1 - 0.5 / T);        // Python doubles rounded once, as torch.linspace receives them
-        const float step = T > 1u ? (hi - lo) / (float)(T - 1u) : 0.0f;
-        float v = linspace_at(lo, hi, step, T, i);
-        if (r) v = v + u / (float)T;
-        out[t] = v;
-    }
+    out[t] = jitter_value(r != nullptr, r ? r[t] : 0.0f, T, i, kind);       // (sn_common.h: shared with k_jitter_tables)
 }
 
 // Per-ray head of the training path (renderer.py:327-347 + network.py:164-170) without per-sample colour tensors:

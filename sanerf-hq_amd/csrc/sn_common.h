@@ -277,6 +277,26 @@ __device__ __forceinline__ float linspace_at(float start, float end, float step,
     return end - m;
 }
 
+// One element of a jittered sampling table from its uniform r in [0,1) (k_jitter, raymarch.hip; k_jitter_tables, jitter.hip -- one
+// statement of the arithmetic, so the two entry points agree bit for bit): column i of a row of T values,
+//   kind 0  renderer.py:262-270   clamp(linspace(0, 1, T)[i] + (r - 0.5) / (T - 1), 0, 1)      stage-0 bins, T = num_steps[0] + 1
+//   kind 1  renderer.py:97-102    linspace(0.5/T, 1 - 0.5/T, T)[i] + (r - 0.5) / T              sample_pdf's u
+// jittered = false: the plain linspace value (r is not used).
+__device__ __forceinline__ float jitter_value(bool jittered, float r, uint32_t T, uint32_t i, int kind) {
+    const float u = jittered ? r - 0.5f : 0.0f;
+    if (kind == 0) {
+        const float step = T > 1u ? 1.0f / (float)(T - 1u) : 0.0f;
+        float v = linspace_at(0.0f, 1.0f, step, T, i);
+        if (jittered) { v = v + u / (float)(T - 1u); v = fminf(fmaxf(v, 0.0f), 1.0f); }
+        return v;
+    }
+    const float lo = (float)(0.5 / T), hi = (float)(1 - 0.5 / T);        // Python doubles rounded once, as torch.linspace receives them
+    const float step = T > 1u ? (hi - lo) / (float)(T - 1u) : 0.0f;
+    float v = linspace_at(lo, hi, step, T, i);
+    if (jittered) v = v + u / (float)T;
+    return v;
+}
+
 // ---- fast-path level addressing shared by the fused kernels (render.hip, heads.hip) ---------------
 // Byte offsets (from the level's base) of the 8 corners of one cell.
 // KIND: 0 = dense level, 1 = hashed level (compile-time, from the kernel's dense-prefix length K),

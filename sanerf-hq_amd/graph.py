@@ -25,8 +25,11 @@ cached tensors, every kernel goes to torch's current stream, the binned grid bac
 
 (The per-tensor route, `multi_tensor=False`, takes its rate as a host number: a captured step keeps the rate it was captured with.)
 
-Random numbers drawn inside the step (perturb=True: torch.rand) advance correctly under replay (torch registers the generator with the
-graph).  Anything that changes the step's SHAPE (number of rays, which parameters require gradients, update_proposal on / off) needs its
+Random numbers drawn inside the step advance under replay, by two mechanisms.  torch.rand (the jitter of the training routes, perturb=True
+with a field gradient): torch registers its generator with the graph and moves the Philox offset before every replay.  The jitter tables of
+a perturbed render WITHOUT a field gradient (NeRFRenderer.fused_perturb; raymarching.DeviceJitter, also the training routes' source once the
+caller has set model.jitter): the draw counter is a device word that the captured launches themselves read and advance, so every replay
+draws the next table and `model.jitter.state_dict()` names the draw a replay will use (`.set(draw=...)` between replays chooses it).  Anything that changes the step's SHAPE (number of rays, which parameters require gradients, update_proposal on / off) needs its
 own GraphedStep.  The reference has no counterpart (its trainer launches eagerly, nerf/trainer.py:360-430)."""
 from __future__ import annotations
 

@@ -8,9 +8,13 @@ Two execution paths:
   * fused (default whenever no gradient has to reach the radiance field): one
     `raymarching.render_rays` call = sn_rm_render_rays, which runs proposal resampling, the
     hash-grid field, the MLPs and compositing on the GPU without materialising per-sample
-    tensors; the SAM-feature and mask heads then consume its last-stage samples.
-  * differentiable (RGB training, perturb=True): the stage loop in torch autograd with the
-    HIP encoders / `sample_pdf` / `composite` as building blocks.
+    tensors; the SAM-feature and mask heads then consume its last-stage samples.  perturb=True
+    without a field gradient (the SAM step's ground-truth image, the viewer's supersampling) is
+    the same call fed with per-ray jitter tables from `model.jitter`, a Philox counter on the
+    device (`raymarching.DeviceJitter`; `fused_perturb = False`: the stage loop below).
+  * differentiable (RGB training): the stage loop in torch autograd with the
+    HIP encoders / `sample_pdf` / `composite` as building blocks; its jitter is `torch.rand`
+    unless the caller has set `model.jitter`.
 """
 from __future__ import annotations
 
@@ -120,7 +124,8 @@ class NeRFRenderer(nn.Module):
         for head in range(0, N, step):
             tail = min(head + step, N)
             cnf = cam_near_far if cam_near_far is None or cam_near_far.shape[0] == 1 else cam_near_far[head:tail]
-            part = self.run(rays_o[head:tail], rays_d[head:tail], cam_near_far=cnf, _image_rays=N, **kwargs)   # (one route for every chunk of the image)
+            # (one route for every chunk of the image; a perturbed image is one draw of the jitter tables whatever max_ray_batch is)
+            part = self.run(rays_o[head:tail], rays_d[head:tail], cam_near_far=cnf, _image_rays=N, _ray_base=head, _advance=tail == N, **kwargs)
             for k, v in part.items():
                 if v is None:
                     continue
@@ -187,6 +192,9 @@ class NeRFRenderer(nn.Module):
     standard_field = True
     fused_mask_head = True        # inference: sn_rm_mask_head (one kernel); False = the three-kernel route (A/B, tests)
     fused_proposals = True        # training calls whose proposal networks get no gradient run those stages in the fused kernels
+    fused_perturb = True          # perturbed calls that need no field gradient take the fused render (False: the operator chain, as before)
+    jitter = None                 # Optional[rm.DeviceJitter]: the Philox state of those calls, created on the rays' device at first need.
+                                  # Set by the caller, it also feeds the autograd routes (one jitter.tables() call instead of torch.rand)
     fused_min_rays = 16384        # fields of other sizes than the reference network's: batches below this take the operator chain (see run())
 
     def _fused_shape(self) -> bool:
@@ -253,10 +261,32 @@ class NeRFRenderer(nn.Module):
         # (single-stage fields only: with proposal stages in front, the chain would also leave THEIR fused kernels)
         if kind == "any" and len(self.opt.num_steps) == 1 and int(kwargs.get("_image_rays", rays_o.shape[0])) < self.fused_min_rays:
             kind = None
-        if perturb or self._needs_field_grad(update_proposal) or kind is None:
+        # staged render: chunk [head, tail) of an image draws its jitter rows with ray_base = head and only the last chunk advances the draw
+        ray_base, advance = int(kwargs.get("_ray_base", 0)), bool(kwargs.get("_advance", True))
+        needs_grad = self._needs_field_grad(update_proposal)
+        if perturb and not needs_grad and kind is not None and self.fused_perturb and rays_o.is_cuda:
+            # a perturbed render that differentiates nothing in the field (the SAM step's ground-truth image, trainer.py:513; the viewer's
+            # supersampling, trainer.py:1308: perturb = spp) is the fused render fed with per-ray jitter tables
+            return self._run_fused(rays_o, rays_d, bg_color, cam_near_far, return_feats, return_mask, H, W, tile_w, packed=kwargs.get("packed"),
+                                   jitter=self._device_jitter(rays_o.device), ray_base=ray_base, advance=advance)
+        if perturb or needs_grad or kind is None:
             return self._run_autograd(rays_o, rays_d, bg_color, perturb, cam_near_far, update_proposal,
-                                      return_feats, return_mask, H, W)
+                                      return_feats, return_mask, H, W, ray_base=ray_base, advance=advance)
         return self._run_fused(rays_o, rays_d, bg_color, cam_near_far, return_feats, return_mask, H, W, tile_w, packed=kwargs.get("packed"))
+
+    def _device_jitter(self, device, explicit_only: bool = False):
+        """The DeviceJitter of this model on `device`.  One that the renderer made itself (seeded from torch's default CPU generator) serves
+        the fused perturbed render only: the autograd routes (explicit_only) keep torch.rand unless the caller has set `model.jitter`."""
+        j = self.jitter
+        if j is not None and j is not getattr(self, "_own_jitter", None):      # the caller's
+            if j.device != device:
+                raise RuntimeError(f"model.jitter lives on {j.device}, the rays on {device}")
+            return j
+        if explicit_only:
+            return None
+        if j is None or j.device != device:
+            self.jitter = self._own_jitter = rm.DeviceJitter(device)
+        return self.jitter
 
     # ---------------------------------------------------------------------------------------
     @staticmethod
@@ -312,9 +342,12 @@ class NeRFRenderer(nn.Module):
                                    "(renderer.py:381 feeds 63 features into a 35-input MLP, network.py:128)")
             results["instance_mask_logits"] = rm.composite(weights.detach(), point_masks)
 
-    def _run_fused(self, rays_o, rays_d, bg_color, cam_near_far, return_feats, return_mask, H, W, tile_w, packed=None):
+    def _run_fused(self, rays_o, rays_d, bg_color, cam_near_far, return_feats, return_mask, H, W, tile_w, packed=None,
+                   jitter=None, ray_base=0, advance=True):
         """packed: optional [N, >=5] buffer that receives rgb | depth | weights_sum in place (rm.render_rays; the all-gather payload of dist.py);
-        only with a scalar background (a tensor background is added after the kernel, renderer.py:353)."""
+        only with a scalar background (a tensor background is added after the kernel, renderer.py:353).
+        jitter: a DeviceJitter = perturb: every stage samples at per-ray jittered positions (renderer.py:262-270, 97-102), the tables of rays
+        ray_base .. ray_base + N - 1 written by one launch."""
         opt = self.opt
         need_heads = opt.with_sam or return_mask > 0
         fused_sam = self._sam_fusable()
@@ -332,8 +365,11 @@ class NeRFRenderer(nn.Module):
         # a tensor background is blended after the kernel, so the image columns would be stale: that case keeps the concatenation
         head_in = fused_sam and opt.sam_use_view_direction and not torch.is_tensor(bg_color)
         with torch.no_grad():
+            b0 = u_tabs = None
+            if jitter is not None:
+                b0, u_tabs = jitter.tables(rays_o.reshape(-1, 3).shape[0], list(opt.num_steps), ray_base=ray_base, advance=advance)
             out = rm.render_rays(plan, rays_o, rays_d, cam_near_far=cam_near_far, bg_color=bg, tile_w=tile_w, want=want,
-                                 packed=None if torch.is_tensor(bg_color) else packed, head_input=head_in)
+                                 packed=None if torch.is_tensor(bg_color) else packed, head_input=head_in, bins0_table=b0, u_tables=u_tabs)
             image = out["image"]
             if torch.is_tensor(bg_color):                   # per-ray / rgb background (renderer.py:353)
                 image = image + (1 - out["weights_sum"]).unsqueeze(-1) * bg_color
@@ -355,7 +391,7 @@ class NeRFRenderer(nn.Module):
                 and self._fused_kind() == "main" and hasattr(self, "field_unit") and hasattr(self, "density_unit")
                 and max(opt.num_steps) <= rm.WEIGHTS_BACKWARD_MAX_T and not torch.is_autocast_enabled())
 
-    def _run_autograd_unit(self, rays_o, rays_d, bg_color, perturb, cam_near_far, update_proposal):
+    def _run_autograd_unit(self, rays_o, rays_d, bg_color, perturb, cam_near_far, update_proposal, ray_base=0, advance=True):
         """renderer.py:261-357 for RGB-mode training out of the fused training operators: per stage one geometry kernel that emits the grid
         encoder's unit-cube coordinates, grid_encode, ONE kernel for the stage's perceptron (trunc_exp folded in), one for sigma -> weights;
         then one kernel for weights_sum / depth / f_image (SH once per ray) and one for view_mlp + sigmoid + background.  All jitter comes from
@@ -370,7 +406,8 @@ class NeRFRenderer(nn.Module):
         if cam_near_far is not None:
             nears = torch.maximum(nears, cam_near_far[:, [0]])
             fars = torch.minimum(fars, cam_near_far[:, [1]])
-        rand = torch.rand(N * sum(T + 1 for T in steps), device=device) if perturb else None
+        jit = self._device_jitter(device, explicit_only=True) if perturb else None      # the caller's model.jitter, if set
+        rand = torch.rand(N * sum(T + 1 for T in steps), device=device) if perturb and jit is None else None
         cursor = [0]
 
         def draw(T1):                                       # the next N*T1 uniform numbers (contiguous), or None
@@ -379,6 +416,14 @@ class NeRFRenderer(nn.Module):
             r = rand[cursor[0]:cursor[0] + N * T1]
             cursor[0] += N * T1
             return r
+
+        if jit is not None:                                 # every stage's table from one launch instead of torch.rand + a jitter launch per stage
+            jb0, ju = jit.tables(N, steps, ray_base=ray_base, advance=advance)
+
+        def table(k):                                       # stage k's perturbed bins (k = 0) / sample_pdf u (k >= 1); the plain bins without perturb
+            if jit is not None:
+                return jb0 if k == 0 else ju[k]
+            return rm.jitter(draw(steps[k] + 1), N, steps[k] + 1, 0 if k == 0 else 1, device=device)
 
         prop_needs_grad = update_proposal and torch.is_grad_enabled() and any(
             p.requires_grad for m in (list(self.prop_encoders) + list(self.prop_mlp)) for p in m.parameters())
@@ -389,8 +434,8 @@ class NeRFRenderer(nn.Module):
         if len(steps) > 1 and not prop_needs_grad and not wants_prop_loss and self.fused_proposals:
             # proposal stages that receive no gradient: the fused inference kernels on the same jitter (see _run_autograd)
             if perturb:
-                b0 = rm.jitter(draw(steps[0] + 1), N, steps[0] + 1, 0)
-                u_tabs = {k: rm.jitter(draw(steps[k] + 1), N, steps[k] + 1, 1) for k in range(1, len(steps))}
+                b0 = table(0)
+                u_tabs = {k: table(k) for k in range(1, len(steps))}
             else:
                 b0, u_tabs = torch.linspace(0, 1, steps[0] + 1, device=device), None
             with torch.no_grad():
@@ -406,9 +451,9 @@ class NeRFRenderer(nn.Module):
             if k == first_stage and first_stage > 0:
                 pass
             elif k == 0:
-                bins = rm.jitter(draw(T + 1), N, T + 1, 0, device=device)
+                bins = table(0)
             elif perturb:
-                bins = rm.sample_pdf(bins, weights, T + 1, False, u=rm.jitter(draw(T + 1), N, T + 1, 1))
+                bins = rm.sample_pdf(bins, weights, T + 1, False, u=table(k))
             else:
                 bins = rm.sample_pdf(bins, weights, T + 1, False)
             real_bins, rays_t, x01 = rm.sample_positions(rays_o, rays_d, nears, fars, bins, contract=opt.contract, grid_bound=float(self.bound))
@@ -437,10 +482,10 @@ class NeRFRenderer(nn.Module):
         return results
 
     def _run_autograd(self, rays_o, rays_d, bg_color, perturb, cam_near_far, update_proposal,
-                      return_feats, return_mask, H, W):
+                      return_feats, return_mask, H, W, ray_base=0, advance=True):
         """The stage loop of renderer.py:261-357 in torch autograd over the HIP encoders."""
         if self._unit_path_ok(rays_o, bg_color, return_mask):
-            return self._run_autograd_unit(rays_o, rays_d, bg_color, perturb, cam_near_far, update_proposal)
+            return self._run_autograd_unit(rays_o, rays_d, bg_color, perturb, cam_near_far, update_proposal, ray_base=ray_base, advance=advance)
         opt = self.opt
         rays_o = rays_o.contiguous()
         rays_d = rays_d.contiguous()
@@ -462,11 +507,17 @@ class NeRFRenderer(nn.Module):
             p.requires_grad for m in (list(getattr(self, "prop_encoders", [])) + list(getattr(self, "prop_mlp", []))) for p in m.parameters())
         wants_prop_loss = self.training and not opt.with_mask and not opt.with_sam and opt.lambda_proposal > 0 and update_proposal
         first_stage = 0
+        # the caller's model.jitter, if set: every stage's table from one launch (the same tables as the fused perturbed render draws)
+        jit = self._device_jitter(device, explicit_only=True) if perturb and rays_o.is_cuda else None
+        if jit is not None:
+            jb0, ju = jit.tables(N, list(steps), ray_base=ray_base, advance=advance)
         if (len(steps) > 1 and not prop_needs_grad and not wants_prop_loss and rays_o.is_cuda and self._fused_shape()
                 and self.fused_proposals):
             b0 = torch.linspace(0, 1, steps[0] + 1, device=device)
             u_tabs = None
-            if perturb:
+            if jit is not None:
+                b0, u_tabs = jb0, ju
+            elif perturb:
                 b0 = (b0.unsqueeze(0).expand(N, -1) + (torch.rand(N, steps[0] + 1, device=device) - 0.5) / steps[0]).clamp(0, 1)
                 u_tabs = {}
                 for k in range(1, len(steps)):
@@ -485,11 +536,16 @@ class NeRFRenderer(nn.Module):
                 pass                                            # bins of the last stage came from the fused proposal stages
             elif k == 0:
                 # (the same stage-0 edges as the fused kernels and the fused training route: aten's scalar linspace recipe, sn_rm_jitter)
-                bins = rm.jitter(torch.rand(N, T + 1, device=device) if perturb else None, N, T + 1, 0, device=device) if rays_o.is_cuda else None
+                if jit is not None:
+                    bins = jb0
+                else:
+                    bins = rm.jitter(torch.rand(N, T + 1, device=device) if perturb else None, N, T + 1, 0, device=device) if rays_o.is_cuda else None
                 if bins is None:
                     bins = torch.linspace(0, 1, T + 1, device=device).unsqueeze(0).expand(N, -1)
                     if perturb:
                         bins = (bins + (torch.rand_like(bins) - 0.5) / T).clamp(0, 1)
+            elif jit is not None:
+                bins = rm.sample_pdf(bins, weights, T + 1, False, u=ju[k])
             else:
                 bins = rm.sample_pdf(bins, weights, T + 1, perturb)
             # bins -> distances, mid-points, (contracted) positions: nothing on this chain is differentiated
