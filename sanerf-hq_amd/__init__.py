@@ -4,8 +4,11 @@ Layout
   csrc/            hand-written HIP kernels + the C ABI (libsanerf_hip.so, include/sanerf_hip.h)
   _lib.py          ctypes binding (the only native boundary; no CPU fallback)
   ops.py          grid / SH / frequency encoders (autograd Functions + modules) over the C ABI
+  _buffers.py      zeros_f32 and the workspaces kept between calls (scratch, zeroed), shared by ops.py and raymarching/
   gridencoder/ shencoder/ freqencoder/ raymarching/ encoding.py activation.py
                    the reference's operator modules, same names and call signatures
+  raymarching/     one module per operator family, as csrc/ has one .hip file each: march jitter mask meters distill rgb_loss prompts
+                   collate heads render, and _args (the tensor-argument helpers); the package re-exports them all
   nerf/            NeRFRenderer / NeRFNetwork / get_rays with the reference's contracts
   dist.py          ray-tile sharding of one image over the GPUs of a node + RCCL all-gather
   synth.py         deterministic synthetic inputs for bench / smoke / tests

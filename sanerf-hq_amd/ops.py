@@ -15,19 +15,16 @@ Observable differences from the reference (all neutral for callers):
 """
 from __future__ import annotations
 
+import ctypes as C
+import weakref
 from typing import Tuple
 
-import ctypes as C
-import os
-
 import numpy as np
-import weakref
-
 import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _lib
+from . import _buffers, _lib
 
 # =============================================================================================
 # hash / tiled grid
@@ -65,7 +62,6 @@ def _table_dtype(embeddings: torch.Tensor) -> int:
 # ("sorted", the name of the rounds 1-3 implementation, is accepted as an alias of "binned").
 GRID_BACKWARD_MODE = "auto"
 _BINNED_MIN_CONTRIBUTIONS = 1 << 19
-_binned_ws = {}
 
 
 def _binned_workspace_bytes(B: int, D: int, Cc: int, L: int, max_level: int, offs, dy_dx) -> int:
@@ -78,25 +74,6 @@ def _binned_workspace_bytes(B: int, D: int, Cc: int, L: int, max_level: int, off
     if GRID_BACKWARD_MODE not in ("binned", "sorted") and n < _BINNED_MIN_CONTRIBUTIONS:
         return 0
     return int(_lib.lib().sn_grid_backward_binned_workspace_bytes(B, D, Cc, L, max_level, _lib.host_i32(offs)))   # 0: shape outside the kernels' limits
-
-
-def _binned_workspace(nbytes: int, device) -> torch.Tensor:
-    ws = _binned_ws.get(device)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _binned_ws[device] = ws
-    return ws
-
-
-def _zeros_f32(shape, device) -> torch.Tensor:
-    """zeros_like(embeddings) of grid.py:83 with the fill as a library kernel on the current stream (sn_zero)."""
-    t = torch.empty(shape, device=device, dtype=torch.float32)
-    nbytes = t.numel() * 4
-    if nbytes and nbytes % 16 == 0 and t.data_ptr() % 16 == 0:
-        _lib.check(_lib.lib().sn_zero(t.data_ptr(), nbytes, _lib.stream()), "zero")
-    else:
-        t.zero_()
-    return t
 
 
 class _grid_encode(Function):
@@ -143,12 +120,12 @@ class _grid_encode(Function):
         inputs, table, dy_dx = ctx.saved_tensors
         offs, B, D, Cc, L, S, H, gridtype, interpolation, max_level, align_corners, emb_dtype = ctx.meta
         grad = grad.contiguous().float()
-        grad_embeddings = _zeros_f32(table.shape, table.device)                                # grid.py:83
+        grad_embeddings = _buffers.zeros_f32(table.shape, table.device)                                # grid.py:83
         grad_inputs = torch.zeros_like(inputs) if dy_dx is not None else None
         lib = _lib.lib()
         need = _binned_workspace_bytes(B, D, Cc, L, max_level, offs, dy_dx)
         if need:
-            ws = _binned_workspace(need, table.device)
+            ws = _buffers.scratch("grid_binned", table.device, need)
             _lib.check(lib.sn_grid_encode_backward_binned(
                 _lib.dev(grad, "grad"), _lib.dev(inputs, "inputs"), _lib.host_i32(offs), _lib.dev(grad_embeddings, "grad_embeddings"),
                 B, D, Cc, L, max_level, S, H, gridtype, int(align_corners), interpolation, _lib.LAYOUT_BLC,
@@ -194,12 +171,12 @@ class _grid_encode_cat(Function):
     def backward(ctx, grad):
         inputs, table = ctx.saved_tensors
         offs, B, D, Cc, L, S, H, gridtype, interpolation, align_corners, emb_dtype = ctx.meta
-        grad_embeddings = _zeros_f32(table.shape, table.device)                                # grid.py:83
+        grad_embeddings = _buffers.zeros_f32(table.shape, table.device)                                # grid.py:83
         lib = _lib.lib()
         need = _binned_workspace_bytes(B, D, Cc, L, L, offs, None)
         if need and grad.is_contiguous() and grad.dtype == torch.float32 and grad.data_ptr() % 16 == 0:
             # the binned scatter reads the first L*C columns of the [B, L*C + E] gradient in place (no slice copy)
-            ws = _binned_workspace(need, table.device)
+            ws = _buffers.scratch("grid_binned", table.device, need)
             _lib.check(lib.sn_grid_encode_backward_binned_rows(
                 _lib.dev(grad, "grad"), grad.shape[1], _lib.dev(inputs, "inputs"), _lib.host_i32(offs), _lib.dev(grad_embeddings, "grad_embeddings"),
                 B, D, Cc, L, L, S, H, gridtype, int(align_corners), interpolation, _lib.LAYOUT_BLC,
@@ -207,7 +184,7 @@ class _grid_encode_cat(Function):
             return None, grad_embeddings.to(emb_dtype), None, None, None, None, None, None, None
         g = grad[:, :L * Cc].contiguous().float()
         if need:
-            ws = _binned_workspace(need, table.device)
+            ws = _buffers.scratch("grid_binned", table.device, need)
             _lib.check(lib.sn_grid_encode_backward_binned(
                 _lib.dev(g, "grad"), _lib.dev(inputs, "inputs"), _lib.host_i32(offs), _lib.dev(grad_embeddings, "grad_embeddings"),
                 B, D, Cc, L, L, S, H, gridtype, int(align_corners), interpolation, _lib.LAYOUT_BLC,
@@ -467,9 +444,6 @@ class FreqEncoder(nn.Module):
 LINEAR_WGRAD_MIN_ROWS = 16384      # below this the BLAS call is as fast
 LINEAR_WGRAD_MAX_OUT = 256         # sn_linear_wgrad's output rows (any fan-in)
 
-_wgrad_ws: dict = {}
-_wgrad_ws_wide: dict = {}
-
 # Weight gradients beside the rest of the backward pass (round 4).  A layer's weight gradient is a leaf of the backward graph: nothing
 # downstream of it runs before the optimiser.  sn_linear_wgrad is matrix-core work, the gradient scatter of the grid encoder that follows it
 # in a mask-field / RGB step is memory and LDS work -- on ONE stream they run one after the other.  With WGRAD_SIDE_STREAM the weight
@@ -607,21 +581,12 @@ class _small_linear(Function):
         if ctx.needs_input_grad[1]:
             x2 = x.reshape(-1, x.shape[-1]).contiguous()
             M, K, N = x2.shape[0], x2.shape[1], gy2.shape[1]
-            lib = _lib.lib()
             gw = torch.empty(N, K, device=x2.device, dtype=torch.float32)
-            if M == 0:
-                gw.zero_()
-            elif N > LINEAR_WGRAD_MAX_OUT:
+            if N > LINEAR_WGRAD_MAX_OUT and M > 0:
                 linear_wgrad_general(x2, gy2, gw)
-            else:
-                need = int(lib.sn_linear_wgrad_workspace_bytes(M, K, N))
-                ws = _wgrad_ws.get(x2.device)
-                if ws is None or ws.numel() < need:
-                    ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=x2.device)
-                    _wgrad_ws[x2.device] = ws
+            else:                      # (an empty batch: _wgrad_into zeroes gw)
                 # (inline: on the side stream the ~10 small launches of an RGB step cost more in forks than they hide -- step as a graph 2.24 -> 2.45 ms)
-                _lib.check(lib.sn_linear_wgrad(_lib.dev(x2, "x"), _lib.dev(gy2, "grad_output"), M, K, N, _lib.dev(gw, "grad_weight"),
-                                               ws.data_ptr(), ws.numel(), _lib.stream()), "sn_linear_wgrad")
+                _wgrad_into(x2, gy2, gw, "linear_wgrad")
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = gy2.sum(0)
         return gx, gw, gb
@@ -632,7 +597,6 @@ class _small_linear(Function):
 # ---------------------------------------------------------------------------------------------
 SMALL_MLP_FUSED = True              # False: nn.Linear layers through torch / rocBLAS (A/B, tests)
 SMALL_ACT_NONE, SMALL_ACT_TRUNC_EXP0, SMALL_ACT_SIGMOID_BG = 0, 1, 2
-_small_ws: dict = {}
 
 
 def _small_desc(weights):
@@ -648,8 +612,8 @@ def _small_desc(weights):
     return desc
 
 
-def _wgrad_into(x2, gy2, gw, cache=_small_ws):
-    """gw[N,K] = gy2[M,N]^T x2[M,K] through sn_linear_wgrad (fixed summation order)."""
+def _wgrad_into(x2, gy2, gw, tag="small_mlp_wgrad"):
+    """gw[N,K] = gy2[M,N]^T x2[M,K] through sn_linear_wgrad (fixed summation order); tag: the caller's workspace (_buffers.scratch)."""
     lib = _lib.lib()
     M, K, N = x2.shape[0], x2.shape[1], gy2.shape[1]
     if M == 0:                      # an empty batch: the sum over no rows
@@ -658,9 +622,7 @@ def _wgrad_into(x2, gy2, gw, cache=_small_ws):
     need = int(lib.sn_linear_wgrad_workspace_bytes(M, K, N))
     if need == 0:
         raise RuntimeError("sn_linear_wgrad: " + lib.sn_last_error().decode())
-    ws = cache.get(x2.device)
-    if ws is None or ws.numel() < need:
-        ws = cache[x2.device] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=x2.device)
+    ws = _buffers.scratch(tag, x2.device, need, floor=1 << 20)
     _lib.check(lib.sn_linear_wgrad(_lib.dev(x2, "x"), _lib.dev(gy2, "grad_output"), M, K, N, _lib.dev(gw, "grad_weight"),
                                    ws.data_ptr(), ws.numel(), _lib.stream()), "sn_linear_wgrad")
 
@@ -780,11 +742,9 @@ WIDE_MLP_RANGE_CHECK_EVERY = 64    # with the split-fp16 forward: every this man
                                     # synchronisation; skipped while a HIP graph is being captured) and a RuntimeError names the cause -- an activation or
                                     # input at or beyond 65504 makes the logits, the loss and every gradient non-finite.  0: never check
 _wide_fwd_calls = [0]
-_wide_fwd_ws: dict = {}
 WIDE_MLP_SIGN_BITS = True           # the split-fp16 training forward also writes one sign bit per hidden unit and the backward data path reads those (A/B, tests: False)
 WIDE_MLP_FORWARD_NATIVE = False     # True: the wide training MLP's forward as ONE kernel (sn_mlp_wide_forward_train: fp32 MFMA, fused activations).  Measured slower
                                     # than the BLAS GEMMs + activation kernels (0.555 vs 0.377 ms for the mask head, csrc/mlp_f32.inc), so opt-in
-_wide_bwd_ws: dict = {}
 
 
 class _wide_mlp_train(Function):
@@ -804,22 +764,13 @@ class _wide_mlp_train(Function):
             rows = x.numel() // x.shape[-1]
             x2 = x.reshape(rows, x.shape[-1]).contiguous()
             ws = [w.contiguous() for w in weights]
-            desc = _lib.MlpDesc()
-            desc.num_layers = nl
+            desc = _small_desc(ws)
             desc.activation = 1 if leaky else 0
-            desc.skip_mask = 0
-            desc.dims[0] = x2.shape[1]
-            for i, w in enumerate(ws):
-                desc.weight[i] = w.data_ptr()
-                desc.bias[i] = None
-                desc.dims[i + 1] = w.shape[0]
             lib = _lib.lib()
             need = int(lib.sn_mlp_wide_workspace_bytes(C.byref(desc)))
             if need == 0:
                 raise RuntimeError("wide MLP forward: " + lib.sn_last_error().decode())
-            wsb = _wide_fwd_ws.get(x.device)
-            if wsb is None or wsb.numel() < need:
-                wsb = _wide_fwd_ws[x.device] = torch.empty(need, dtype=torch.uint8, device=x.device)
+            wsb = _buffers.scratch("wide_mlp_forward", x.device, need)
             hs = [torch.empty(*x.shape[:-1], 256, device=x.device, dtype=torch.float32) for _ in range(nl - 1)]
             h = torch.empty(*x.shape[:-1], ws[-1].shape[0], device=x.device, dtype=torch.float32)
             hid = (C.c_void_p * max(nl - 1, 1))(*[t.data_ptr() for t in hs])
@@ -849,15 +800,8 @@ class _wide_mlp_train(Function):
             rows = x.numel() // x.shape[-1]
             x2 = x.reshape(rows, x.shape[-1]).contiguous()
             ws = [w.contiguous() for w in weights]
-            desc = _lib.MlpDesc()
-            desc.num_layers = nl
+            desc = _small_desc(ws)
             desc.activation = 1 if leaky else 0
-            desc.skip_mask = 0
-            desc.dims[0] = x2.shape[1]
-            for i, w in enumerate(ws):
-                desc.weight[i] = w.data_ptr()
-                desc.bias[i] = None
-                desc.dims[i + 1] = w.shape[0]
             hs = [torch.empty(*x.shape[:-1], 256, device=x.device, dtype=torch.float32) for _ in range(nl - 1)]
             h = torch.empty(*x.shape[:-1], ws[-1].shape[0], device=x.device, dtype=torch.float32)
             hid = (C.c_void_p * max(nl - 1, 1))(*[t.data_ptr() for t in hs])
@@ -887,22 +831,12 @@ class _wide_mlp_train(Function):
         gy2 = gy.reshape(-1, gy.shape[-1]).contiguous().float()
         N = gy2.shape[0]
         x2 = x.reshape(N, -1)
-        desc = _lib.MlpDesc()
-        desc.num_layers = nl
+        desc = _small_desc(ws)
         desc.activation = 1 if ctx.leaky else 0
-        desc.skip_mask = 0
-        desc.dims[0] = x2.shape[1]
-        for i, w in enumerate(ws):
-            desc.weight[i] = w.data_ptr()
-            desc.bias[i] = None
-            desc.dims[i + 1] = w.shape[0]
         need = int(lib.sn_mlp_wide_backward_workspace_bytes(C.byref(desc)))
         if need == 0:
             raise RuntimeError("wide MLP backward: " + lib.sn_last_error().decode())
-        ws_buf = _wide_bwd_ws.get(x.device)
-        if ws_buf is None or ws_buf.numel() < need:
-            ws_buf = torch.empty(need, dtype=torch.uint8, device=x.device)
-            _wide_bwd_ws[x.device] = ws_buf
+        ws_buf = _buffers.scratch("wide_mlp_backward", x.device, need)
         gx = torch.empty(N, x2.shape[1], device=x.device, dtype=torch.float32)
         gh = [torch.empty(N, 256, device=x.device, dtype=torch.float32) for _ in range(nl - 1)]
         hid = (C.c_void_p * (nl - 1))(*[h.reshape(N, 256).data_ptr() for h in hs])
@@ -921,10 +855,8 @@ class _wide_mlp_train(Function):
         todo = [i for i in range(nl) if ctx.needs_input_grad[2 + i]]
         gws = {i: torch.empty(outs[i].shape[1], inputs[i].shape[1], device=x.device, dtype=torch.float32) for i in todo}
         wneed = max([int(lib.sn_linear_wgrad_workspace_bytes(N, inputs[i].shape[1], outs[i].shape[1])) for i in todo], default=0)
-        wsb = _wgrad_ws_wide.get(x.device)                       # (its own workspace: these launches may run beside _linear's on the main stream)
-        if todo and (wsb is None or wsb.numel() < wneed):
-            wsb = torch.empty(max(wneed, 1 << 20), dtype=torch.uint8, device=x.device)
-            _wgrad_ws_wide[x.device] = wsb
+        # (its own workspace: these launches may run beside _linear's on the main stream)
+        wsb = _buffers.scratch("wide_mlp_wgrad", x.device, wneed, floor=1 << 20) if todo else None
 
         def launch_wgrads():
             for i in todo:

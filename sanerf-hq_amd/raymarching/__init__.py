@@ -1,9 +1,33 @@
-"""The `raymarching` operator surface over libsanerf_hip.so (see raymarching.py for the table of operators and their places in
-the reference).  Jitter of a perturbed render: `jitter(uniform, ...)` turns caller-supplied uniforms into one stage's table;
-`jitter_tables(state, N, steps, ...)` / `DeviceJitter(device, seed)` write the tables of every stage in one capturable launch from a
-Philox4x32-10 counter on the device -- (seed, draw, stage, ray, column) name a value, `draw` advances once per image."""
-from .raymarching import (  # noqa: F401
-    jitter_tables, DeviceJitter,
-    composite, contract, distort_loss, generate_rays, rays_from_pixels, grid_composite, mask_head, mask_head_fusable, mask_nll, ray_pair_select, ray_pair_rgb_loss, mask_error, error_map_update, mask_output, mask_eval_accumulate, image_sqerr_accumulate, image_ssim_accumulate, ssim_record, ssim_workspace, read_ssim_record, feature_distill_loss, feature_map, rgb_loss, points_lift, point_store, point_store_update, points_project, prompt_overlay, reference_resize_ratio, weighted_draw, collate_gather, COLLATE_OUTPUTS, eval_record, eval_workspace, read_eval_record, mlp_forward, near_far_from_aabb, proposal_loss_stage, render_rays, sample_pdf, sample_positions, weights_from_sigma, jitter, ray_composite, proposal_loss_all, zeros_f32,
-    RenderPlan, Tuning, tuning, last_launch_info, route_info, tile_order_info, PROPOSAL_LOSS_MAX_T, WEIGHTS_BACKWARD_MAX_T, DISTORT_LOSS_MAX_T, FP16_SPLIT_LIMIT, mlp_wide_overflow, _host_values,
-)
+"""`raymarching` operators on MI355X, over libsanerf_hip.so.
+
+The reference's README (README.md:32-34) mentions a `raymarching` extension that is not in its tree; the ray-marching maths lives as torch
+code in nerf/utils.py and nerf/renderer.py.  This package is that operator surface, one module per native file of csrc/:
+
+    march     generate_rays        nerf/utils.py:182-304 (full image branch)
+              near_far_from_aabb   nerf/renderer.py:122-139
+              contract             nerf/renderer.py:60-69
+              sample_pdf           nerf/renderer.py:84-119   (+ the integer searchsorted result)
+              weights_from_sigma   nerf/renderer.py:308-325
+              composite            nerf/renderer.py:333-338, 361, 384  (autograd w.r.t. both operands)
+    heads     grid_composite       nerf/renderer.py:301-302 + 361: composite(weights, s_grid(xyzs)) fused (inference)
+              mlp_forward          nerf/network.py:31-66 (+ LayerNorm :115): the 256-wide head MLPs on the matrix cores (inference)
+    render    render_rays          nerf/renderer.py:221-357 + nerf/network.py:146-186, fused
+    jitter    jitter               nerf/renderer.py:262-270, 97-102: one stage's perturbed bins / u from caller-supplied uniforms
+              jitter_tables        the same tables for every stage in one launch, uniforms from a Philox counter on the device (DeviceJitter)
+    mask, meters, distill, rgb_loss, prompts, collate: the mask field's losses and output stage, the device-side meters, the distillation
+    loss, the RGB loss tail, point prompts, the batch draw; _args: their tensor-argument helpers (workspaces: .._buffers)."""
+from .._buffers import zeros_f32  # noqa: F401
+from .march import (  # noqa: F401
+    composite, contract, distort_loss, generate_rays, rays_from_pixels, near_far_from_aabb, proposal_loss_stage, proposal_loss_all, sample_pdf,
+    sample_positions, weights_from_sigma, ray_composite, PROPOSAL_LOSS_MAX_T, WEIGHTS_BACKWARD_MAX_T, DISTORT_LOSS_MAX_T, _host_values)
+from .jitter import jitter, jitter_tables, DeviceJitter  # noqa: F401
+from .mask import mask_nll, ray_pair_select, ray_pair_rgb_loss, mask_error, error_map_update, mask_output  # noqa: F401
+from .meters import (  # noqa: F401
+    mask_eval_accumulate, image_sqerr_accumulate, image_ssim_accumulate, ssim_record, ssim_workspace, read_ssim_record, eval_record,
+    eval_workspace, read_eval_record)
+from .distill import feature_distill_loss, feature_map  # noqa: F401
+from .rgb_loss import rgb_loss  # noqa: F401
+from .prompts import points_lift, point_store, point_store_update, points_project, prompt_overlay, reference_resize_ratio  # noqa: F401
+from .collate import weighted_draw, collate_gather, COLLATE_OUTPUTS  # noqa: F401
+from .heads import grid_composite, mlp_forward, mlp_wide_overflow, mask_head, mask_head_fusable  # noqa: F401
+from .render import RenderPlan, Tuning, tuning, last_launch_info, route_info, tile_order_info, render_rays, FP16_SPLIT_LIMIT  # noqa: F401

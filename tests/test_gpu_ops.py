@@ -299,7 +299,7 @@ def test_weights_from_sigma_autograd(gpu, orc, T_, opaque):
     go = rng.standard_normal((N, T_)).astype(np.float32)
     s1 = T(sg, gpu).requires_grad_(True)
     w = rm.weights_from_sigma(T(rb, gpu), s1, opaque)
-    if T_ <= rm.raymarching.WEIGHTS_BACKWARD_MAX_T:
+    if T_ <= rm.WEIGHTS_BACKWARD_MAX_T:
         assert np.array_equal(w.detach().cpu().numpy(), orc.weights_from_sigma(rb, sg, opaque))
     else:   # longer rays fall back to torch's chain (fp32 cumsum on the device): close, not bit-equal
         np.testing.assert_allclose(w.detach().cpu().numpy(), orc.weights_from_sigma(rb, sg, opaque), rtol=2e-4, atol=1e-7)
@@ -315,7 +315,7 @@ def test_weights_from_sigma_autograd(gpu, orc, T_, opaque):
     ((alphas * trans).nan_to_num(0) * T(go, gpu).double()).sum().backward()
     ref = s2.grad.float()
     err = float((s1.grad - ref).abs().max()) / (float(ref.abs().max()) + 1e-30)
-    assert err < (2e-5 if T_ <= rm.raymarching.WEIGHTS_BACKWARD_MAX_T else 1e-3), err
+    assert err < (2e-5 if T_ <= rm.WEIGHTS_BACKWARD_MAX_T else 1e-3), err
     if opaque:
         assert float(s1.grad[:, -1].abs().max()) == 0.0, "the opaque last sample is a constant"
 

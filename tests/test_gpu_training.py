@@ -321,7 +321,7 @@ def test_torch_formulated_routes_of_the_training_path(gpu, monkeypatch):
     in registers: T > 256 for the weights backward, > 512 / 2048 for the loss kernels; head MLPs that are not 256 wide).  Each
     such route is pinned here against the kernel route on shapes both can run, values and gradients."""
     from sanerf_hq_amd import raymarching as rm
-    from sanerf_hq_amd.raymarching import raymarching as rmm
+    from sanerf_hq_amd.raymarching import march as rmm
     from sanerf_hq_amd.nerf import renderer as R
     from sanerf_hq_amd.nerf.network import SkipConnMLP
     torch.manual_seed(1)
@@ -336,6 +336,7 @@ def test_torch_formulated_routes_of_the_training_path(gpu, monkeypatch):
         return out.detach().clone(), sig.grad.clone()
 
     w_k, g_k = grads(lambda: rm.weights_from_sigma(bins, sig, True))
+    assert rm.weights_from_sigma.__globals__ is vars(rmm)             # the patch below lands where weights_from_sigma reads the constant
     monkeypatch.setattr(rmm, "WEIGHTS_BACKWARD_MAX_T", 8)
     w_t, g_t = grads(lambda: rm.weights_from_sigma(bins, sig, True))
     monkeypatch.undo()
