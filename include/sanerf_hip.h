@@ -852,6 +852,43 @@ int sn_rm_mask_head(const float *xyzs, const float *extra, const float *weights,
                     float bound, const sn_grid_desc *grid, const sn_mlp_desc *mlp, float *out,
                     void *workspace, size_t workspace_bytes, sn_stream_t stream);
 
+/* Render a segmented object alone (NeRFRenderer.render_object): a per-sample label gate on the densities of the last stage, in two launches.
+ * (The reference names the feature -- main.py:183-185 --render_mesh / --render_mask_instance_id, trainer.py:711-713 outputs['mesh_image'] --
+ * and does not deliver it; this is the project's own definition, and tests/object_ref64.py states it in fp64.)
+ *
+ * Take one ray and the T samples of the LAST stage of the ordinary render (proposal stages are not gated: the sample positions are exactly
+ * those of render(..., return_mask=1)): densities sigma_i, real bin edges b_0 .. b_T with delta_i = b_{i+1} - b_i, mid-points
+ * t_i = (b_{i+1} + b_i) / 2, geometry channels geo_i in R^15, positions x_i.
+ *   1. l_i = mask_mlp(cat[m_grid(x_i), geo_i]) in R^K;  label_i = the lowest index attaining max_k l_i,k
+ *   2. g_i = (label_i in S) xor invert;  S = a set of instance ids, passed as a 32-bit keep mask (K <= 32); invert renders the scene
+ *      without the object
+ *   3. y_i = g_i ? delta_i sigma_i : 0 -- a select, not a product: a gated-out sigma = inf gives 0, not NaN.  With last_sample_opaque
+ *      (opt.background == 'last_sample'): y_{T-1} = g_{T-1} ? +inf : 0
+ *   4. alpha_i = 1 - exp(-y_i);  T_i = exp(-sum_{j<i} y_j);  w'_i = alpha_i T_i, NaN -> 0 as sn_rm_weights_from_sigma
+ *   5. weights_sum = sum w'_i (the object's alpha matte);  depth = sum w'_i t_i;
+ *      f_image = [sum w'_i geo_i | (sum w'_i) SH4(d / |d|)], 31 values, as sn_rm_ray_composite builds it;
+ *      object_image = sigmoid(view_mlp(f_image)) + (1 - sum w') bg   (the per-ray head, not part of these entries)
+ * w'_i can be non-zero where the ordinary weight w_i is exactly 0 (the occluder in front is gated away): nothing is keyed on a weight.
+ *
+ * sn_rm_mask_point_labels: step 1 in the one-kernel mask head (sn_rm_mask_head's matrix-core kernel with a label epilogue: the logits stay
+ * in registers).  xyzs [N,T,3], extra [N,T,E], live [N,T] -> labels [N,T] uint8 and, if logits != NULL (tests, tools; NULL in production),
+ * logits [N,T,K] fp32 from the same registers.  `live` is y = delta sigma: a tile of 128 samples (rays 32 r .. 32 r + 31 x depth indices
+ * 4 p .. 4 p + 3) whose live values are all exactly 0 is skipped; its labels are 255 and its logits 0 (both outputs are filled on the
+ * stream first).  255 appears only where live == 0.  A NaN logit never wins; a row of NaN / -inf logits gets label 0.
+ * Accepts what sn_rm_mask_head's 16-row kernel accepts -- 3 bias-free layers, hidden width 256, K <= 16, E <= 16, <= 16 levels of a 3-D
+ * fp32 level_dim-8 grid of the fast-path shape, T a power of two in 4 .. 128 -- and answers SN_ERR_UNSUPPORTED (with a message) otherwise:
+ * there is no second route.  workspace >= sn_rm_mask_head_workspace_bytes(), 16-byte aligned.  Deterministic: two calls give equal bits.
+ *
+ * sn_rm_object_composite: steps 2-5 in one launch.  labels [N,T] uint8 (a value >= 32, such as 255, is in no S), sigmas [N,T],
+ * real_bins [N,T+1], geo_feat [N,T,15], rays_d [N,3] un-normalised -> weights_sum [N], depth [N], f_image [N,31] and, if != NULL,
+ * weights [N,T] = w'.  16 lanes per ray; every sum runs in sample order (the prefix of y in fp64), so a ray's results do not depend on N. */
+int sn_rm_mask_point_labels(const float *xyzs, const float *extra, const float *live, uint32_t N, uint32_t T, uint32_t E,
+                            float bound, const sn_grid_desc *grid, const sn_mlp_desc *mlp, uint8_t *labels, float *logits,
+                            void *workspace, size_t workspace_bytes, sn_stream_t stream);
+int sn_rm_object_composite(const uint8_t *labels, const float *sigmas, const float *real_bins, const float *geo_feat, const float *rays_d,
+                           uint32_t N, uint32_t T, uint32_t keep_mask, int32_t invert, int32_t last_sample_opaque, float *weights_sum,
+                           float *depth, float *f_image, float *weights, sn_stream_t stream);
+
 /* Training-time forward of a bias-free perceptron with 256-wide hidden layers and no skip connections (nerf/network.py:31-66: F.linear +
  * activation per layer; the per-sample mask head in training, network.py:118-123, trainer.py:401-428) in ONE kernel, true fp32 products
  * and accumulation on the matrix cores (v_mfma_f32_32x32x2_f32; results differ from a BLAS GEMM only by summation order).

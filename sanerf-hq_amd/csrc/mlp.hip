@@ -71,6 +71,7 @@ struct WideArgs {
     // neuron 32 t + (r & 3) + 8 (r >> 2) + 4 half.  Written by the SAVE forward (k_mlp_wide_j), read by the backward (k_mlp_wide<5>) INSTEAD of the
     // [N, 256] fp32 outputs: the branch of a LeakyReLU / ReLU unit is all the backward data path needs of them (1 KiB -> 32 bytes per row and layer)
     uint32_t *bits[SN_MAX_LAYERS];
+    uint8_t *labels;                      // k_mask16<.., MASK16_LABELS> (sn_rm_mask_point_labels): [N] per-sample argmax; `out` is then the optional [N, dout] logits
 };
 
 struct PackArgs {
@@ -1857,6 +1858,58 @@ extern "C" size_t sn_rm_mask_head_workspace_bytes(const sn_mlp_desc *mlp) {
     return a > b ? a : b;
 }
 
+// The k_mask16 launch (mlp16.inc) that sn_rm_mask_head and sn_rm_mask_point_labels share: pack the weights into the workspace, fill the
+// arguments, launch.  labels == NULL: the compositing epilogue into out [N, dout]; else the label epilogue (out = the optional logits).
+static int mask16_launch(const char *what, const float *xyzs, const float *extra, const float *weights, uint32_t N, uint32_t T, uint32_t E, float bound,
+                         const sn_grid_desc *grid, const sn_mlp_desc *mlp, const GridLevels &gl16, float *out, uint8_t *labels,
+                         void *workspace, size_t workspace_bytes, sn_stream_t stream) {
+    const uint32_t nl = mlp->num_layers;
+    int rc;
+    PackArgs p16;
+    size_t n16 = 0;
+    rc = wide16_plan(mlp, grid->L, E, p16.layer, &n16);
+    if (rc) return rc;
+    SN_REQUIRE(workspace_bytes >= n16 * sizeof(uint4), "%s: workspace too small (%zu bytes, need %zu)", what, workspace_bytes, n16 * sizeof(uint4));
+    SN_REQUIRE((uint64_t)N * T < (1ull << 32), "%s: N*T does not fit 32 bits", what);
+    hipStream_t st = (hipStream_t)stream;
+    p16.din = mlp->dims[0]; p16.nl = nl; p16.pack = reinterpret_cast<uint4 *>(workspace); p16.transposed = 0;
+    p16.pair_ks = div_up(grid->L, 4); p16.pair_levels = grid->L;
+    uint32_t max_threads = 0;
+    for (uint32_t l = 0; l < nl; ++l) {
+        p16.w[l] = mlp->weight[l];
+        p16.in_dim[l] = l == 0 ? mlp->dims[0] : (uint32_t)WIDE;
+        const uint32_t th = ((p16.layer[l].uses_h ? W16_HKS : 0) + p16.layer[l].x_ks) * (uint32_t)W16_MT * 64u;
+        if (th > max_threads) max_threads = th;
+    }
+    hipLaunchKernelGGL(k_pack_mlp16, dim3(div_up(max_threads, 256), nl), dim3(256), 0, st, p16);
+    SN_LAUNCH_CHECK("k_pack_mlp16");
+    WideArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.out = out; wa.pack = p16.pack;
+    wa.N = N * T; wa.din = mlp->dims[0]; wa.nl = nl; wa.leaky = mlp->activation; wa.total_chunks = (uint32_t)(n16 / W16_CHUNK_U4);
+    for (uint32_t l = 0; l < nl; ++l) { wa.bias[l] = mlp->bias[l]; wa.layer[l] = p16.layer[l]; }
+    wa.xyz = xyzs; wa.extra = extra; wa.wts = weights; wa.table = reinterpret_cast<const float *>(grid->embeddings);
+    wa.T = T; wa.E = E; wa.bound = bound;
+    int e = 0;
+    const float mant = frexpf(2.0f * bound, &e);
+    wa.inv_den = (mant == 0.5f && e > -100 && e < 100) ? 1.0f / (2.0f * bound) : 0.0f;
+    wa.g = gl16;
+    // weight ring (2 chunks), staged grid operands of the tile ahead [4][hi | lo][512] uint4, the narrow layer's resident weights, biases, level table
+    // ... the appended channels' operand [hi | lo][256] uint4, the level table + the live-tile word
+    const size_t lds16 = (size_t)W16Cfg<8>::NBUF * W16_CHUNK_U4 * sizeof(uint4) + 4u * 2u * 512u * sizeof(uint4) + (size_t)W16_HKS * 128u * sizeof(uint4) +
+                         512u * sizeof(uint4) + 4u * SN_MAX_LEVELS * sizeof(uint32_t) + 16u;
+    if (labels) {          // out: the optional per-sample logits
+        wa.labels = labels;
+        SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mask16<8, MASK16_LABELS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+        hipLaunchKernelGGL((k_mask16<8, MASK16_LABELS>), dim3(div_up(N, 32u)), dim3(512), lds16, st, wa);
+    } else {
+        SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mask16<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+        hipLaunchKernelGGL((k_mask16<8>), dim3(div_up(N, 32u)), dim3(512), lds16, st, wa);
+    }
+    SN_LAUNCH_CHECK("k_mask16");
+    return SN_OK;
+}
+
 extern "C" int sn_rm_mask_head(const float *xyzs, const float *extra, const float *weights, uint32_t N, uint32_t T, uint32_t E,
                                float bound, const sn_grid_desc *grid, const sn_mlp_desc *mlp, float *out,
                                void *workspace, size_t workspace_bytes, sn_stream_t stream) {
@@ -1893,45 +1946,7 @@ extern "C" int sn_rm_mask_head(const float *xyzs, const float *extra, const floa
         for (uint32_t l = 0; l < nl; ++l) any_bias = any_bias || mlp->bias[l] != nullptr;
         const bool fit16 = g_mask_head16 != 0 && nl == 3u && !any_bias && E <= 16u && mlp->dims[nl] <= 16u && mlp->skip_mask == 0u && T >= 4u && E <= 32u && grid->L <= 16u && levels_fast(gl16) &&
                            (uint64_t)grid->offsets[grid->L] * 32u < (1ull << 32);
-        if (fit16) {
-            PackArgs p16;
-            size_t n16 = 0;
-            rc = wide16_plan(mlp, grid->L, E, p16.layer, &n16);
-            if (rc) return rc;
-            SN_REQUIRE(workspace_bytes >= n16 * sizeof(uint4), "mask_head: workspace too small (%zu bytes, need %zu)", workspace_bytes, n16 * sizeof(uint4));
-            SN_REQUIRE((uint64_t)N * T < (1ull << 32), "mask_head: N*T does not fit 32 bits");
-            hipStream_t st = (hipStream_t)stream;
-            p16.din = mlp->dims[0]; p16.nl = nl; p16.pack = reinterpret_cast<uint4 *>(workspace); p16.transposed = 0;
-            p16.pair_ks = div_up(grid->L, 4); p16.pair_levels = grid->L;
-            uint32_t max_threads = 0;
-            for (uint32_t l = 0; l < nl; ++l) {
-                p16.w[l] = mlp->weight[l];
-                p16.in_dim[l] = l == 0 ? mlp->dims[0] : (uint32_t)WIDE;
-                const uint32_t th = ((p16.layer[l].uses_h ? W16_HKS : 0) + p16.layer[l].x_ks) * (uint32_t)W16_MT * 64u;
-                if (th > max_threads) max_threads = th;
-            }
-            hipLaunchKernelGGL(k_pack_mlp16, dim3(div_up(max_threads, 256), nl), dim3(256), 0, st, p16);
-            SN_LAUNCH_CHECK("k_pack_mlp16");
-            WideArgs wa;
-            memset(&wa, 0, sizeof(wa));
-            wa.out = out; wa.pack = p16.pack;
-            wa.N = N * T; wa.din = mlp->dims[0]; wa.nl = nl; wa.leaky = mlp->activation; wa.total_chunks = (uint32_t)(n16 / W16_CHUNK_U4);
-            for (uint32_t l = 0; l < nl; ++l) { wa.bias[l] = mlp->bias[l]; wa.layer[l] = p16.layer[l]; }
-            wa.xyz = xyzs; wa.extra = extra; wa.wts = weights; wa.table = reinterpret_cast<const float *>(grid->embeddings);
-            wa.T = T; wa.E = E; wa.bound = bound;
-            int e = 0;
-            const float mant = frexpf(2.0f * bound, &e);
-            wa.inv_den = (mant == 0.5f && e > -100 && e < 100) ? 1.0f / (2.0f * bound) : 0.0f;
-            wa.g = gl16;
-            // weight ring (2 chunks), staged grid operands of the tile ahead [4][hi | lo][512] uint4, the narrow layer's resident weights, biases, level table
-            // ... the appended channels' operand [hi | lo][256] uint4, the level table + the live-tile word
-            const size_t lds16 = (size_t)W16Cfg<8>::NBUF * W16_CHUNK_U4 * sizeof(uint4) + 4u * 2u * 512u * sizeof(uint4) + (size_t)W16_HKS * 128u * sizeof(uint4) +
-                                 512u * sizeof(uint4) + 4u * SN_MAX_LEVELS * sizeof(uint32_t) + 16u;
-            SN_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mask16<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-            hipLaunchKernelGGL((k_mask16<8>), dim3(div_up(N, 32u)), dim3(512), lds16, st, wa);
-            SN_LAUNCH_CHECK("k_mask16");
-            return SN_OK;
-        }
+        if (fit16) return mask16_launch("mask_head", xyzs, extra, weights, N, T, E, bound, grid, mlp, gl16, out, nullptr, workspace, workspace_bytes, stream);
     }
     if (mlp->dims[nl] > 32u || mlp->skip_mask != 0u) {
         set_error("mask_head: fused path composites at most 32 outputs and no skip layers (got %u outputs, skip mask %u)", mlp->dims[nl], mlp->skip_mask);
@@ -1990,6 +2005,53 @@ extern "C" int sn_rm_mask_head(const float *xyzs, const float *extra, const floa
     }
     SN_LAUNCH_CHECK("k_mlp_wide<3>");
     return SN_OK;
+}
+
+// Per-sample labels of the mask field (include/sanerf_hip.h): k_mask16 with the label epilogue.  Same acceptance as sn_rm_mask_head's fit16
+// branch; nothing else takes this call.
+extern "C" int sn_rm_mask_point_labels(const float *xyzs, const float *extra, const float *live, uint32_t N, uint32_t T, uint32_t E,
+                                       float bound, const sn_grid_desc *grid, const sn_mlp_desc *mlp, uint8_t *labels, float *logits,
+                                       void *workspace, size_t workspace_bytes, sn_stream_t stream) {
+    SN_REQUIRE(grid && mlp, "mask_point_labels: grid/mlp is NULL");
+    if (N == 0) return SN_OK;
+    SN_REQUIRE(xyzs && live && labels && workspace && (extra || E == 0), "mask_point_labels: xyzs/extra/live/labels/workspace must be device pointers");
+    SN_REQUIRE(table_aligned(workspace) && grid->embeddings && table_aligned(grid->embeddings), "mask_point_labels: workspace / table must be 16-byte aligned");
+    SN_REQUIRE(bound > 0.0f, "mask_point_labels: bound must be positive");
+    const uint32_t nl = mlp->num_layers;
+    bool any_bias = false;
+    for (uint32_t l = 0; l < nl && l < (uint32_t)SN_MAX_LAYERS; ++l) any_bias = any_bias || mlp->bias[l] != nullptr;
+    if (!(grid->D == 3 && grid->C == 8 && grid->table_dtype == SN_F32 && grid->L >= 1 && grid->L <= 16u && E <= 16u)) {
+        set_error("mask_point_labels: needs a 3-D fp32 grid with level_dim 8, <= 16 levels and <= 16 appended channels (got D=%u C=%u dtype=%d L=%u E=%u)",
+                  grid->D, grid->C, (int)grid->table_dtype, grid->L, E);
+        return SN_ERR_UNSUPPORTED;
+    }
+    if (!(T >= 4u && T <= 128u && (T & (T - 1u)) == 0u)) {
+        set_error("mask_point_labels: samples per ray must be a power of two, 4 .. 128 (got %u)", T);
+        return SN_ERR_UNSUPPORTED;
+    }
+    if (!(nl == 3u && !any_bias && mlp->skip_mask == 0u && mlp->dims[nl] >= 1u && mlp->dims[nl] <= 16u)) {
+        set_error("mask_point_labels: needs 3 bias-free layers without skip connections and <= 16 outputs (got %u layers, %u outputs, skip mask %u%s)",
+                  nl, nl <= (uint32_t)SN_MAX_LAYERS ? mlp->dims[nl] : 0u, mlp->skip_mask, any_bias ? ", biases" : "");
+        return SN_ERR_UNSUPPORTED;
+    }
+    SN_REQUIRE(mlp->dims[0] == grid->L * 8u + E, "mask_point_labels: mlp input width %u != %u grid features + %u appended", mlp->dims[0], grid->L * 8u, E);
+    SN_REQUIRE((grid->L & 1u) == 0u || E == 0u, "mask_point_labels: an odd number of levels cannot be followed by appended channels");
+    PackArgs pa;
+    size_t u4 = 0;
+    int rc = wide_plan(mlp, pa.layer, &u4);          // (hidden width 256 and the layer shapes: the same validation as sn_rm_mask_head)
+    if (rc) return rc;
+    GridLevels gl16;
+    rc = build_grid_levels(&gl16, grid->offsets, grid->D, grid->C, grid->L, grid->S, grid->H, grid->gridtype, (int)grid->align_corners, grid->interp);
+    if (rc) return rc;
+    if (!(levels_fast(gl16) && (uint64_t)grid->offsets[grid->L] * 32u < (1ull << 32))) {
+        set_error("mask_point_labels: needs a grid of the fast-path shape (hash / tiled levels, linear interpolation, rows within 32-bit byte offsets)");
+        return SN_ERR_UNSUPPORTED;
+    }
+    SN_REQUIRE((uint64_t)N * T < (1ull << 32), "mask_point_labels: N*T does not fit 32 bits");
+    // skipped tiles are not written by the kernel: label 255 (and logit 0) wherever a whole 128-sample tile has live == 0
+    SN_HIP_OK(hipMemsetAsync(labels, 0xFF, (size_t)N * T, (hipStream_t)stream));
+    if (logits) SN_HIP_OK(hipMemsetAsync(logits, 0, (size_t)N * T * mlp->dims[nl] * sizeof(float), (hipStream_t)stream));
+    return mask16_launch("mask_point_labels", xyzs, extra, live, N, T, E, bound, grid, mlp, gl16, logits, labels, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------

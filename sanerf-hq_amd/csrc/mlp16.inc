@@ -137,7 +137,19 @@ __global__ void k_pack_mlp16(PackArgs a) {
 // M0 and the DMA that reads it (dma16 / dma16x4 in mlp.hip: fixed, M0 saved and restored) -- a real hazard, but not this one: the
 // cross-chunk variant rebuilt on the fixed helpers is still irreproducible, with a counted wait and with a full drain at the synchronisation
 // alike, and slower than this order (profiles/r06/mask16_cross_ab_rejected.txt); it is not in the tree.
-template <int WAVES>
+//
+// EPI selects the epilogue behind the narrow layer; everything in front of it is one source path.
+//   MASK16_COMPOSITE  out[ray, m] = sum_t wts[ray, t] * logit[ray, t, m] (sn_rm_mask_head): per-wave sums, then the fixed-order cross-wave sum.
+//   MASK16_LABELS     labels[ray, t] = the lowest index attaining max_m logit[ray, t, m] (sn_rm_mask_point_labels): nothing is summed, `wts` only
+//                     says which tiles are live (the caller passes y = delta * sigma).  Lane 16 q + nloc holds neurons 4 q .. 4 q + 3 of row
+//                     nloc: a max with lowest-index tie-break over the lane's valid neurons, then two cross-lane steps on (value, index) pairs
+//                     (v_permlane16_swap joins rows 0|1 and 2|3, v_permlane32_swap the halves -- no LDS, no counter), and lanes 0..15 store
+//                     one byte per row; a.out != NULL: every lane also stores its valid logits to out[row][m].  A NaN logit never wins a
+//                     comparison; a row whose logits are all NaN or -inf gets label 0.  Plain stores, issued right behind the narrow layer;
+//                     the next sync_and_refill's vmcnt(0) (or the kernel's last one) drains them: no counted wait, nothing else crosses a chunk.
+//                     Skipped tiles are not written: the host fills labels with 0xFF (and logits with 0) on the stream first.
+constexpr int MASK16_COMPOSITE = 0, MASK16_LABELS = 1;
+template <int WAVES, int EPI = MASK16_COMPOSITE>
 __global__ __launch_bounds__(64 * WAVES, 2) void k_mask16(WideArgs a) {
     SN_POISON_ALL();
     typedef W16Cfg<WAVES> Cfg;
@@ -498,14 +510,48 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_mask16(WideArgs a) {
             for (int r = 0; r < 4; ++r) chk = __builtin_fmaf(acc[0][r], 0.0f, chk);
             if (ok && chk != chk) g_wide_overflow = 1;
         }
-        // renderer.py:384: out[ray, m] = sum_t w[ray, t] * logits[ray, t, m]: this wave's t of this tile
+        if constexpr (EPI == MASK16_LABELS) {
+            const uint32_t K = a.layer[a.nl - 1u].out, nn = row0 + 4u * tile;     // this lane's row of the tile: sample (ray, 4 tile + phase)
+            float best = -__builtin_inff();
+            uint32_t bi = 4u * q;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const float t = wt * acc[0][r]; out_acc[r] = out_acc[r] + t; }
+            for (int r = 0; r < 4; ++r) {
+                const uint32_t m = 4u * q + (uint32_t)r;
+                const float v = acc[0][r];
+                if (m < K && v > best) { best = v; bi = m; }
+                if (a.out && ok && m < K) a.out[(size_t)nn * K + m] = v;
+            }
+            auto join = [&](float v0, uint32_t i0, float v1, uint32_t i1) {     // (value, index) pairs: the larger value, the lower index on a tie
+                const bool second = v1 > v0 || (v1 == v0 && i1 < i0);
+                best = second ? v1 : v0; bi = second ? i1 : i0;
+            };
+            {
+                const auto pv = __builtin_amdgcn_permlane16_swap(__float_as_uint(best), __float_as_uint(best), false, false);   // [r0 r0 r2 r2], [r1 r1 r3 r3]
+                const auto pi = __builtin_amdgcn_permlane16_swap(bi, bi, false, false);
+                join(__uint_as_float(pv[0]), pi[0], __uint_as_float(pv[1]), pi[1]);
+            }
+            {
+                const auto pv = __builtin_amdgcn_permlane32_swap(__float_as_uint(best), __float_as_uint(best), false, false);   // [lo | lo], [hi | hi]
+                const auto pi = __builtin_amdgcn_permlane32_swap(bi, bi, false, false);
+                join(__uint_as_float(pv[0]), pi[0], __uint_as_float(pv[1]), pi[1]);
+            }
+            if (ok && q == 0u) a.labels[nn] = (uint8_t)bi;
+            (void)wt; (void)out_acc;
+        } else {
+            // renderer.py:384: out[ray, m] = sum_t w[ray, t] * logits[ray, t, m]: this wave's t of this tile
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { const float t = wt * acc[0][r]; out_acc[r] = out_acc[r] + t; }
+        }
         wt = wt_next; tile = nt;
         wide_trace(142u);
     }                                      // tiles
-    const WideLayer LL = a.layer[a.nl - 1u];
     wide_trace(160u);
+    if constexpr (EPI == MASK16_LABELS) {
+        asm volatile("s_waitcnt vmcnt(0)" : : : "memory");         // (skipped tiles leave a prefetched weight chunk in flight: it lands before the LDS is given back)
+        __syncthreads();
+        return;
+    }
+    const WideLayer LL = a.layer[a.nl - 1u];
     // waves GROUPS d + group, d = 0..3, hold the depth phases of the same 16 rays: fixed-order sum through LDS (the weight ring is dead)
     float *part = reinterpret_cast<float *>(lds_w);                  // [WAVES][16 rays][16 neurons]
     asm volatile("s_waitcnt vmcnt(0)" : : : "memory");             // (skipped tiles leave a prefetched weight chunk in flight)

@@ -381,6 +381,100 @@ class NeRFRenderer(nn.Module):
         return results
 
     # ---------------------------------------------------------------------------------------
+    fused_point_labels = True     # render_object: per-sample labels from sn_rm_mask_point_labels (False: the operator chain, A/B and tests)
+
+    def render_object(self, rays_o, rays_d, instance_ids, invert=False, staged=False, cam_near_far=None, bg_color=None, H=None, W=None):
+        """Render the object that the mask field assigns to `instance_ids` alone -- or, with invert=True, the scene without it.
+        (The reference names this, main.py:183-185 --render_mesh / --render_mask_instance_id and trainer.py:711-713 outputs['mesh_image'],
+        and leaves it commented out; the definition is this project's: include/sanerf_hip.h, tests/object_ref64.py.)
+
+        Only the LAST stage is gated: the samples are exactly those of render(..., return_mask=1).  Each gets the label argmax_k
+        mask_mlp(cat[m_grid(x), geo_feat]) (lowest index on a tie); the samples whose label is in `instance_ids` (xor invert) keep their
+        density, the others get none, and the ray is integrated again.  Returns image / depth / weights_sum of the full scene (free, from the
+        same call) and object_image / object_depth / object_weights_sum; mesh_image is object_image.  No-grad only; nothing is read back
+        to the host, so a warmed-up call can be captured as a HIP graph.  staged=True: chunks of opt.max_ray_batch, same bits."""
+        if self._needs_field_grad(True) or (torch.is_grad_enabled() and any(p.requires_grad for m in (self.m_grid, self.mask_mlp) for p in m.parameters())):
+            raise RuntimeError("render_object is an inference render: call it under torch.no_grad() (or on a frozen field)")
+        keep = rm.keep_mask_of(instance_ids)
+        rays_o, rays_d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
+        N = rays_o.shape[0]
+        bg_color = 1 if bg_color is None else bg_color
+        per_ray_bg = torch.is_tensor(bg_color) and bg_color.dim() == 2 and bg_color.shape[0] == N and N > 1
+        with torch.no_grad():
+            if not staged:
+                cnf = cam_near_far if getattr(self, "unstaged_cam_near_far", False) else None     # (as render(): the reference drops it here)
+                res = self._run_object(rays_o, rays_d, keep, bool(invert), cnf, bg_color)
+            else:
+                res: Dict[str, torch.Tensor] = {}
+                step = self.opt.max_ray_batch
+                for head in range(0, N, step):
+                    tail = min(head + step, N)
+                    cnf = cam_near_far if cam_near_far is None or cam_near_far.shape[0] == 1 else cam_near_far[head:tail]
+                    part = self._run_object(rays_o[head:tail], rays_d[head:tail], keep, bool(invert), cnf,
+                                            bg_color[head:tail] if per_ray_bg else bg_color)
+                    for k, v in part.items():
+                        if k not in res:
+                            res[k] = torch.empty(N, *v.shape[1:], device=v.device, dtype=v.dtype)
+                        res[k][head:tail] = v
+        res["mesh_image"] = res["object_image"]             # the key the reference's test_step reads (trainer.py:711-713)
+        return res
+
+    def _point_labels(self, live, xyzs, geo_feat, want_logits=False):
+        """label = argmax_k mask_mlp(cat[m_grid(x), geo_feat]) per sample, uint8 [N,T]: one kernel where sn_rm_mask_point_labels takes the head
+        (255 on the tiles it skips, where live == 0 throughout), else m_grid.forward_cat -> the matrix-core MLP -> argmax."""
+        if self.opt.mask_mlp_type != "default":
+            raise RuntimeError("render_object needs mask_mlp_type='default' (see _heads)")
+        mlp = self.mask_mlp[0]
+        if (self.fused_point_labels and live.is_cuda and len(self.mask_mlp) == 1
+                and rm.mask_point_labels_fusable(self.m_grid, mlp, live.shape[1], geo_feat.shape[-1])):
+            return rm.mask_point_labels(live, xyzs, geo_feat, self.m_grid, mlp, self.bound, want_logits=want_logits)
+        logits = self._head_mlp(self.mask_mlp, self.m_grid.forward_cat(xyzs, geo_feat, bound=self.bound))
+        if logits.shape[-1] > 32:
+            raise RuntimeError(f"render_object: at most 32 instances (the mask field has {logits.shape[-1]})")
+        labels = torch.argmax(logits, dim=-1).to(torch.uint8)
+        return (labels, logits) if want_logits else labels
+
+    def _object_samples(self, rays_o, rays_d, cam_near_far, bg_color):
+        """The full-scene render and the last stage's samples: (results, sigmas [N,T], real_bins [N,T+1], xyzs [N,T,3], geo_feat [N,T,15])."""
+        opt = self.opt
+        rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()
+        if self._fused_kind() is not None and rays_o.is_cuda:
+            bg = float(bg_color) if not torch.is_tensor(bg_color) else 0.0
+            out = rm.render_rays(self._get_plan(), rays_o, rays_d, cam_near_far=cam_near_far, bg_color=bg,
+                                 want=["xyzs_last", "geo_feat_last", "sigmas_last", "bins_last"])
+            last = len(opt.num_steps) - 1
+            image = out["image"]
+            if torch.is_tensor(bg_color):                   # per-ray / rgb background (renderer.py:353)
+                image = image + (1 - out["weights_sum"]).unsqueeze(-1) * bg_color
+            results = {"image": image, "depth": out["depth"], "weights_sum": out["weights_sum"]}
+            # real bin edges from the existing sample_positions arithmetic (the fused render's own real_bin)
+            nears, fars = rm.near_far_from_aabb(rays_o, rays_d, self.aabb_train if self.training else self.aabb_infer, self.min_near)
+            if cam_near_far is not None:
+                nears = torch.maximum(nears, cam_near_far[:, [0]])
+                fars = torch.minimum(fars, cam_near_far[:, [1]])
+            real_bins = rm.sample_positions(rays_o, rays_d, nears, fars, out[f"bins{last}"], contract=opt.contract)[0]
+            return results, out[f"sigmas{last}"], real_bins, out["xyzs_last"], out["geo_feat_last"]
+        samples: dict = {}
+        results = self._run_autograd(rays_o, rays_d, bg_color, False, cam_near_far, False, 0, 0, None, None, samples=samples)
+        return ({k: results[k] for k in ("image", "depth", "weights_sum")}, samples["sigmas"], samples["real_bins"], samples["xyzs"],
+                samples["geo_feat"])
+
+    def _run_object(self, rays_o, rays_d, keep_mask, invert, cam_near_far, bg_color):
+        last_opaque = self.opt.background == "last_sample"
+        results, sigmas, real_bins, xyzs, geo_feat = self._object_samples(rays_o, rays_d, cam_near_far, bg_color)
+        # which samples can matter at all: y = delta * sigma != 0 (not "weight != 0": a sample behind a gated-away occluder has weight 0)
+        live = (real_bins[:, 1:] - real_bins[:, :-1]) * sigmas
+        if last_opaque:
+            live[:, -1] = 1.0                               # the last sample is opaque whenever it is kept, whatever its density
+        labels = self._point_labels(live, xyzs, geo_feat)
+        wsum, depth, f_image = rm.object_composite(labels, sigmas, real_bins, geo_feat, rays_d, keep_mask, invert, last_opaque)
+        image = self.view_mlp.forward_sigmoid_bg(f_image, wsum, float(bg_color) if not torch.is_tensor(bg_color) else 0.0)
+        if torch.is_tensor(bg_color):
+            image = image + (1 - wsum).unsqueeze(-1) * bg_color
+        results.update(object_image=image, object_depth=depth, object_weights_sum=wsum)
+        return results
+
+    # ---------------------------------------------------------------------------------------
     fused_training_ops = True     # RGB-mode training: unit-cube positions, fused small MLPs, one-kernel per-ray head (False: the operator chain)
 
     def _unit_path_ok(self, rays_o, bg_color, return_mask) -> bool:
@@ -482,9 +576,10 @@ class NeRFRenderer(nn.Module):
         return results
 
     def _run_autograd(self, rays_o, rays_d, bg_color, perturb, cam_near_far, update_proposal,
-                      return_feats, return_mask, H, W, ray_base=0, advance=True):
-        """The stage loop of renderer.py:261-357 in torch autograd over the HIP encoders."""
-        if self._unit_path_ok(rays_o, bg_color, return_mask):
+                      return_feats, return_mask, H, W, ray_base=0, advance=True, samples=None):
+        """The stage loop of renderer.py:261-357 in torch autograd over the HIP encoders.
+        samples: a dict that receives the last stage's sigmas, real_bins, xyzs and geo_feat (render_object on a field the fused render does not take)."""
+        if samples is None and self._unit_path_ok(rays_o, bg_color, return_mask):
             return self._run_autograd_unit(rays_o, rays_d, bg_color, perturb, cam_near_far, update_proposal, ray_base=ray_base, advance=advance)
         opt = self.opt
         rays_o = rays_o.contiguous()
@@ -581,6 +676,9 @@ class NeRFRenderer(nn.Module):
         results["weights_sum"] = weights_sum
         results["depth"] = depth
         results["image"] = image
+        if samples is not None:
+            samples.update(sigmas=sigmas, real_bins=real_bins, xyzs=xyzs, geo_feat=geo_feat)
+            return results
         if opt.with_sam or return_mask > 0:
             self._heads(results, weights, xyzs, geo_feat, f_image, image, depth, return_feats, return_mask, H, W)
         return results

@@ -11,6 +11,8 @@ code in nerf/utils.py and nerf/renderer.py.  This package is that operator surfa
               composite            nerf/renderer.py:333-338, 361, 384  (autograd w.r.t. both operands)
     heads     grid_composite       nerf/renderer.py:301-302 + 361: composite(weights, s_grid(xyzs)) fused (inference)
               mlp_forward          nerf/network.py:31-66 (+ LayerNorm :115): the 256-wide head MLPs on the matrix cores (inference)
+              mask_point_labels    per-sample argmax of the mask field in the one-kernel mask head (nothing per-sample but the labels written)
+    object    object_composite     re-integration of a ray over the samples whose label is kept: the object alone, or the scene without it
     render    render_rays          nerf/renderer.py:221-357 + nerf/network.py:146-186, fused
     jitter    jitter               nerf/renderer.py:262-270, 97-102: one stage's perturbed bins / u from caller-supplied uniforms
               jitter_tables        the same tables for every stage in one launch, uniforms from a Philox counter on the device (DeviceJitter)
@@ -29,5 +31,7 @@ from .distill import feature_distill_loss, feature_map  # noqa: F401
 from .rgb_loss import rgb_loss  # noqa: F401
 from .prompts import points_lift, point_store, point_store_update, points_project, prompt_overlay, reference_resize_ratio  # noqa: F401
 from .collate import weighted_draw, collate_gather, COLLATE_OUTPUTS  # noqa: F401
-from .heads import grid_composite, mlp_forward, mlp_wide_overflow, mask_head, mask_head_fusable  # noqa: F401
+from .heads import (  # noqa: F401
+    grid_composite, mlp_forward, mlp_wide_overflow, mask_head, mask_head_fusable, mask_point_labels, mask_point_labels_fusable)
+from .object import object_composite, keep_mask_of, LABEL_SKIPPED  # noqa: F401
 from .render import RenderPlan, Tuning, tuning, last_launch_info, route_info, tile_order_info, render_rays, FP16_SPLIT_LIMIT  # noqa: F401

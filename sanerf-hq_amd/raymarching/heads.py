@@ -2,6 +2,8 @@
 
     grid_composite       nerf/renderer.py:301-302 + 361: composite(weights, s_grid(xyzs)) fused (inference)
     mlp_forward          nerf/network.py:31-66 (+ LayerNorm :115): the 256-wide head MLPs on the matrix cores (inference)
+    mask_head            nerf/renderer.py:304-305, 376-385: grid gather -> mask MLP -> compositing in one kernel (inference)
+    mask_point_labels    the same kernel with a label epilogue: per-sample argmax of the mask field (render_object; raymarching/object.py)
 """
 from __future__ import annotations
 
@@ -109,3 +111,42 @@ def mask_head(weights: torch.Tensor, xyzs: torch.Tensor, extra: torch.Tensor, en
                                  C.byref(gdesc), C.byref(mdesc), _lib.dev(out, "out"), ws.data_ptr(), ws.numel(), _lib.stream()),
                "sn_rm_mask_head")
     return out
+
+
+def mask_point_labels_fusable(encoder, mlp, T: int, E: int) -> bool:
+    """Can sn_rm_mask_point_labels take this head?  What sn_rm_mask_head's 16-row kernel takes: a 3-D fp32 grid with level_dim 8 and at most
+    16 levels of the fast-path shape (hash / tiled levels, linear interpolation, no align_corners), a 256-wide perceptron of three bias-free
+    layers without skip connections and at most 16 outputs, at most 16 appended channels, a power-of-two number of samples per ray in 4..128."""
+    net = list(getattr(mlp, "net", []))
+    return (mask_head_fusable(encoder, mlp, T, E) and T >= 4 and len(net) == 3 and all(l.bias is None for l in net) and mlp.dim_out <= 16
+            and encoder.num_levels <= 16 and getattr(encoder, "gridtype_id", 0) == 0 and not getattr(encoder, "align_corners", False)
+            and getattr(encoder, "interp_id", 0) == 0)
+
+
+def mask_point_labels(live: torch.Tensor, xyzs: torch.Tensor, extra: torch.Tensor, encoder, mlp, bound: float, want_logits: bool = False):
+    """Per-sample labels of the mask field in ONE kernel: labels[n,t] = the lowest index attaining max_k mlp(cat([encoder(xyzs[n,t], bound),
+    extra[n,t]]))_k, uint8 [N,T].  live [N,T] (y = delta * sigma): a 128-sample tile (32 consecutive rays x 4 consecutive depth indices) whose
+    live values are all exactly 0 is skipped and gets label 255.  want_logits: returns (labels, logits [N,T,K] fp32, 0 on skipped tiles) --
+    for tests and tools.  Inference only; raises where mask_point_labels_fusable() is False (there is no second route)."""
+    N, T = live.shape
+    E = int(extra.shape[-1]) if extra is not None else 0
+    assert xyzs.shape == (N, T, 3)
+    L = _lib.lib()
+    lv, x = _f32(live), _f32(xyzs)
+    e = _f32(extra) if E else None
+    gdesc = _lib.GridDesc()
+    _fill_grid(gdesc, encoder, encoder.embeddings.detach().contiguous())
+    mdesc = _lib.MlpDesc()
+    keep: list = []
+    _fill_mlp(mdesc, list(mlp.net), mlp.dim_in, keep)
+    mdesc.activation = 1 if getattr(mlp, "skip_layers", None) is not None else 0      # SkipConnMLP: LeakyReLU(0.01)
+    need = int(L.sn_rm_mask_head_workspace_bytes(C.byref(mdesc)))
+    if need == 0:
+        raise RuntimeError("mask_point_labels: " + L.sn_last_error().decode())
+    ws = torch.empty(need, dtype=torch.uint8, device=lv.device)
+    labels = torch.empty(N, T, device=lv.device, dtype=torch.uint8)
+    logits = torch.empty(N, T, mdesc.dims[mdesc.num_layers], device=lv.device, dtype=torch.float32) if want_logits else None
+    _lib.check(L.sn_rm_mask_point_labels(_lib.dev(x, "xyzs"), _lib.dev(e, "extra"), _lib.dev(lv, "live"), N, T, E, float(bound),
+                                         C.byref(gdesc), C.byref(mdesc), _lib.dev(labels, "labels", torch.uint8), _lib.dev(logits, "logits"),
+                                         ws.data_ptr(), ws.numel(), _lib.stream()), "sn_rm_mask_point_labels")
+    return (labels, logits) if want_logits else labels

@@ -285,11 +285,11 @@ def _fill_io(plan: RenderPlan, io, N: int, tile_w: int, want, u_tables, bins0_ta
             io.weights_sum = buf("weights_sum", (N,))
     for k in range(S):
         T = plan.num_steps[k]
-        if "bins" in want:
+        if "bins" in want or (k == S - 1 and "bins_last" in want):
             io.bins[k] = buf(f"bins{k}", (N, T + 1))
         if "weights" in want or (k == S - 1 and "weights_last" in want):
             io.weights[k] = buf(f"weights{k}", (N, T))
-        if "sigmas" in want:
+        if "sigmas" in want or (k == S - 1 and "sigmas_last" in want):
             io.sigmas[k] = buf(f"sigmas{k}", (N, T))
         if "inds" in want and k >= 1:
             io.inds[k] = buf(f"inds{k}", (N, T + 1), torch.int32)
