@@ -1638,15 +1638,139 @@ __device__ __forceinline__ void stage_w3p(float *__restrict__ dst, const float *
 }
 // sum_i w[i] * x[i] over the lane's 32 hidden rows: four interleaved ascending fmaf chains, combined (s0 + s1) + (s2 + s3)
 typedef float f2v __attribute__((ext_vector_type(2)));
+// (one step of the four chains and their closing sum stand alone: the spread matrix phase below issues them apart, in the same order)
+__device__ __forceinline__ void dot32_step(const float4 &ww, float x0, float x1, float x2, float x3, f2v &s01, f2v &s23) {
+    s01 = __builtin_elementwise_fma(f2v{ww.x, ww.y}, f2v{x0, x1}, s01);
+    s23 = __builtin_elementwise_fma(f2v{ww.z, ww.w}, f2v{x2, x3}, s23);
+}
+__device__ __forceinline__ float dot32_sum(const f2v &s01, const f2v &s23) { return (s01.x + s01.y) + (s23.x + s23.y); }
 __device__ __forceinline__ float dot32_lds(const float *__restrict__ w, const float (&x)[32]) {
     f2v s01 = {0.0f, 0.0f}, s23 = {0.0f, 0.0f};
 #pragma unroll
     for (int i4 = 0; i4 < 8; ++i4) {
         const float4 ww = *reinterpret_cast<const float4 *>(w + 4 * i4);
-        s01 = __builtin_elementwise_fma(f2v{ww.x, ww.y}, f2v{x[4 * i4 + 0], x[4 * i4 + 1]}, s01);
-        s23 = __builtin_elementwise_fma(f2v{ww.z, ww.w}, f2v{x[4 * i4 + 2], x[4 * i4 + 3]}, s23);
+        dot32_step(ww, x[4 * i4 + 0], x[4 * i4 + 1], x[4 * i4 + 2], x[4 * i4 + 3], s01, s23);
     }
-    return (s01.x + s01.y) + (s23.x + s23.y);
+    return dot32_sum(s01, s23);
+}
+
+// The matrix phase of one wave-sample in the linear-tail kernel -- layers 1 and 2 of BOTH tiles and each tile's share of the density row --
+// with its vector work issued UNDER its MFMAs.  grid_mlp_mfma16_l12 + dot32_lds above issue the same instructions in clumps: the 12 layer-1
+// MFMAs of a tile back to back with empty gaps, then ReLU + split blocks with the matrix pipe idle, every weight fragment requested right
+// in front of the wait that consumes it.  An MFMA of this shape holds the SIMD's vector issue for 8 of its 32 cycles, so about five vector
+// instructions per gap are (nearly) free and a clump is paid in full.  Here every gap between two MFMAs is one scheduling region (closed
+// by a sched_barrier) that holds what the table below puts there, one "piece" of about six vector instructions at a time:
+//   W(s)      the (hi, lo) weight fragment of step s is requested under step s - 1: lo behind its first MFMA (the only one that reads a lo
+//             image), hi behind its last -- each into registers that have just died, so the prefetch costs none (the waits are counted:
+//             later requests are in flight behind it)
+//   S(q, p)   ReLU + split of one register pair of h1 -> dword p of the layer-2 B operand q:  q = 0, 1 under the layer-1 mt = 1 chain,
+//             q = 2, 3 under the first layer-2 steps; each is complete one gap before the MFMA that reads it
+//   X(i4)     ReLU of four h2 registers + their step of the density dot: the mt = 0 half under the layer-2 mt = 1 chain, the mt = 1 half
+//             of tile 0 under tile 1's layer-1 chain (tile 1's own is the tail of the phase)
+//   B(t + 1)  tile 1's slab rows are requested under tile 0's layer 2, when the registers of tile 0's rows are free again
+// Every accumulator receives the products of its chain in the order of grid_mlp_mfma16_l12 (Al Bh, Ah Bl, Ah Bh; k ascending) and the
+// dot keeps dot32_lds's four chains: the results are equal bit for bit (tests/test_gpu_final_matrix_phase.py holds the two orders together).
+template <bool SW>
+__device__ __forceinline__ void grid_mlp_mfma16_l12_spread(const uint4 *__restrict__ pk, const uint32_t *__restrict__ slab_hi,
+                                                           const uint32_t *__restrict__ slab_lo, const float *__restrict__ w3,
+                                                           float (&xh)[2][32], float (&part)[2]) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lo = lane & 31u, hi = lane >> 5;
+    const floatx16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint4 W[2][2];                  // [step & 1][0 = hi image, 1 = lo image]
+    uint4 B[2][2];                  // layer-1 B operand: [st][hi, lo]
+    uint32_t bb[4][2][4];           // layer-2 B operands: [q][hi, lo][dword]
+    floatx16 h1[2], h2[2][2];       // h2[tile][mt]
+    float4 ww[2][8];                // [tile][i4]: rows of the density row, requested a gap or two ahead of their step
+    f2v s01[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}}, s23[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
+    // tile 1 reads the weights tile 0 read: behind an offset of its own, or the optimiser keeps all 24 fragments of tile 0 in registers for it
+    const uint32_t oz1 = opaque_zero();
+    const uint4 *const pkT[2] = {pk, pk + oz1};
+    const float *const w3T[2] = {w3, w3 + oz1};
+    auto rdW = [&](int S, int im) { W[S & 1][im] = pkT[S / 12][((S % 12) * 2 + im) * 64 + lane]; };
+    auto rdB = [&](int t, int st, int im) {
+        const uint32_t off = slab_dword<SW>((uint32_t)t * 32u + lo, 4u * hi + 8u * (uint32_t)st);
+        B[st][im] = *reinterpret_cast<const uint4 *>((im ? slab_lo : slab_hi) + off);
+    };
+    auto rdw3 = [&](int t, int i4) { ww[t][i4] = *reinterpret_cast<const float4 *>(w3T[t] + 4 * i4); };
+    auto S_ = [&](int q, int p) {
+        const floatx16 &v = h1[q >> 1];
+        const int i = 8 * (q & 1) + 2 * p;
+        split2(relu_ieee(v[i]), relu_ieee(v[i + 1]), bb[q][0][p], bb[q][1][p]);
+    };
+    auto X_ = [&](int t, int i4) {
+        const floatx16 &v = h2[t][i4 >> 2];
+        const int r = 4 * (i4 & 3);
+        float (&x)[32] = xh[t];
+        x[4 * i4 + 0] = relu_ieee(v[r + 0]); x[4 * i4 + 1] = relu_ieee(v[r + 1]);
+        x[4 * i4 + 2] = relu_ieee(v[r + 2]); x[4 * i4 + 3] = relu_ieee(v[r + 3]);
+        dot32_step(ww[t][i4], x[4 * i4 + 0], x[4 * i4 + 1], x[4 * i4 + 2], x[4 * i4 + 3], s01[t], s23[t]);
+    };
+    // head: what the first MFMA reads first
+    rdW(0, 1); rdB(0, 0, 0); rdW(0, 0); rdB(0, 0, 1); rdB(0, 1, 0); rdB(0, 1, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    static_for<0, 2>([&](auto tt) {
+        constexpr int t = decltype(tt)::value;
+        static_for<0, 36>([&](auto mm) {
+            constexpr int m = decltype(mm)::value, s = m / 3, k = m % 3, S = 12 * t + s;
+            // ---- MFMA m of the tile: product k of step s ----
+            uint4 bh, bl;
+            if constexpr (s < 4) { bh = B[s & 1][0]; bl = B[s & 1][1]; }
+            else {
+                constexpr int q = s & 3;
+                bh = uint4{bb[q][0][0], bb[q][0][1], bb[q][0][2], bb[q][0][3]};
+                bl = uint4{bb[q][1][0], bb[q][1][1], bb[q][1][2], bb[q][1][3]};
+            }
+            floatx16 &acc = s < 4 ? h1[(s >> 1) & 1] : h2[t][s < 4 ? 0 : (s - 4) >> 2];
+            if constexpr (k == 0 && (s == 0 || s == 2 || s == 4 || s == 8)) acc = zero16;
+            const half8_t Ah = __builtin_bit_cast(half8_t, W[S & 1][0]), Al = __builtin_bit_cast(half8_t, W[S & 1][1]);
+            const half8_t Bh = __builtin_bit_cast(half8_t, bh), Bl = __builtin_bit_cast(half8_t, bl);
+            if constexpr (k == 0) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh, acc, 0, 0, 0);   // small terms first (mfma3)
+            if constexpr (k == 1) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl, acc, 0, 0, 0);
+            if constexpr (k == 2) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh, acc, 0, 0, 0);
+            // ---- the gap behind it ----
+            if constexpr (k == 0 && S + 1 < 24) rdW(S + 1, 1);       // the lo image was read by product 0 only: its registers take the next step's
+            if constexpr (k == 2 && S + 1 < 24) rdW(S + 1, 0);       // and the hi image's behind the step's last product
+            if constexpr (t == 1) {           // tile 0's tail
+                if constexpr (m == 0) { X_(0, 4); rdw3(0, 5); }
+                if constexpr (m == 1) { rdw3(0, 6); rdw3(0, 7); }
+                if constexpr (m == 3) X_(0, 5);
+                if constexpr (m == 4) X_(0, 6);
+                if constexpr (m == 5) { X_(0, 7); part[0] = dot32_sum(s01[0], s23[0]); }
+            }
+            if constexpr (m >= 6 && m < 14) S_((m - 6) >> 2, (m - 6) & 3);
+            if constexpr (m == 14) S_(2, 0);
+            if constexpr (m == 15) S_(2, 1);
+            if constexpr (m == 16) { S_(2, 2); S_(2, 3); }
+            if constexpr (m == 17) S_(3, 0);
+            if constexpr (m == 18) S_(3, 1);
+            if constexpr (m == 19) { S_(3, 2); S_(3, 3); }
+            if constexpr (t == 0) {           // tile 1's slab rows, into the registers the layer-2 operands q = 0..2 leave behind
+                if constexpr (m == 30) rdB(1, 0, 0);
+                if constexpr (m == 32) rdB(1, 0, 1);
+                if constexpr (m == 33) rdB(1, 1, 0);
+                if constexpr (m == 34) rdB(1, 1, 1);
+            }
+            if constexpr (m == 24) rdw3(t, 0);
+            if constexpr (m == 26) rdw3(t, 1);
+            if constexpr (m == 28) rdw3(t, 2);
+            if constexpr (m == 30) rdw3(t, 3);
+            if constexpr (m == 32) rdw3(t, 4);
+            if constexpr (m == 26) X_(t, 0);
+            if constexpr (m == 28) X_(t, 1);
+            if constexpr (m == 30) X_(t, 2);
+            if constexpr (m == 32) X_(t, 3);
+            if constexpr (t == 1) {           // the rows of the tail, while the last MFMAs run (no tile follows: the slab-row registers are free)
+                if constexpr (m == 33) rdw3(1, 5);
+                if constexpr (m == 34) rdw3(1, 6);
+                if constexpr (m == 35) rdw3(1, 7);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    });
+    // tail: tile 1's mt = 1 half
+    X_(1, 4); X_(1, 5); X_(1, 6); X_(1, 7);
+    part[1] = dot32_sum(s01[1], s23[1]);
 }
 
 // hash-grid features of one position, split into f16 hi / lo and written to this lane's slab rows
@@ -1709,7 +1833,9 @@ enum { MLP_VALU = 0, MLP_F32 = 1, MLP_F16X3 = 2 };
 
 // AUX: the instantiation that also serves the feature stage (weights -> scratch) and the opt-in early termination;
 // the plain one carries neither (one spilled register less in the march of the headline configuration)
-template <typename TT, int L, int C, int H1, int H2, int NOUT, int VH, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3>
+// PORD: the matrix phase of the linear-tail form in the order it had before grid_mlp_mfma16_l12_spread (tile by tile, vector work in clumps):
+// the A/B partner of the spread order, instantiated by experiments builds only (SN_EXP_MATRIX_CLUMPED)
+template <typename TT, int L, int C, int H1, int H2, int NOUT, int VH, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3, bool PORD = false>
 __global__ __launch_bounds__(256, MODE == MLP_VALU ? 1 : SN_FINAL_WAVES) void k_final_stage(FinalArgs a) {
     SN_POISON_ALL();
     static_assert(NP == 3 || (LT && !L0L && !AUX), "reduced-product MLP forms: plain linear-tail instantiations only");
@@ -1978,10 +2104,14 @@ __global__ __launch_bounds__(256, MODE == MLP_VALU ? 1 : SN_FINAL_WAVES) void k_
         if constexpr (LT) {
             const uint32_t oz = opaque_zero();
             float part[2];
+            if constexpr (NP == 3 && !PORD) {
+                grid_mlp_mfma16_l12_spread<L0L>(reinterpret_cast<const uint4 *>(lds) + oz, slab_hi, slab_lo, w3p + oz, xh, part);
+            } else {
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                grid_mlp_mfma16_l12<L0L, NP>(reinterpret_cast<const uint4 *>(lds) + oz, slab_hi, slab_lo, t, xh[t]);
-                part[t] = dot32_lds(w3p + oz, xh[t]);                                  // this half's share of the density row
+                for (int t = 0; t < 2; ++t) {
+                    grid_mlp_mfma16_l12<L0L, NP>(reinterpret_cast<const uint4 *>(lds) + oz, slab_hi, slab_lo, t, xh[t]);
+                    part[t] = dot32_lds(w3p + oz, xh[t]);                              // this half's share of the density row
+                }
             }
             __builtin_amdgcn_wave_barrier();
             // lanes 0-31 are the home of the tile-0 samples, lanes 32-63 of the tile-1 samples: half 0's share + half 1's share
@@ -3416,6 +3546,7 @@ struct FinalRoute {
     int K = -1;                            // dense levels the instantiation reads as packed rows (-1: level kind at run time)
     bool aux = false, eo = false;          // AUX (last-stage weights out / early stop), EO (exact early-out)
     int np = 3;                            // products per split multiply
+    bool clumped = false;                  // LT: the matrix phase in its clumped order (SN_EXP_MATRIX_CLUMPED, experiments builds)
     uint32_t grid = 0, block = 256;
     size_t lds = 0;                        // dynamic LDS bytes of the launch
     const char *name = "";                 // what sn_launch_info reports, with the two figures below
@@ -3543,6 +3674,8 @@ static void plan_final(const sn_render_cfg *cfg, const sn_render_io *io, RenderR
         f.dense = f.K; f.gathers = lv_gathers(f.K) - (l0 ? 2u : 0u);
         // SN_MLP_F16X1: the reduced form of the plain launch with fp16 tables
         if (f16 && !f.eo && r->mlp_np == 1 && !f.aux && !l0) f.np = 1;
+        // SN_EXP_MATRIX_CLUMPED (round 9): the A/B partner of the spread matrix phase, same bits (the reduced-product form has no spread order)
+        f.clumped = xp == SN_EXP_MATRIX_CLUMPED && f.np == 3 && !l0;
         // SN_EXP_FINAL_ONE_WG (round 6): the last stage asks for 84 KiB of LDS, so only ONE of its workgroups fits a CU and half of every SIMD's
         // registers stay free for the proposal-stage workgroups of the OTHER row band (tuning.band_streams): vector-ALU-bound waves beside
         // texture-bound ones on the same SIMD instead of on different CUs
@@ -3766,8 +3899,8 @@ static PropKern prop_kernel(const PropRoute &p) {
 
 using FinalKern = void (*)(FinalArgs);
 // k_final_stage at the reference network's sizes
-template <typename TT, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3>
-static FinalKern fs() { return k_final_stage<TT, 16, 2, 64, 64, 16, 32, MODE, K, AUX, LT, L0L, EO, NP>; }
+template <typename TT, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3, bool PORD = false>
+static FinalKern fs() { return k_final_stage<TT, 16, 2, 64, 64, 16, 32, MODE, K, AUX, LT, L0L, EO, NP, PORD>; }
 template <typename TT> static FinalKern final_kernel_of(const FinalRoute &f) {
     constexpr bool half = std::is_same<TT, __half>::value;
     switch (f.family) {
@@ -3782,6 +3915,13 @@ template <typename TT> static FinalKern final_kernel_of(const FinalRoute &f) {
             if constexpr (half) {
                 if (f.np == 1) return f.K == 7 ? fs<__half, MLP_F16X3, 7, false, true, false, false, 1>() : fs<__half, MLP_F16X3, 5, false, true, false, false, 1>();
             }
+#ifdef SN_EXPERIMENTS
+            if (f.clumped) {
+                if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, false, true, false, true, 3, true>() : fs<TT, MLP_F16X3, 7, false, true, false, false, 3, true>();
+                if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, true, true, false, true, 3, true>() : fs<TT, MLP_F16X3, 5, true, true, false, false, 3, true>();
+                return f.eo ? fs<TT, MLP_F16X3, 5, false, true, false, true, 3, true>() : fs<TT, MLP_F16X3, 5, false, true, false, false, 3, true>();
+            }
+#endif
             if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, false, true, false, true>() : fs<TT, MLP_F16X3, 7, false, true, false, false>();
             if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, true, true, false, true>() : fs<TT, MLP_F16X3, 5, true, true, false, false>();
             return f.eo ? fs<TT, MLP_F16X3, 5, false, true, false, true>() : fs<TT, MLP_F16X3, 5, false, true, false, false>();
