@@ -890,6 +890,57 @@ int sn_rm_object_composite(const uint8_t *labels, const float *sigmas, const flo
                            uint32_t N, uint32_t T, uint32_t keep_mask, int32_t invert, int32_t last_sample_opaque, float *weights_sum,
                            float *depth, float *f_image, float *weights, sn_stream_t stream);
 
+/* Geometry export (NeRFRenderer.density_volume / extract_mesh): the object, or the whole scene, taken out of the field as a triangle mesh.
+ * (The reference offers --render_mesh / --density_thresh, main.py:183-185, imports mcubes and trimesh, nerf/renderer.py, and calls neither.
+ * The definition below is this project's; tests/mesh_ref.py restates it operation for operation, and topology pins the restatement.)
+ *
+ * sn_rm_lattice_points: positions of the lattice vertices first .. first + count - 1 of an nx x ny x nz lattice -> xyz [count,3].  Linear
+ * index (x ny + y) nz + z, z fastest; p_a = origin_a + (float)i_a * step_a, the product and the sum rounded separately; contract != 0: then
+ * through the contraction of sn_rm_contract.  Bit-equal to that operator on the same lattice made with torch; it spares a meshgrid per chunk.
+ * origin, step: 3 floats each on the HOST.  count == 0 returns SN_OK without touching a pointer.
+ *
+ * Marching tetrahedra.  volume [nx,ny,nz] fp32, z fastest.
+ *   Inside test     a lattice vertex is inside iff f > iso, evaluated in fp32: NaN is outside, +inf is inside, a value equal to iso is outside.
+ *   Edge slots      each lattice vertex owns up to 7 edges: slot e goes to the vertex at offset (1,0,0),(0,1,0),(0,0,1),(1,1,0),(1,0,1),
+ *                   (0,1,1),(1,1,1) for e = 0..6, where that vertex is in range.  An edge carries a mesh vertex iff its two ends differ in
+ *                   inside-ness.
+ *   Position        t = (iso - f_a) / (f_b - f_a) in fp32 with IEEE division, a the owning end; if !(t >= 0 && t <= 1) then t = 0.5 (NaN,
+ *                   inf/inf).  Per axis pos = origin + ((float)i + t e) step, each operation rounded on its own (e = the offset's 0 or 1).
+ *   Vertex order    by the owning lattice vertex's linear index, then slot: id(v,e) = base[v] + popcount(mask[v] & ((1 << e) - 1)).
+ *   Tetrahedra      a cell is identified by its lowest corner; its six tetrahedra are the Kuhn paths v0 = (0,0,0) -> v0 + e_p1 -> + e_p2 ->
+ *                   (1,1,1) for the six axis permutations p in lexicographic order.  (The diagonal of every cube face runs from the face's
+ *                   lowest to its highest corner, the same for both cubes that share the face: no ambiguous cases, watertight by construction.)
+ *   Triangles       per tetrahedron, corners in path order.  One inside corner I and outside corners O0,O1,O2: (I,O0),(I,O1),(I,O2).  Three
+ *                   inside corners: (I0,O),(I1,O),(I2,O).  Two: the quad a=(I0,O0), b=(I0,O1), c=(I1,O1), d=(I1,O0) as (a,b,c),(a,c,d).
+ *   Orientation     each triangle is flipped (its last two vertices swapped) so that its normal points from inside to outside.  Decided once,
+ *                   when the 16 x 6 table is generated (csrc/mesh_table.h, at compile time), from the edge mid-points on the unit lattice and
+ *                   the centroids of the inside and outside corners -- never from run-time positions, which lose consistency on zero-area
+ *                   triangles.
+ *   Triangle order  by cell linear index (x (ny-1) + y)(nz-1) + z, then tetrahedron, then triangle.
+ *   Degenerate      zero-area triangles (a mesh vertex sitting on a lattice vertex) are kept: the topology stays manifold.
+ *   Normals         lattice gradient by central differences (f[i+1] - f[i-1]) / (2 step), one-sided (f[i+1] - f[i]) / step at the faces;
+ *                   g = g_a + t (g_b - g_a) along the edge with the same t; n = -g / |g| (outward for a density), |g| =
+ *                   sqrt((gx gx + gy gy) + gz gz); a zero or non-finite length gives (0,0,0).
+ *
+ * sn_rm_isosurface_workspace_bytes: 8 bytes per 1024 lattice vertices + 4 bytes + 1 byte per lattice vertex (each part rounded up to 16):
+ * at most 8 bytes per lattice vertex.  0 (with a message) for an unsupported size: a dimension < 2, or nx ny nz >= 2^31.
+ * sn_rm_isosurface_count: classifies every lattice vertex (one byte: inside bit + 7 edge bits), ranks, scans, and leaves
+ * counts[0..1] = {n_vertices, n_triangles} (uint32, DEVICE; 2^32 - 1 = more than that) -- two launches, the second a single workgroup.
+ * sn_rm_isosurface_emit: vertices [cap_v,3] f32, normals [cap_v,3] f32 or NULL, triangles [cap_t,3] int32, from the workspace the count
+ * left.  Every store is guarded by the capacities and the structure is read from the workspace alone: a volume that changed between the
+ * two calls, or a capacity that is too small, truncates or misplaces the output and never writes out of bounds.  With both capacities 0
+ * it returns SN_OK without touching a pointer.  origin, step: 3 floats each on the HOST.  workspace: 16-byte aligned.
+ * No atomics, no workgroup waits on another: the output is identical from run to run and identical in order to the restatement.
+ * Errors before any launch: SN_ERR_INVALID (NULL pointer, misaligned workspace), SN_ERR_UNSUPPORTED (size), SN_ERR_WORKSPACE. */
+int sn_rm_lattice_points(const float *origin, const float *step, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t first, uint32_t count,
+                         int32_t contract, float *xyz, sn_stream_t stream);
+size_t sn_rm_isosurface_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int sn_rm_isosurface_count(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void *workspace, size_t workspace_bytes,
+                           uint32_t *counts, sn_stream_t stream);
+int sn_rm_isosurface_emit(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, const float *origin, const float *step,
+                          const void *workspace, size_t workspace_bytes, float *vertices, float *normals, int32_t *triangles,
+                          uint32_t cap_v, uint32_t cap_t, sn_stream_t stream);
+
 /* Training-time forward of a bias-free perceptron with 256-wide hidden layers and no skip connections (nerf/network.py:31-66: F.linear +
  * activation per layer; the per-sample mask head in training, network.py:118-123, trainer.py:401-428) in ONE kernel, true fp32 products
  * and accumulation on the matrix cores (v_mfma_f32_32x32x2_f32; results differ from a BLAS GEMM only by summation order).

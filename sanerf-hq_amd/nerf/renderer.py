@@ -475,7 +475,78 @@ class NeRFRenderer(nn.Module):
         return results
 
     # ---------------------------------------------------------------------------------------
-    fused_training_ops = True     # RGB-mode training: unit-cube positions, fused small MLPs, one-kernel per-ray head (False: the operator chain)
+    # Geometry export: the density of the main field on a world-space lattice, and its isosurface as a triangle mesh.  (The reference offers
+    # --render_mesh / --density_thresh, imports mcubes and trimesh, and calls neither; this is the project's own definition:
+    # include/sanerf_hip.h, tests/mesh_ref.py.)
+    def _inference_only(self, what: str):
+        if self._needs_field_grad(True) or (torch.is_grad_enabled() and self.opt.with_mask
+                                            and any(p.requires_grad for m in (self.m_grid, self.mask_mlp) for p in m.parameters())):
+            raise RuntimeError(f"{what} is an inference query: call it under torch.no_grad() (or on a frozen field)")
+
+    @staticmethod
+    def _lattice(resolution, aabb):
+        """((nx, ny, nz), origin, step) of a lattice with its first and last vertices on the faces of aabb; origin and step as the fp32
+        values the kernels receive."""
+        import numpy as np
+        res = (int(resolution),) * 3 if isinstance(resolution, int) else tuple(int(r) for r in resolution)
+        if len(res) != 3 or min(res) < 2:
+            raise ValueError(f"resolution must be an int or a triple, every entry >= 2 (got {resolution})")
+        box = [-1.0, -1.0, -1.0, 1.0, 1.0, 1.0] if aabb is None else [float(v) for v in (aabb.tolist() if torch.is_tensor(aabb) else aabb)]
+        if len(box) != 6:
+            raise ValueError("aabb must be [xmin, ymin, zmin, xmax, ymax, zmax]")
+        origin = [float(np.float32(box[a])) for a in range(3)]
+        step = [float(np.float32((box[3 + a] - box[a]) / (res[a] - 1))) for a in range(3)]
+        return res, origin, step
+
+    def density_volume(self, resolution, aabb=None, instance_ids=None, invert=False, chunk=1 << 20):
+        """sigma of the main field on a world-space lattice: [nx,ny,nz] fp32 (z fastest), vertex i at aabb_min + i * step per axis.
+        resolution: an int or a triple; aabb: default [-1,1]^3, the region the contraction leaves alone (positions outside it are contracted
+        when opt.contract is set).  With instance_ids, sigma is kept where the mask field's label -- _point_labels, the kernels of
+        render_object -- is in the set, xor invert, and is 0 elsewhere.  Works in chunks of `chunk` lattice vertices (positions from
+        raymarching.lattice_points, no meshgrid); the result does not depend on chunk.  No-grad only."""
+        self._inference_only("density_volume")
+        res, origin, step = self._lattice(resolution, aabb)
+        total = res[0] * res[1] * res[2]
+        chunk = max(int(chunk), 1)
+        device = self.aabb_train.device
+        lut = None
+        if instance_ids is not None:
+            if not self.opt.with_mask:
+                raise RuntimeError("density_volume: instance_ids need the mask field (opt.with_mask)")
+            keep = rm.keep_mask_of(instance_ids)
+            lut = torch.tensor([i < 32 and bool((keep >> i) & 1) for i in range(256)], device=device) ^ bool(invert)
+        volume = torch.empty(total, device=device, dtype=torch.float32)
+        with torch.no_grad():
+            for first in range(0, total, chunk):
+                count = min(chunk, total - first)
+                xyz = rm.lattice_points(origin, step, res, first, count, contract=bool(self.opt.contract), device=device)
+                out = self.density(xyz)
+                sigma = out["sigma"].reshape(-1).float()
+                if lut is not None:
+                    # the label kernel takes [rays, samples] with at least 4 samples a ray: rows of 4 lattice vertices, the last one padded
+                    pad = (-count) % 4
+                    geo = out["geo_feat"]
+                    if pad:
+                        xyz = torch.cat([xyz, xyz.new_zeros(pad, 3)])
+                        geo = torch.cat([geo, geo.new_zeros(pad, geo.shape[-1])])
+                    live = torch.cat([sigma, sigma.new_zeros(pad)]) if pad else sigma
+                    labels = self._point_labels(live.reshape(-1, 4), xyz.reshape(-1, 4, 3), geo.reshape(-1, 4, geo.shape[-1]).contiguous())
+                    sigma = torch.where(lut[labels.reshape(-1)[:count].long()], sigma, torch.zeros_like(sigma))
+                volume[first:first + count] = sigma
+        return volume.reshape(res)
+
+    def extract_mesh(self, resolution=256, threshold=None, aabb=None, instance_ids=None, invert=False, normals=True):
+        """The surface sigma = threshold (default self.density_thresh) of density_volume(resolution, aabb, instance_ids, invert) by marching
+        tetrahedra on the device: {"vertices" [V,3] f32, "normals" [V,3] f32 or None, "triangles" [T,3] int32} in world coordinates -- the
+        whole scene, or with instance_ids the object alone (invert: the scene without it).  The size of the result depends on the data
+        (raymarching.isosurface reads two totals back once).  nerf.utils.save_mesh writes it as a PLY file."""
+        res, origin, step = self._lattice(resolution, aabb)
+        volume = self.density_volume(res, aabb, instance_ids, invert)
+        iso = float(self.density_thresh if threshold is None else threshold)
+        return rm.isosurface(volume, iso, origin, step, normals=normals)
+
+    # ---------------------------------------------------------------------------------------
+    fused_training_ops = True    # RGB-mode training: unit-cube positions, fused small MLPs, one-kernel per-ray head (False: the operator chain)
 
     def _unit_path_ok(self, rays_o, bg_color, return_mask) -> bool:
         """The training route built from the fused training operators (_run_autograd_unit): the reference network's own field

@@ -309,3 +309,42 @@ def freeze_loaded_parameters(model, model_dict):
             v.requires_grad = False
             frozen.append(k)
     return frozen
+
+
+# ---------------------------------------------------------------------------------------------
+# geometry export: what NeRFRenderer.extract_mesh returns, as a file
+# ---------------------------------------------------------------------------------------------
+def save_mesh(path, vertices, triangles, normals=None):
+    """Write a triangle mesh as a binary little-endian PLY file: vertices [V,3] (float x y z, and float nx ny nz with normals [V,3]) and
+    triangles [T,3] (uchar 3 + three int32 vertex indices per face).  Tensors or arrays; host side, numpy only."""
+    def host(a, dtype, what):
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"save_mesh: {what} must be [n,3], got {tuple(a.shape)}")
+        return np.ascontiguousarray(a, dtype=dtype)
+
+    v, t = host(vertices, "<f4", "vertices"), host(triangles, "<i4", "triangles")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        n = host(normals, "<f4", "normals")
+        if n.shape[0] != v.shape[0]:
+            raise ValueError(f"save_mesh: {n.shape[0]} normals for {v.shape[0]} vertices")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if t.size and (t.min() < 0 or t.max() >= v.shape[0]):
+        raise ValueError("save_mesh: a triangle index is outside the vertices")
+    vert = np.empty(v.shape[0], dtype=fields)
+    for i, name in enumerate("xyz"):
+        vert[name] = v[:, i]
+        if normals is not None:
+            vert["n" + name] = n[:, i]
+    face = np.empty(t.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    face["n"] = 3
+    face["v"] = t
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
+    header += [f"property float {name}" for name, _ in fields]
+    header += [f"element face {t.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())
+    return path

@@ -13,7 +13,9 @@ code in nerf/utils.py and nerf/renderer.py.  This package is that operator surfa
               mlp_forward          nerf/network.py:31-66 (+ LayerNorm :115): the 256-wide head MLPs on the matrix cores (inference)
               mask_point_labels    per-sample argmax of the mask field in the one-kernel mask head (nothing per-sample but the labels written)
     object    object_composite     re-integration of a ray over the samples whose label is kept: the object alone, or the scene without it
-    render    render_rays          nerf/renderer.py:221-357 + nerf/network.py:146-186, fused
+    mesh      lattice_points       positions of a window of a world-space lattice (contracted or not), no meshgrid
+              isosurface           marching tetrahedra on a density lattice: vertices, normals, triangles (the size is data-dependent)
+    render    render_rays         nerf/renderer.py:221-357 + nerf/network.py:146-186, fused
     jitter    jitter               nerf/renderer.py:262-270, 97-102: one stage's perturbed bins / u from caller-supplied uniforms
               jitter_tables        the same tables for every stage in one launch, uniforms from a Philox counter on the device (DeviceJitter)
     mask, meters, distill, rgb_loss, prompts, collate: the mask field's losses and output stage, the device-side meters, the distillation
@@ -34,4 +36,5 @@ from .collate import weighted_draw, collate_gather, COLLATE_OUTPUTS  # noqa: F40
 from .heads import (  # noqa: F401
     grid_composite, mlp_forward, mlp_wide_overflow, mask_head, mask_head_fusable, mask_point_labels, mask_point_labels_fusable)
 from .object import object_composite, keep_mask_of, LABEL_SKIPPED  # noqa: F401
+from .mesh import lattice_points, isosurface, isosurface_counts, isosurface_emit, ISOSURFACE_MAX_VERTICES  # noqa: F401
 from .render import RenderPlan, Tuning, tuning, last_launch_info, route_info, tile_order_info, render_rays, FP16_SPLIT_LIMIT  # noqa: F401
