@@ -941,6 +941,63 @@ int sn_rm_isosurface_emit(const float *volume, uint32_t nx, uint32_t ny, uint32_
                           const void *workspace, size_t workspace_bytes, float *vertices, float *normals, int32_t *triangles,
                           uint32_t cap_v, uint32_t cap_t, sn_stream_t stream);
 
+/* Mesh clean-up (raymarching.mesh_components / mesh_clean, NeRFRenderer.extract_mesh(min_component_triangles, keep_largest)): the connected
+ * components of an indexed triangle mesh and the removal of the small ones -- floaters, label noise -- on the device (csrc/mesh_clean.hip).
+ * The definition is this project's; tests/mesh_clean_ref.py restates it in numpy.
+ *
+ * Input: triangles [T,3] int32 and a vertex count V.  Any indexed mesh, not only the isosurface's.
+ *   Valid triangle  all three indices in [0, V).  An invalid triangle connects nothing, is counted nowhere and is never emitted; every index
+ *                   is range-tested before it is used as an address.  Degenerate triangles (a,a,b) and (a,a,a) are valid.  Duplicates are
+ *                   valid and each counts.
+ *   Component       two vertices are connected iff some valid triangle contains both, closed transitively.  labels[v] (int32) is the
+ *                   smallest vertex index of v's component.  A vertex in no valid triangle is its own component with 0 triangles.
+ *   Statistics      [V] arrays that are nonzero only at roots (labels[r] == r): triangle_counts[r] = the number of valid triangles of r's
+ *                   component (a triangle belongs to the component of its corners), vertex_counts[r] = its number of vertices (int32);
+ *                   counts[0] = the number of roots, counts[1] = the number of roots with at least one triangle (uint32, DEVICE).
+ *   Key             key[r] = (uint64)triangle_counts[r] << 32 | (0xFFFFFFFF - r).  Keys are unique: a larger key means more triangles,
+ *                   then the lower root index.
+ *   Selection       a component is kept iff triangle_counts[r] >= max(min_triangles, 1) AND key[r] >= *min_key.  min_key is one uint64 on
+ *                   the DEVICE; 0 keeps everything.  "Keep the largest k": *min_key = the k-th largest key (with k at or beyond the number
+ *                   of components that have triangles, all of them are kept).
+ *   Filtered mesh   a vertex is kept iff its component is; a triangle iff it is valid and its component is kept.  Kept vertices keep their
+ *                   relative order, and so do kept triangles.  The new index of a vertex is its rank among the kept vertices; triangle
+ *                   indices are remapped to it.  Vertex and normal rows are copied bit for bit.  source_vertex [V'] (int32, optional) =
+ *                   the old index of each kept vertex.
+ * The labels are a unique fixed point: they depend on neither the algorithm, the launch shape nor the run.
+ *
+ * sn_rm_mesh_components_init: labels[v] = v.
+ * sn_rm_mesh_components_sweep: `rounds` rounds (at most 4096 per call) of two launches each over labels that init, or an earlier sweep,
+ * left.  Hook, one lane per triangle: range-test a, b, c; la, lb, lc = their labels, m = the smallest; for each corner x with lx > m,
+ * atomicMin(&labels[x], m) and atomicMin(&labels[lx], m).  Jump, one lane per vertex: l = labels[l] until labels[l] == l, stored by
+ * atomicMin.  changed [rounds] (uint32, DEVICE; zeroed by the call): changed[i] != 0 iff round i lowered a label.  A round that lowered
+ * none proves the fixed point (csrc/mesh_clean.hip has the argument): the caller sweeps until the last round of a call reports 0.  No
+ * workgroup waits on another; stale reads only delay convergence; every chain that is followed strictly decreases.
+ * sn_rm_mesh_component_stats: the three statistics from final labels (the arrays are zeroed by the call); integer atomic adds.
+ * sn_rm_mesh_clean_workspace_bytes(V, T): 4 bytes per vertex + 4 bytes per triangle + 4 bytes per 1024 vertices + 4 bytes per 1024
+ * triangles, each of the four parts rounded up to 16.  0 (with a message) if V or T >= 2^31.
+ * sn_rm_mesh_filter_count: per vertex and per triangle the keep flag and the rank inside its segment of 1024, the scanned segment totals,
+ * and counts[0..1] = {V', T'} (uint32, DEVICE) -- three launches, the last a single workgroup.
+ * sn_rm_mesh_filter_emit: out_vertices [cap_v,3], out_normals [cap_v,3] (iff normals != NULL), out_triangles [cap_t,3], source_vertex
+ * [cap_v] or NULL, from the workspace the count left and `triangles` alone (labels are not read).  Every store is guarded by the capacities
+ * and every index is range-tested again: triangles that changed between the two calls, or a capacity that is too small, truncate or
+ * misplace the output (an index out of range is emitted as -1) and never write out of bounds.  workspace: 16-byte aligned.
+ * Every entry returns SN_OK without touching a pointer when V == 0 (the empty mesh: the caller knows every count is 0), the sweep also
+ * with rounds == 0, the emit also with both capacities 0.  triangles may be NULL when T == 0.
+ * Errors before any launch: SN_ERR_INVALID (NULL pointer, misaligned workspace), SN_ERR_UNSUPPORTED (V or T >= 2^31), SN_ERR_WORKSPACE.
+ * Nothing is placed by an atomic: the output is identical from run to run and identical in order to the restatement. */
+size_t sn_rm_mesh_clean_workspace_bytes(uint32_t V, uint32_t T);
+int sn_rm_mesh_components_init(uint32_t V, int32_t *labels, sn_stream_t stream);
+int sn_rm_mesh_components_sweep(const int32_t *triangles, uint32_t T, uint32_t V, int32_t *labels, uint32_t rounds, uint32_t *changed,
+                                sn_stream_t stream);
+int sn_rm_mesh_component_stats(const int32_t *triangles, uint32_t T, uint32_t V, const int32_t *labels, int32_t *triangle_counts,
+                               int32_t *vertex_counts, uint32_t *counts, sn_stream_t stream);
+int sn_rm_mesh_filter_count(const int32_t *triangles, uint32_t T, uint32_t V, const int32_t *labels, const int32_t *triangle_counts,
+                            uint32_t min_triangles, const uint64_t *min_key, void *workspace, size_t workspace_bytes, uint32_t *counts,
+                            sn_stream_t stream);
+int sn_rm_mesh_filter_emit(const int32_t *triangles, uint32_t T, uint32_t V, const float *vertices, const float *normals,
+                           const void *workspace, size_t workspace_bytes, float *out_vertices, float *out_normals, int32_t *out_triangles,
+                           int32_t *source_vertex, uint32_t cap_v, uint32_t cap_t, sn_stream_t stream);
+
 /* Training-time forward of a bias-free perceptron with 256-wide hidden layers and no skip connections (nerf/network.py:31-66: F.linear +
  * activation per layer; the per-sample mask head in training, network.py:118-123, trainer.py:401-428) in ONE kernel, true fp32 products
  * and accumulation on the matrix cores (v_mfma_f32_32x32x2_f32; results differ from a BLAS GEMM only by summation order).

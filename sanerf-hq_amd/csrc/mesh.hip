@@ -20,6 +20,7 @@
 // Every store of the emit is guarded by cap_v / cap_t; every load stays inside the lattice by the kernel's own range tests.
 // Workspace: 8 bytes per segment, 4 bytes + 1 byte per lattice vertex.  Plain vector loads and stores.
 #include "sn_common.h"
+#include "sn_wave.h"
 #include "mesh_table.h"
 
 namespace sn {
@@ -54,22 +55,6 @@ static inline IsoLayout iso_layout(const IsoDims &d) {
     l.mask = l.base + (size_t)d.V * 4u;
     l.bytes = l.mask + align16(d.V);
     return l;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// Exclusive prefix and total of a small per-lane count over the wave: one ballot per bit of the count.  Every lane of the wave calls it.
-template <int BITS>
-__device__ __forceinline__ void wave_rank(uint32_t cnt, uint32_t &prefix, uint32_t &total) {
-    prefix = 0u; total = 0u;
-#pragma unroll
-    for (int b = 0; b < BITS; ++b) {
-        const uint64_t m = __ballot((cnt >> b) & 1u);
-        prefix += lanes_below(m) << b;
-        total += (uint32_t)__popcll(m) << b;
-    }
 }
 
 __device__ __forceinline__ bool inside_of(float f, float iso) { return f > iso; }      // NaN outside, +inf inside, f == iso outside

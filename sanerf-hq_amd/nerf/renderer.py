@@ -535,15 +535,22 @@ class NeRFRenderer(nn.Module):
                 volume[first:first + count] = sigma
         return volume.reshape(res)
 
-    def extract_mesh(self, resolution=256, threshold=None, aabb=None, instance_ids=None, invert=False, normals=True):
+    def extract_mesh(self, resolution=256, threshold=None, aabb=None, instance_ids=None, invert=False, normals=True,
+                     min_component_triangles=0, keep_largest=0):
         """The surface sigma = threshold (default self.density_thresh) of density_volume(resolution, aabb, instance_ids, invert) by marching
         tetrahedra on the device: {"vertices" [V,3] f32, "normals" [V,3] f32 or None, "triangles" [T,3] int32} in world coordinates -- the
         whole scene, or with instance_ids the object alone (invert: the scene without it).  The size of the result depends on the data
-        (raymarching.isosurface reads two totals back once).  nerf.utils.save_mesh writes it as a PLY file."""
+        (raymarching.isosurface reads two totals back once).  nerf.utils.save_mesh writes it as a PLY file.
+
+        min_component_triangles, keep_largest (both 0: everything above the threshold, floaters included): the mesh then goes through
+        raymarching.mesh_clean, which keeps the connected components of at least that many triangles and / or the k largest."""
         res, origin, step = self._lattice(resolution, aabb)
         volume = self.density_volume(res, aabb, instance_ids, invert)
         iso = float(self.density_thresh if threshold is None else threshold)
-        return rm.isosurface(volume, iso, origin, step, normals=normals)
+        mesh = rm.isosurface(volume, iso, origin, step, normals=normals)
+        if min_component_triangles or keep_largest:
+            mesh = rm.mesh_clean(mesh, min_triangles=min_component_triangles, keep_largest=keep_largest)
+        return mesh
 
     # ---------------------------------------------------------------------------------------
     fused_training_ops = True    # RGB-mode training: unit-cube positions, fused small MLPs, one-kernel per-ray head (False: the operator chain)

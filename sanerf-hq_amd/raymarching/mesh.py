@@ -1,9 +1,12 @@
-"""Geometry export (mesh.hip): lattice positions and marching tetrahedra on a density lattice.
+"""Geometry export (mesh.hip, mesh_clean.hip): lattice positions, marching tetrahedra on a density lattice, and the clean-up of the mesh.
 
     lattice_points     positions of a window of the vertices of an nx x ny x nz lattice, optionally contracted -- no meshgrid per chunk
     isosurface         volume [nx,ny,nz], iso -> {"vertices" [V,3], "normals" [V,3] or None, "triangles" [T,3] int32}
-include/sanerf_hip.h states the definition (inside test, edge slots, Kuhn tetrahedra, orientation from the table, both orders, normals);
-tests/mesh_ref.py restates it in numpy, operation for operation."""
+    mesh_components    triangles [T,3], V -> labels, triangle and vertex counts per connected component
+    mesh_clean         a mesh without its small components (floaters, label noise): by triangle count and / or the largest k
+include/sanerf_hip.h states the definitions (inside test, edge slots, Kuhn tetrahedra, orientation from the table, both orders, normals;
+valid triangles, components, keys, selection, the filtered mesh's order); tests/mesh_ref.py and tests/mesh_clean_ref.py restate them in
+numpy."""
 from __future__ import annotations
 
 from typing import Sequence
@@ -99,3 +102,136 @@ def isosurface(volume: torch.Tensor, iso: float, origin=(0.0, 0.0, 0.0), step=(1
     if nv or nt:
         isosurface_emit(vol, iso, origin, step, ws, vertices, nrm, triangles)
     return {"vertices": vertices, "normals": nrm, "triangles": triangles}
+
+
+# ---- clean-up: connected components, floater removal (mesh_clean.hip) -------------------------------------------------------------------
+COMPONENT_ROUNDS_PER_CALL = 4          # rounds per sweep call = per host read of the round flags
+COMPONENT_MAX_ROUNDS = 4096            # a terminator for a bug, not a tuning value: propagation alone needs at most V rounds, real meshes single digits
+
+
+def _triangles_i32(triangles: torch.Tensor, n_vertices: int):
+    if triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise RuntimeError(f"triangles must be [T,3], got {tuple(triangles.shape)}")
+    V, T = int(n_vertices), triangles.shape[0]
+    if V < 0 or V > ISOSURFACE_MAX_VERTICES or T > ISOSURFACE_MAX_VERTICES:
+        raise RuntimeError(f"mesh of {V} vertices / {T} triangles: both counts must be in [0, 2^31)")
+    return triangles.contiguous(), V, T
+
+
+def mesh_components(triangles: torch.Tensor, n_vertices: int) -> dict:
+    """Connected components of an indexed mesh: triangles [T,3] int32 on the device over n_vertices vertices (a row with an index outside
+    [0, V) connects nothing and counts nowhere) -> {"labels" [V] int32, the smallest vertex index of each vertex's component;
+    "triangle_counts", "vertex_counts" [V] int32, nonzero at the roots (labels[r] == r) only; "counts" int32 [2] on the device = {roots,
+    roots with at least one triangle}; "rounds": the rounds it took, the confirming one included}.
+
+    The labels are a unique fixed point, reached by rounds of hook + jump launches in which no workgroup waits on another; the rounds are
+    issued 4 to a call, and the 4 round flags are read back after each call -- one small copy per batch, which also makes this call
+    uncapturable as a graph -- until a round reports that it lowered no label.  Deterministic: two calls give equal bits."""
+    tri, V, T = _triangles_i32(triangles, n_vertices)
+    p_tri = _lib.dev(tri, "triangles", torch.int32)
+    dev = tri.device
+    out = {k: torch.empty(V, device=dev, dtype=torch.int32) for k in ("labels", "triangle_counts", "vertex_counts")}
+    out["counts"] = torch.zeros(2, device=dev, dtype=torch.int32)
+    out["rounds"] = 0
+    if V == 0:
+        return out
+    L, st = _lib.lib(), _lib.stream()
+    p_lab = out["labels"].data_ptr()
+    _lib.check(L.sn_rm_mesh_components_init(V, p_lab, st), "sn_rm_mesh_components_init")
+    changed = torch.empty(COMPONENT_ROUNDS_PER_CALL, device=dev, dtype=torch.int32)
+    rounds = 0
+    while True:
+        if rounds >= COMPONENT_MAX_ROUNDS:
+            raise RuntimeError("mesh_components did not converge")
+        _lib.check(L.sn_rm_mesh_components_sweep(p_tri, T, V, p_lab, COMPONENT_ROUNDS_PER_CALL, changed.data_ptr(), st),
+                   "sn_rm_mesh_components_sweep")
+        flags = changed.tolist()
+        if flags[-1] == 0:                     # (an unchanged round is followed by unchanged rounds only)
+            rounds += next(i for i, f in enumerate(flags) if f == 0) + 1
+            break
+        rounds += COMPONENT_ROUNDS_PER_CALL
+    _lib.check(L.sn_rm_mesh_component_stats(p_tri, T, V, p_lab, out["triangle_counts"].data_ptr(), out["vertex_counts"].data_ptr(),
+                                            out["counts"].data_ptr(), st), "sn_rm_mesh_component_stats")
+    out["rounds"] = rounds
+    return out
+
+
+def mesh_filter_counts(triangles: torch.Tensor, n_vertices: int, components: dict, min_triangles: int = 0, keep_largest: int = 0):
+    """The first half of mesh_clean(): (counts, workspace) with counts = {V', T'} as an int32 [2] tensor on the device (nothing is read
+    back) and the workspace that mesh_filter_emit() takes -- the module's one "mesh_clean" buffer per device: the next call on that device
+    reuses it.  components: what mesh_components() returned for this mesh.  keep_largest = k > 0: the k-th largest key comes from one
+    torch.topk over the int64 keys on the device (the keys are unique, so it is deterministic) and stays there."""
+    tri, V, T = _triangles_i32(triangles, n_vertices)
+    dev = tri.device
+    counts = torch.zeros(2, device=dev, dtype=torch.int32)
+    L = _lib.lib()
+    need = int(L.sn_rm_mesh_clean_workspace_bytes(V, T))
+    if need == 0 and V:
+        raise RuntimeError("mesh_clean: " + L.sn_last_error().decode())
+    ws = _buffers.scratch("mesh_clean", dev, max(need, 16))
+    if V == 0:
+        return counts, ws
+    tc = components["triangle_counts"]
+    if keep_largest > 0:
+        keys = (tc.to(torch.int64) << 32) | (0xFFFFFFFF - torch.arange(V, device=dev, dtype=torch.int64))
+        min_key = torch.topk(keys, min(int(keep_largest), V)).values[-1:].contiguous()
+    else:
+        min_key = torch.zeros(1, device=dev, dtype=torch.int64)
+    _lib.check(L.sn_rm_mesh_filter_count(_lib.dev(tri, "triangles", torch.int32), T, V, _lib.dev(components["labels"], "labels", torch.int32),
+                                         _lib.dev(tc, "triangle_counts", torch.int32), min(int(min_triangles), 0xFFFFFFFF), min_key.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), counts.data_ptr(), _lib.stream()), "sn_rm_mesh_filter_count")
+    return counts, ws
+
+
+def mesh_filter_emit(triangles: torch.Tensor, vertices: torch.Tensor, normals, workspace: torch.Tensor, out_vertices: torch.Tensor, out_normals,
+                     out_triangles: torch.Tensor, source_vertex=None, cap_v: int | None = None, cap_t: int | None = None):
+    """The second half: fills out_vertices [>= cap_v, 3] f32, out_normals (same shape; iff normals is given), out_triangles [>= cap_t, 3]
+    int32 and source_vertex [>= cap_v] int32 (or None) from the workspace mesh_filter_counts() left.  Capacities below the counts truncate:
+    the stored prefix is the full result's."""
+    tri, V, T = _triangles_i32(triangles, vertices.shape[0])
+    cap_v = out_vertices.shape[0] if cap_v is None else int(cap_v)
+    cap_t = out_triangles.shape[0] if cap_t is None else int(cap_t)
+    if (cap_v > out_vertices.shape[0] or cap_t > out_triangles.shape[0] or (normals is not None and (out_normals is None or out_normals.shape[0] < cap_v))
+            or (source_vertex is not None and source_vertex.shape[0] < cap_v)):
+        raise ValueError("mesh_filter_emit: a capacity exceeds its buffer")
+    if (tuple(vertices.shape[1:]) != (3,) or tuple(out_vertices.shape[1:]) != (3,) or tuple(out_triangles.shape[1:]) != (3,)
+            or (normals is not None and (tuple(normals.shape) != tuple(vertices.shape) or tuple(out_normals.shape[1:]) != (3,)))):
+        raise RuntimeError("mesh_filter_emit: vertices, normals and triangles are [n,3]")
+    _lib.check(_lib.lib().sn_rm_mesh_filter_emit(_lib.dev(tri, "triangles", torch.int32), T, V, _lib.dev(vertices, "vertices"),
+                                                 _lib.dev(normals, "normals"), workspace.data_ptr(), workspace.numel(),
+                                                 _lib.dev(out_vertices, "out_vertices"), _lib.dev(out_normals if normals is not None else None, "out_normals"),
+                                                 _lib.dev(out_triangles, "out_triangles", torch.int32),
+                                                 _lib.dev(source_vertex, "source_vertex", torch.int32), cap_v, cap_t, _lib.stream()),
+               "sn_rm_mesh_filter_emit")
+
+
+def mesh_clean(mesh: dict, min_triangles: int = 0, keep_largest: int = 0, return_source: bool = False) -> dict:
+    """The mesh without its small connected components -- the floaters of a density field, the label noise of a gated one.  mesh: the keys
+    of isosurface() ("vertices" [V,3] f32, "normals" [V,3] f32 or None, "triangles" [T,3] int32; any indexed mesh on the device).  A component
+    is kept iff it has at least max(min_triangles, 1) valid triangles and -- keep_largest = k > 0 -- is among the k with the most triangles
+    (ties: the component with the lower smallest vertex index first).  Kept vertices and triangles keep their order; rows are copied bit for
+    bit and indices remapped.  return_source: also "source_vertex" [V'] int32, the old index of each kept vertex, to carry other attributes
+    across.  With both options 0 the input dict is returned as it is, with no launch.
+
+    mesh_components() reads its round flags back, and the two totals {V', T'} are read back once to allocate the result exactly: this call
+    cannot be captured as a graph.  Deterministic: two calls give equal bits."""
+    min_triangles, keep_largest = int(min_triangles), int(keep_largest)
+    if min_triangles < 0 or keep_largest < 0:
+        raise ValueError(f"mesh_clean: min_triangles = {min_triangles} and keep_largest = {keep_largest} must not be negative")
+    if min_triangles == 0 and keep_largest == 0:
+        return mesh
+    vertices, normals, triangles = _f32(mesh["vertices"]), mesh["normals"], mesh["triangles"]
+    normals = None if normals is None else _f32(normals)
+    V, dev = vertices.shape[0], vertices.device
+    comp = mesh_components(triangles, V)
+    counts, ws = mesh_filter_counts(triangles, V, comp, min_triangles, keep_largest)
+    nv, nt = (int(c) & 0xFFFFFFFF for c in counts.tolist())
+    out = {"vertices": torch.empty(nv, 3, device=dev, dtype=torch.float32),
+           "normals": None if normals is None else torch.empty(nv, 3, device=dev, dtype=torch.float32),
+           "triangles": torch.empty(nt, 3, device=dev, dtype=torch.int32)}
+    source = torch.empty(nv, device=dev, dtype=torch.int32) if return_source else None
+    if nv or nt:
+        mesh_filter_emit(triangles, vertices, normals, ws, out["vertices"], out["normals"], out["triangles"], source)
+    if return_source:
+        out["source_vertex"] = source
+    return out
