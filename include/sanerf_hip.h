@@ -998,6 +998,65 @@ int sn_rm_mesh_filter_emit(const int32_t *triangles, uint32_t T, uint32_t V, con
                            const void *workspace, size_t workspace_bytes, float *out_vertices, float *out_normals, int32_t *out_triangles,
                            int32_t *source_vertex, uint32_t cap_v, uint32_t cap_t, sn_stream_t stream);
 
+/* Mesh simplification (raymarching.mesh_simplify, NeRFRenderer.extract_mesh(simplify)): uniform vertex clustering of an indexed triangle mesh
+ * on the device (csrc/mesh_simplify.hip) -- one output vertex per occupied cell of a coarse lattice.  The definition is this project's;
+ * tests/mesh_simplify_ref.py restates it in numpy.  Every quantity below is an integer or the correctly rounded result of the stated
+ * operations, so the device's output EQUALS the restatement's: triangles, cluster map and counts exactly, vertices and normals bit for bit.
+ * (No operation was found whose rounding cannot be pinned: the fp64 division and square root are IEEE on gfx950.)
+ *
+ * Input: vertices [V,3] fp32, normals [V,3] fp32 or NULL, triangles [T,3] int32 -- any indexed mesh, not only the isosurface's -- and a
+ * lattice of cells: origin[3] (fp32, finite), cell[3] (fp32, > 0 and finite), dims[3] (uint32, each >= 1, product < 2^31); HOST arrays.
+ *   Cell of a vertex  per axis u = p - origin and s = u / cell in fp32 (IEEE division; two roundings, no contraction), i = (int)floor(s).  A
+ *                     vertex with a non-finite coordinate, or with some i outside [0, dims[a]), has NO cell: nothing is clamped, the caller
+ *                     chooses a lattice that covers the mesh.  key = (ix dims[1] + iy) dims[2] + iz.
+ *   Offset            q = (int)rint((s - (float)i) 65536.0f) in [0, 65536]; the subtraction and the product are exact in fp32.
+ *   Triangle classes  invalid: an index outside [0, V) or a corner without a cell (every index is range-tested before it is an address).
+ *                     degenerate: valid, and two corners share a cell.  duplicate: valid, not degenerate, and some triangle of LOWER index
+ *                     is valid, not degenerate and has the same SET of three keys (orientation is ignored).  kept: every other triangle.
+ *                     Kept triangles keep their relative order and their corner order (so their orientation).
+ *   Output vertices   a cell is used iff it is a corner of a kept triangle; output vertex j is the j-th used cell in increasing key order.
+ *                     Position per axis, in fp64, every operation rounded on its own, stored as fp32 with one rounding:
+ *                         origin + cell ((double)i + ((double)sum_q / (double)n) / 65536.0)
+ *                     sum_q (unsigned 64-bit) and n run over ALL input vertices of the cell, referenced by a triangle or not.
+ *   Output normals    iff normals != NULL.  Per component Q = (int64)rint(n_a 1048576.0f) where that product is finite and below 2^31 in
+ *                     magnitude, else 0 (a non-finite or absurd component contributes nothing, and no sum of < 2^31 terms can overflow);
+ *                     S = sum Q (signed 64-bit) over the cell's vertices; the result is S / sqrt((Sx Sx + Sy Sy) + Sz Sz) in fp64 ((double)S
+ *                     is the conversion's one rounding), no contraction, rounded once to fp32; (0,0,0) when S is zero.
+ *   Cluster map       vertex_cluster [V] int32 (optional): the output index of the vertex's cell, -1 without a cell or in an unused one.
+ *   Counts            {V', T'} as uint32 on the DEVICE.
+ * The sums are integers, so they depend on neither the order of accumulation, the launch shape nor the run.
+ *
+ * sn_rm_mesh_simplify_workspace_bytes(V, T, cells), cells = the product of dims: with W = ceil(cells / 32) words of cell bitmap and C = the
+ * smallest power of two >= max(2T, 1) slots of triangle table,
+ *     16 + up(4V) + 2 up(4T) + up(4 ceil(T / 1024)) + up(4C) + 2 up(4W) + up(4 ceil(W / 1024)) + 64V      (up = rounded up to 16)
+ * i.e. 68 bytes per vertex (a key and an 8 x 64-bit row of sums; output vertices can number at most V, so the count needs no host read
+ * before it accumulates), 16 to 24 bytes per triangle and 2 bits per cell.  0 (with a message) if V, T or cells >= 2^31.
+ * sn_rm_mesh_simplify_count: vertex keys; the valid, non-degenerate triangles enter an insert-only open-addressing table keyed by their key
+ * set, whose slots end at the set's lowest triangle index (atomicCAS to claim, atomicMin after comparing the occupant's key set; a slot's
+ * set never changes and slots never empty, so the result does not depend on the interleaving -- csrc/mesh_simplify.hip has the argument);
+ * kept = the slot holds my index; kept corners set their cells' bits; used cells and kept triangles are ranked by segment and scanned by
+ * one workgroup; the sums go into one row per OUTPUT vertex by 64-bit integer atomic adds, aggregated over runs of lanes of a wave.
+ * counts[0..1] = {V', T'} -- six launches behind two memsets, no workgroup waits on another, no probe loop longer than the table.
+ * sn_rm_mesh_simplify_emit: out_vertices [cap_v,3], out_normals [cap_v,3] (iff normals != NULL), out_triangles [cap_t,3], vertex_cluster
+ * [V] or NULL, from the workspace the count left and `triangles` (`vertices` is not read, `normals` only says whether normals exist).
+ * Every store is guarded by the capacities and every index and key is range-tested again: triangles that changed between the two calls,
+ * or a capacity that is too small, truncate or misplace the output (a corner that no longer has a used cell is emitted as -1) and never
+ * write out of bounds; a capacity below the count stores the prefix of the full result.  workspace: 16-byte aligned.
+ * Both entries return SN_OK without touching a pointer when V == 0, the emit also with both capacities 0 and no cluster map.  triangles
+ * may be NULL when T == 0.  Errors before any launch: SN_ERR_INVALID (NULL pointer, misaligned workspace, a cell that is not positive and
+ * finite, a non-finite origin, a zero dim), SN_ERR_UNSUPPORTED (V, T or cells >= 2^31), SN_ERR_WORKSPACE.
+ * Nothing is placed by an atomic -- atomics compute minima, sets and integer sums only -- so the output is identical from run to run.
+ * Not promised: manifoldness (clustering can pinch a thin wall into edges shared by more than two triangles), and nothing here weighs the
+ * error it makes: this is not quadric-error decimation. */
+size_t sn_rm_mesh_simplify_workspace_bytes(uint32_t V, uint32_t T, uint32_t cells);
+int sn_rm_mesh_simplify_count(const float *vertices, const float *normals, const int32_t *triangles, uint32_t V, uint32_t T,
+                              const float *origin, const float *cell, const uint32_t *dims, void *workspace, size_t workspace_bytes,
+                              uint32_t *counts, sn_stream_t stream);
+int sn_rm_mesh_simplify_emit(const float *vertices, const float *normals, const int32_t *triangles, uint32_t V, uint32_t T,
+                             const float *origin, const float *cell, const uint32_t *dims, const void *workspace, size_t workspace_bytes,
+                             float *out_vertices, float *out_normals, int32_t *out_triangles, int32_t *vertex_cluster, uint32_t cap_v,
+                             uint32_t cap_t, sn_stream_t stream);
+
 /* Training-time forward of a bias-free perceptron with 256-wide hidden layers and no skip connections (nerf/network.py:31-66: F.linear +
  * activation per layer; the per-sample mask head in training, network.py:118-123, trainer.py:401-428) in ONE kernel, true fp32 products
  * and accumulation on the matrix cores (v_mfma_f32_32x32x2_f32; results differ from a BLAS GEMM only by summation order).

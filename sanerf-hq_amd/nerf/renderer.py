@@ -536,20 +536,33 @@ class NeRFRenderer(nn.Module):
         return volume.reshape(res)
 
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, instance_ids=None, invert=False, normals=True,
-                     min_component_triangles=0, keep_largest=0):
+                     min_component_triangles=0, keep_largest=0, simplify=0):
         """The surface sigma = threshold (default self.density_thresh) of density_volume(resolution, aabb, instance_ids, invert) by marching
         tetrahedra on the device: {"vertices" [V,3] f32, "normals" [V,3] f32 or None, "triangles" [T,3] int32} in world coordinates -- the
         whole scene, or with instance_ids the object alone (invert: the scene without it).  The size of the result depends on the data
         (raymarching.isosurface reads two totals back once).  nerf.utils.save_mesh writes it as a PLY file.
 
         min_component_triangles, keep_largest (both 0: everything above the threshold, floaters included): the mesh then goes through
-        raymarching.mesh_clean, which keeps the connected components of at least that many triangles and / or the k largest."""
+        raymarching.mesh_clean, which keeps the connected components of at least that many triangles and / or the k largest.
+
+        simplify = k >= 1 (fractional allowed; 0: off, and nothing is launched for it): after the clean-up the mesh goes through
+        raymarching.mesh_simplify -- uniform vertex clustering -- with cells of k lattice steps that are aligned with the extraction's own
+        lattice (cell = k step, origin = lattice origin - step / 2, dims covering the lattice), so the result does not depend on where
+        the object sits in its bounding box.  Clustering does not preserve manifoldness."""
+        simplify = float(simplify)
+        if simplify != 0.0 and not (1.0 <= simplify < float("inf")):
+            raise ValueError(f"extract_mesh: simplify = {simplify} must be 0 (off) or at least 1 lattice step")
         res, origin, step = self._lattice(resolution, aabb)
         volume = self.density_volume(res, aabb, instance_ids, invert)
         iso = float(self.density_thresh if threshold is None else threshold)
         mesh = rm.isosurface(volume, iso, origin, step, normals=normals)
         if min_component_triangles or keep_largest:
             mesh = rm.mesh_clean(mesh, min_triangles=min_component_triangles, keep_largest=keep_largest)
+        if simplify:
+            import numpy as np
+            mesh = rm.mesh_simplify(mesh, cell=[float(np.float32(simplify * step[a])) for a in range(3)],
+                                    origin=[float(np.float32(origin[a]) - np.float32(0.5) * np.float32(step[a])) for a in range(3)],
+                                    dims=[int((res[a] - 0.5) // simplify) + 2 for a in range(3)])     # one spare cell for the rounding of the last vertex
         return mesh
 
     # ---------------------------------------------------------------------------------------

@@ -1,12 +1,14 @@
-"""Geometry export (mesh.hip, mesh_clean.hip): lattice positions, marching tetrahedra on a density lattice, and the clean-up of the mesh.
+"""Geometry export (mesh.hip, mesh_clean.hip, mesh_simplify.hip): lattice positions, marching tetrahedra on a density lattice, the clean-up
+of the mesh and its simplification.
 
     lattice_points     positions of a window of the vertices of an nx x ny x nz lattice, optionally contracted -- no meshgrid per chunk
     isosurface         volume [nx,ny,nz], iso -> {"vertices" [V,3], "normals" [V,3] or None, "triangles" [T,3] int32}
     mesh_components    triangles [T,3], V -> labels, triangle and vertex counts per connected component
     mesh_clean         a mesh without its small components (floaters, label noise): by triangle count and / or the largest k
+    mesh_simplify      uniform vertex clustering: one vertex per occupied cell of a coarse lattice
 include/sanerf_hip.h states the definitions (inside test, edge slots, Kuhn tetrahedra, orientation from the table, both orders, normals;
-valid triangles, components, keys, selection, the filtered mesh's order); tests/mesh_ref.py and tests/mesh_clean_ref.py restate them in
-numpy."""
+valid triangles, components, keys, selection, the filtered mesh's order; cells, triangle classes, the integer sums); tests/mesh_ref.py,
+tests/mesh_clean_ref.py and tests/mesh_simplify_ref.py restate them in numpy."""
 from __future__ import annotations
 
 from typing import Sequence
@@ -234,4 +236,125 @@ def mesh_clean(mesh: dict, min_triangles: int = 0, keep_largest: int = 0, return
         mesh_filter_emit(triangles, vertices, normals, ws, out["vertices"], out["normals"], out["triangles"], source)
     if return_source:
         out["source_vertex"] = source
+    return out
+
+
+# ---- simplification: uniform vertex clustering (mesh_simplify.hip) ------------------------------------------------------------------------
+def _cell_lattice(origin, cell, dims):
+    origin, cell, dims = _triple(origin, "origin"), _triple(cell, "cell"), _triple(dims, "dims", int)
+    cells = dims[0] * dims[1] * dims[2]
+    if min(dims) < 1 or cells > ISOSURFACE_MAX_VERTICES:
+        raise ValueError(f"mesh_simplify: dims = {dims}: every entry at least 1 and the product below 2^31")
+    return _lib.host_f32(origin), _lib.host_f32(cell), _lib.host_i32(dims), cells
+
+
+def _mesh_f32(vertices, normals):
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or (normals is not None and tuple(normals.shape) != tuple(vertices.shape)):
+        raise RuntimeError("mesh_simplify: vertices and normals are [V,3]")
+    return _lib.dev(vertices, "vertices"), _lib.dev(normals, "normals")
+
+
+def mesh_simplify_counts(vertices: torch.Tensor, normals, triangles: torch.Tensor, origin, cell, dims):
+    """The first half of mesh_simplify(): (counts, workspace) with counts = {V', T'} as an int32 [2] tensor on the device (nothing is read
+    back) and the workspace that mesh_simplify_emit() takes -- the module's one "mesh_simplify" buffer per device: the next call on that
+    device reuses it.  origin, cell: 3 floats each; dims: 3 ints, the cells per axis (a vertex outside them has no cell)."""
+    tri, V, T = _triangles_i32(triangles, vertices.shape[0])
+    p_v, p_n = _mesh_f32(vertices, normals)
+    h_origin, h_cell, h_dims, cells = _cell_lattice(origin, cell, dims)
+    dev = vertices.device
+    counts = torch.zeros(2, device=dev, dtype=torch.int32)
+    L = _lib.lib()
+    need = int(L.sn_rm_mesh_simplify_workspace_bytes(V, T, cells))
+    if need == 0:
+        raise RuntimeError("mesh_simplify: " + L.sn_last_error().decode())
+    ws = _buffers.scratch("mesh_simplify", dev, need)
+    _lib.check(L.sn_rm_mesh_simplify_count(p_v, p_n, _lib.dev(tri, "triangles", torch.int32), V, T, h_origin, h_cell, h_dims, ws.data_ptr(),
+                                           ws.numel(), counts.data_ptr(), _lib.stream()), "sn_rm_mesh_simplify_count")
+    return counts, ws
+
+
+def mesh_simplify_emit(vertices: torch.Tensor, normals, triangles: torch.Tensor, origin, cell, dims, workspace: torch.Tensor,
+                       out_vertices: torch.Tensor, out_normals, out_triangles: torch.Tensor, vertex_cluster=None, cap_v: int | None = None,
+                       cap_t: int | None = None):
+    """The second half: fills out_vertices [>= cap_v, 3] f32, out_normals (same shape; iff normals is given), out_triangles [>= cap_t, 3]
+    int32 and vertex_cluster [V] int32 (or None) from the workspace mesh_simplify_counts() left for the same mesh and lattice.  Capacities
+    below the counts truncate: the stored prefix is the full result's."""
+    tri, V, T = _triangles_i32(triangles, vertices.shape[0])
+    p_v, p_n = _mesh_f32(vertices, normals)
+    h_origin, h_cell, h_dims, _ = _cell_lattice(origin, cell, dims)
+    cap_v = out_vertices.shape[0] if cap_v is None else int(cap_v)
+    cap_t = out_triangles.shape[0] if cap_t is None else int(cap_t)
+    if (cap_v > out_vertices.shape[0] or cap_t > out_triangles.shape[0] or (normals is not None and (out_normals is None or out_normals.shape[0] < cap_v))
+            or (vertex_cluster is not None and vertex_cluster.shape[0] < V)):
+        raise ValueError("mesh_simplify_emit: a capacity exceeds its buffer")
+    if (tuple(out_vertices.shape[1:]) != (3,) or tuple(out_triangles.shape[1:]) != (3,)
+            or (normals is not None and tuple(out_normals.shape[1:]) != (3,))):
+        raise RuntimeError("mesh_simplify_emit: vertices, normals and triangles are [n,3]")
+    _lib.check(_lib.lib().sn_rm_mesh_simplify_emit(p_v, p_n, _lib.dev(tri, "triangles", torch.int32), V, T, h_origin, h_cell, h_dims,
+                                                   workspace.data_ptr(), workspace.numel(), _lib.dev(out_vertices, "out_vertices"),
+                                                   _lib.dev(out_normals if normals is not None else None, "out_normals"),
+                                                   _lib.dev(out_triangles, "out_triangles", torch.int32),
+                                                   _lib.dev(vertex_cluster, "vertex_cluster", torch.int32), cap_v, cap_t, _lib.stream()),
+               "sn_rm_mesh_simplify_emit")
+
+
+def _covering_lattice(vertices: torch.Tensor, cell):
+    """(origin, dims) of the cell lattice over the bounding box of the finite vertices, the lower corner pulled back by half a cell; None
+    without a finite vertex.  One aminmax on the device, its six values read back."""
+    import numpy as np
+    finite = vertices[torch.isfinite(vertices).all(dim=1)]
+    if finite.shape[0] == 0:
+        return None
+    lo, hi = torch.aminmax(finite, dim=0)
+    box = torch.stack([lo, hi]).tolist()
+    origin, dims = [], []
+    for a in range(3):
+        o = np.float32(np.float32(box[0][a]) - np.float32(0.5) * np.float32(cell[a]))
+        if not np.isfinite(o):
+            raise ValueError("mesh_simplify: the bounding box overflows fp32")
+        origin.append(float(o))
+        dims.append(int(np.floor((float(np.float32(box[1][a])) - float(o)) / float(np.float32(cell[a])))) + 2)    # one spare cell for the fp32 rounding of s
+    return origin, dims
+
+
+def mesh_simplify(mesh: dict, cell, origin=None, dims=None, return_cluster: bool = False) -> dict:
+    """Uniform vertex clustering: the mesh with one vertex per occupied cell of a lattice of `cell`-sized boxes (a float or a triple) -- the
+    triangle budget of a lattice-dense isosurface brought down on the device.  mesh: the keys of isosurface() ("vertices" [V,3] f32,
+    "normals" [V,3] f32 or None, "triangles" [T,3] int32; any indexed mesh on the device); the result has the same keys.  A vertex moves
+    to the mean of ALL input vertices of its cell (normals: the normalised sum); a triangle whose corners fall into fewer than three cells
+    is dropped, and so is every triangle whose set of three cells an earlier triangle already has; the others keep their order and
+    orientation, and only cells they touch become vertices, in cell-key order.  include/sanerf_hip.h has the definition, exact to the
+    bit; tests/mesh_simplify_ref.py restates it.  return_cluster: also "vertex_cluster" [V] int32, the new index of each old vertex (-1:
+    none), to carry other attributes across.
+
+    origin, dims: the cell lattice (cell i covers origin + [i, i + 1) cell per axis); a vertex outside it has no cell and its triangles are
+    dropped.  With both None the lattice covers the bounding box of the finite vertices, its lower corner pulled back by half a cell: one
+    torch.aminmax on the device, read back.  Not promised: manifoldness, and no error metric is weighed -- this is not quadric decimation.
+
+    The two totals {V', T'} are read back once to allocate the result exactly (as isosurface and mesh_clean do): this call cannot be
+    captured as a graph.  Deterministic, and independent of the order of the input vertices: the sums are integers."""
+    cell = _triple(cell, "cell") if hasattr(cell, "__len__") else [float(cell)] * 3
+    if not all(c > 0.0 and c < float("inf") for c in cell):
+        raise ValueError(f"mesh_simplify: cell = {cell} must be positive and finite")
+    if (origin is None) != (dims is None):
+        raise ValueError("mesh_simplify: give origin and dims together, or neither")
+    vertices, normals, triangles = _f32(mesh["vertices"]), mesh["normals"], mesh["triangles"]
+    normals = None if normals is None else _f32(normals)
+    _triangles_i32(triangles, vertices.shape[0])
+    _lib.dev(vertices, "vertices")
+    V, dev = vertices.shape[0], vertices.device
+    lattice = (origin, dims) if origin is not None else (_covering_lattice(vertices, cell) if V else None)
+    nv = nt = 0
+    if V and lattice is not None:
+        origin, dims = lattice
+        counts, ws = mesh_simplify_counts(vertices, normals, triangles, origin, cell, dims)
+        nv, nt = (int(c) & 0xFFFFFFFF for c in counts.tolist())
+    out = {"vertices": torch.empty(nv, 3, device=dev, dtype=torch.float32),
+           "normals": None if normals is None else torch.empty(nv, 3, device=dev, dtype=torch.float32),
+           "triangles": torch.empty(nt, 3, device=dev, dtype=torch.int32)}
+    cluster = torch.full((V,), -1, device=dev, dtype=torch.int32) if return_cluster else None
+    if nv or nt:
+        mesh_simplify_emit(vertices, normals, triangles, origin, cell, dims, ws, out["vertices"], out["normals"], out["triangles"], cluster)
+    if return_cluster:
+        out["vertex_cluster"] = cluster
     return out
