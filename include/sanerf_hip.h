@@ -890,6 +890,41 @@ int sn_rm_object_composite(const uint8_t *labels, const float *sigmas, const flo
                            uint32_t N, uint32_t T, uint32_t keep_mask, int32_t invert, int32_t last_sample_opaque, float *weights_sum,
                            float *depth, float *f_image, float *weights, sn_stream_t stream);
 
+/* Vertex colours and instance labels of an exported mesh (NeRFRenderer.vertex_attributes, extract_mesh(vertex_colors, vertex_labels)):
+ * surface probes.  The colour head is deferred -- pixel = sigmoid(view_mlp([sum w geo | SH4(d)])) -- so a vertex is shaded the way a pixel
+ * is: by a short ray that enters the surface head-on, composited and normalised.  (The project's own definition; the reference has none.
+ * tests/mesh_attr_ref64.py states it in fp64.)
+ *
+ * Per vertex: a position v and a mesh normal n that points out of the inside.  K in {4, 8, 16, 32} probe samples, step h (finite, > 0).
+ *   1. Direction   d = -n / |n|; (0, 0, -1) where |n| is 0 or not finite (a NaN or inf component included).  In fp32: m = the largest
+ *                  |n_a|, s = n / m, len = sqrt((s_x s_x + s_y s_y) + s_z s_z), d_a = -(s_a / len) -- no square overflows or vanishes.
+ *   2. Positions   t_i = (i + 1/2 - K/2) h for i = 0 .. K-1 (the factor is exact: one rounding); p_i = v + t_i d per axis, the product and
+ *                  the sum rounded separately, as sn_rm_lattice_points; contract != 0: then through sn_rm_contract's arithmetic.  The probe
+ *                  starts outside (t < 0) and ends inside.
+ *   3. Queries     sigma_i, geo_i in R^15 from the main field at p_i, label_i from the mask head (sn_rm_mask_point_labels) -- the
+ *                  existing operators.  A label >= 32 (255 = "not evaluated") is in no set.
+ *   4. Gate        g_i = (label_i in S) xor invert; g_i = true when no labels are given.  y_i = g_i ? h sigma_i : 0 -- a select.
+ *   5. Weights     w_i = (1 - exp(-y_i)) exp(-sum_{j<i} y_j), the prefix summed in fp64 in sample order, NaN -> 0: exactly
+ *                  sn_rm_object_composite's weight.  There is no opaque last sample.
+ *   6. Coverage    W = sum w_i;  G = sum w_i geo_i.  Where W >= 2^-126: g = G / W.  Otherwise (nothing kept, or empty space) the fallback
+ *                  g = (sum_i geo_i) (1 / K) over all K samples, ungated, in sample order.
+ *   7. Colour      f = [g | SH4(d / |d|)], 31 values; colour = sigmoid(view_mlp(f)) -- the per-ray head, not part of these entries.
+ *   8. Label vote  (only with labels) vote_l = sum_{i: label_i = l} w_i for l < 32, in fp32 in sample order; the vertex label is the lowest
+ *                  l attaining the maximum vote if that maximum is > 0, else 255.
+ * The order of every sum is a function of K alone: a vertex's result does not depend on V, on the launch grid or on chunking.
+ *
+ * sn_rm_vertex_probe_points: steps 1-2 for the vertices first .. first + count - 1 of vertices / normals [V_total,3] -> xyz [count,K,3],
+ * dirs [count,3].  count == 0 returns SN_OK without touching a pointer; count K < 2^32.
+ * sn_rm_vertex_probe_composite: steps 4-8 but the perceptron, in one launch.  labels [V,K] uint8 or NULL (no gate, no vote), sigmas [V,K],
+ * geo_feat [V,K,15] (16-byte aligned), dirs [V,3] -> f [V,31], coverage [V] and, if != NULL (needs labels), vertex_label [V] uint8.
+ * 16 lanes per vertex; a workgroup reads the geometry of its 16 vertices as one contiguous block.  V == 0 returns SN_OK; V < 2^28.
+ * Both answer SN_ERR_UNSUPPORTED (with a message) for a K outside the set and SN_ERR_INVALID for h.  Deterministic. */
+int sn_rm_vertex_probe_points(const float *vertices, const float *normals, uint32_t V_total, uint32_t first, uint32_t count, uint32_t K,
+                              float h, int32_t contract, float *xyz, float *dirs, sn_stream_t stream);
+int sn_rm_vertex_probe_composite(const uint8_t *labels, const float *sigmas, const float *geo_feat, const float *dirs, uint32_t V, uint32_t K,
+                                 float h, uint32_t keep_mask, int32_t invert, float *f, float *coverage, uint8_t *vertex_label,
+                                 sn_stream_t stream);
+
 /* Geometry export (NeRFRenderer.density_volume / extract_mesh): the object, or the whole scene, taken out of the field as a triangle mesh.
  * (The reference offers --render_mesh / --density_thresh, main.py:183-185, imports mcubes and trimesh, nerf/renderer.py, and calls neither.
  * The definition below is this project's; tests/mesh_ref.py restates it operation for operation, and topology pins the restatement.)

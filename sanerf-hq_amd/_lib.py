@@ -189,6 +189,8 @@ _SIGNATURES = {
     "sn_rm_mask_head": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _f32, C.POINTER(GridDesc), C.POINTER(MlpDesc), _vp, _vp, C.c_size_t, _vp]),
     "sn_rm_mask_point_labels": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _f32, C.POINTER(GridDesc), C.POINTER(MlpDesc), _vp, _vp, _vp, C.c_size_t, _vp]),
     "sn_rm_object_composite": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "sn_rm_vertex_probe_points": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _i32, _vp, _vp, _vp]),
+    "sn_rm_vertex_probe_composite": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _u32, _i32, _vp, _vp, _vp, _vp]),
     "sn_rm_lattice_points": (_int, [C.POINTER(_f32), C.POINTER(_f32), _u32, _u32, _u32, _u32, _u32, _i32, _vp, _vp]),
     "sn_rm_isosurface_workspace_bytes": (C.c_size_t, [_u32, _u32, _u32]),
     "sn_rm_isosurface_count": (_int, [_vp, _u32, _u32, _u32, _f32, _vp, C.c_size_t, _vp, _vp]),

@@ -535,8 +535,54 @@ class NeRFRenderer(nn.Module):
                 volume[first:first + count] = sigma
         return volume.reshape(res)
 
+    def vertex_attributes(self, mesh, probe_step, samples=8, instance_ids=None, invert=False, labels=False, chunk=1 << 17):
+        """Colour, coverage and instance label of every vertex of a mesh (the keys of extract_mesh; needs mesh["normals"]): each vertex is
+        shaded the way a pixel is, by a short ray of `samples` = K in {4, 8, 16, 32} samples, `probe_step` = h apart, that enters the
+        surface head-on (d = -normal) and is composited and normalised -- include/sanerf_hip.h states the definition,
+        tests/mesh_attr_ref64.py its fp64 twin.  With instance_ids only the samples whose mask-field label is in the set (xor invert) are
+        integrated; with labels=True each vertex also gets the id that holds most of its weight (255: none).
+
+        Returns {"colors" [V,3] f32 in [0,1], "coverage" [V] f32 (the probe's alpha: near 0 where nothing kept was hit, and the colour is
+        then that of the plain mean of the probe's geometry), "labels" [V] uint8 or None}.  Works in chunks of `chunk` vertices -- probe
+        points -> density -> _point_labels (when asked for) -> composite -> colour head; the result does not depend on chunk.  No-grad
+        only; nothing is read back to the host."""
+        self._inference_only("vertex_attributes")
+        if mesh.get("normals") is None:
+            raise ValueError("vertex_attributes: the probes need mesh['normals'] (extract_mesh(normals=True))")
+        K = int(samples)
+        h = float(probe_step)
+        if K not in rm.PROBE_SAMPLES:
+            raise ValueError(f"vertex_attributes: samples = {K} must be one of {rm.PROBE_SAMPLES}")
+        if not (0.0 < h < float("inf")):
+            raise ValueError(f"vertex_attributes: probe_step = {h} must be positive and finite")
+        gated = instance_ids is not None
+        if (gated or labels) and not self.opt.with_mask:
+            raise RuntimeError("vertex_attributes: labels and instance_ids need the mask field (opt.with_mask)")
+        keep = rm.keep_mask_of(instance_ids) if gated else 0xFFFFFFFF
+        vertices, normals = mesh["vertices"], mesh["normals"]
+        V, device = vertices.shape[0], vertices.device
+        chunk = max(int(chunk), 1)
+        colors = torch.empty(V, 3, device=device, dtype=torch.float32)
+        coverage = torch.empty(V, device=device, dtype=torch.float32)
+        vlabels = torch.empty(V, device=device, dtype=torch.uint8) if labels else None
+        with torch.no_grad():
+            for first in range(0, V, chunk):
+                count = min(chunk, V - first)
+                xyz, dirs = rm.vertex_probe_points(vertices, normals, K, h, first, count, contract=bool(self.opt.contract))
+                out = self.density(xyz.reshape(-1, 3))
+                sigma = out["sigma"].reshape(count, K).float()
+                geo = out["geo_feat"].reshape(count, K, -1).contiguous()
+                lab = self._point_labels(sigma, xyz, geo) if (gated or labels) else None
+                f, cov, vl = rm.vertex_probe_composite(sigma, geo, dirs, h, lab, keep, gated and bool(invert), want_labels=bool(labels))
+                colors[first:first + count] = self.view_mlp.forward_sigmoid_bg(f, torch.ones_like(cov), 0.0)
+                coverage[first:first + count] = cov
+                if labels:
+                    vlabels[first:first + count] = vl
+        return {"colors": colors, "coverage": coverage, "labels": vlabels}
+
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, instance_ids=None, invert=False, normals=True,
-                     min_component_triangles=0, keep_largest=0, simplify=0):
+                     min_component_triangles=0, keep_largest=0, simplify=0, vertex_colors=False, vertex_labels=False, probe_samples=8,
+                     probe_step=0.5):
         """The surface sigma = threshold (default self.density_thresh) of density_volume(resolution, aabb, instance_ids, invert) by marching
         tetrahedra on the device: {"vertices" [V,3] f32, "normals" [V,3] f32 or None, "triangles" [T,3] int32} in world coordinates -- the
         whole scene, or with instance_ids the object alone (invert: the scene without it).  The size of the result depends on the data
@@ -548,11 +594,27 @@ class NeRFRenderer(nn.Module):
         simplify = k >= 1 (fractional allowed; 0: off, and nothing is launched for it): after the clean-up the mesh goes through
         raymarching.mesh_simplify -- uniform vertex clustering -- with cells of k lattice steps that are aligned with the extraction's own
         lattice (cell = k step, origin = lattice origin - step / 2, dims covering the lattice), so the result does not depend on where
-        the object sits in its bounding box.  Clustering does not preserve manifoldness."""
+        the object sits in its bounding box.  Clustering does not preserve manifoldness.
+
+        vertex_colors, vertex_labels (both False: nothing is launched for them and the dict has the three keys above; either needs
+        normals=True): the FINAL mesh -- after clean-up and simplification -- goes through vertex_attributes with probe_samples samples
+        probe_step lattice steps apart (h = probe_step min(step)) and the same instance_ids / invert, and the dict gains "colors" [V,3]
+        and "coverage" [V] (vertex_colors) and "labels" [V] uint8 (vertex_labels).  save_mesh writes both."""
         simplify = float(simplify)
         if simplify != 0.0 and not (1.0 <= simplify < float("inf")):
             raise ValueError(f"extract_mesh: simplify = {simplify} must be 0 (off) or at least 1 lattice step")
         res, origin, step = self._lattice(resolution, aabb)
+        attributes = bool(vertex_colors) or bool(vertex_labels)
+        if attributes:
+            if not normals:
+                raise ValueError("extract_mesh: vertex_colors / vertex_labels need normals=True (the probes enter along the normal)")
+            if int(probe_samples) not in rm.PROBE_SAMPLES:
+                raise ValueError(f"extract_mesh: probe_samples = {probe_samples} must be one of {rm.PROBE_SAMPLES}")
+            probe_h = float(probe_step) * min(abs(v) for v in step)
+            if not (0.0 < probe_h < float("inf")):
+                raise ValueError(f"extract_mesh: probe_step = {probe_step} must be positive and finite")
+            if vertex_labels and not self.opt.with_mask:
+                raise RuntimeError("extract_mesh: vertex_labels need the mask field (opt.with_mask)")
         volume = self.density_volume(res, aabb, instance_ids, invert)
         iso = float(self.density_thresh if threshold is None else threshold)
         mesh = rm.isosurface(volume, iso, origin, step, normals=normals)
@@ -563,6 +625,14 @@ class NeRFRenderer(nn.Module):
             mesh = rm.mesh_simplify(mesh, cell=[float(np.float32(simplify * step[a])) for a in range(3)],
                                     origin=[float(np.float32(origin[a]) - np.float32(0.5) * np.float32(step[a])) for a in range(3)],
                                     dims=[int((res[a] - 0.5) // simplify) + 2 for a in range(3)])     # one spare cell for the rounding of the last vertex
+        if attributes:
+            attr = self.vertex_attributes(mesh, probe_h, samples=int(probe_samples), instance_ids=instance_ids, invert=invert,
+                                          labels=bool(vertex_labels))
+            mesh = dict(mesh)
+            if vertex_colors:
+                mesh["colors"], mesh["coverage"] = attr["colors"], attr["coverage"]
+            if vertex_labels:
+                mesh["labels"] = attr["labels"]
         return mesh
 
     # ---------------------------------------------------------------------------------------

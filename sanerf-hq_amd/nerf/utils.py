@@ -314,9 +314,11 @@ def freeze_loaded_parameters(model, model_dict):
 # ---------------------------------------------------------------------------------------------
 # geometry export: what NeRFRenderer.extract_mesh returns, as a file
 # ---------------------------------------------------------------------------------------------
-def save_mesh(path, vertices, triangles, normals=None):
+def save_mesh(path, vertices, triangles, normals=None, colors=None, labels=None):
     """Write a triangle mesh as a binary little-endian PLY file: vertices [V,3] (float x y z, and float nx ny nz with normals [V,3]) and
-    triangles [T,3] (uchar 3 + three int32 vertex indices per face).  Tensors or arrays; host side, numpy only."""
+    triangles [T,3] (uchar 3 + three int32 vertex indices per face).  colors [V,3]: uchar red green blue per vertex -- uint8 values as
+    they are, floats as clip(rint(255 c), 0, 255) with NaN -> 0; labels [V]: uchar label.  Without both the file is what it was before
+    they existed, byte for byte.  Tensors or arrays; host side, numpy only."""
     def host(a, dtype, what):
         a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
         if a.ndim != 2 or a.shape[1] != 3:
@@ -330,6 +332,20 @@ def save_mesh(path, vertices, triangles, normals=None):
         if n.shape[0] != v.shape[0]:
             raise ValueError(f"save_mesh: {n.shape[0]} normals for {v.shape[0]} vertices")
         fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    rgb = lab = None
+    if colors is not None:
+        rgb = colors.detach().cpu().numpy() if torch.is_tensor(colors) else np.asarray(colors)
+        if rgb.shape != (v.shape[0], 3):
+            raise ValueError(f"save_mesh: colors must be [{v.shape[0]},3], got {tuple(rgb.shape)}")
+        if rgb.dtype != np.uint8:
+            rgb = rgb.astype(np.float64)
+            rgb = np.clip(np.rint(255.0 * np.where(np.isnan(rgb), 0.0, rgb)), 0, 255).astype(np.uint8)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    if labels is not None:
+        lab = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+        if lab.shape != (v.shape[0],) or lab.dtype.kind not in "ui" or (lab.size and (lab.min() < 0 or lab.max() > 255)):
+            raise ValueError(f"save_mesh: labels must be [{v.shape[0]}] integers in 0..255")
+        fields += [("label", "u1")]
     if t.size and (t.min() < 0 or t.max() >= v.shape[0]):
         raise ValueError("save_mesh: a triangle index is outside the vertices")
     vert = np.empty(v.shape[0], dtype=fields)
@@ -337,11 +353,16 @@ def save_mesh(path, vertices, triangles, normals=None):
         vert[name] = v[:, i]
         if normals is not None:
             vert["n" + name] = n[:, i]
+    if rgb is not None:
+        for i, name in enumerate(("red", "green", "blue")):
+            vert[name] = rgb[:, i]
+    if lab is not None:
+        vert["label"] = lab
     face = np.empty(t.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
     face["n"] = 3
     face["v"] = t
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
-    header += [f"property float {name}" for name, _ in fields]
+    header += [f"property {'uchar' if kind == 'u1' else 'float'} {name}" for name, kind in fields]
     header += [f"element face {t.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     with open(path, "wb") as fh:
         fh.write(("\n".join(header) + "\n").encode("ascii"))

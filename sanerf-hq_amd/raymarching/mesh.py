@@ -1,11 +1,13 @@
-"""Geometry export (mesh.hip, mesh_clean.hip, mesh_simplify.hip): lattice positions, marching tetrahedra on a density lattice, the clean-up
-of the mesh and its simplification.
+"""Geometry export (mesh.hip, mesh_clean.hip, mesh_simplify.hip, mesh_attr.hip): lattice positions, marching tetrahedra on a density lattice,
+the clean-up of the mesh, its simplification, and the surface probes that give its vertices a colour and an instance label.
 
     lattice_points     positions of a window of the vertices of an nx x ny x nz lattice, optionally contracted -- no meshgrid per chunk
     isosurface         volume [nx,ny,nz], iso -> {"vertices" [V,3], "normals" [V,3] or None, "triangles" [T,3] int32}
     mesh_components    triangles [T,3], V -> labels, triangle and vertex counts per connected component
     mesh_clean         a mesh without its small components (floaters, label noise): by triangle count and / or the largest k
     mesh_simplify      uniform vertex clustering: one vertex per occupied cell of a coarse lattice
+    vertex_probe_points, vertex_probe_composite   K samples of a short ray into the surface at every vertex; their gated re-integration
+                       into the colour head's input, the coverage and the voted label (tests/mesh_attr_ref64.py states it in fp64)
 include/sanerf_hip.h states the definitions (inside test, edge slots, Kuhn tetrahedra, orientation from the table, both orders, normals;
 valid triangles, components, keys, selection, the filtered mesh's order; cells, triangle classes, the integer sums); tests/mesh_ref.py,
 tests/mesh_clean_ref.py and tests/mesh_simplify_ref.py restate them in numpy."""
@@ -358,3 +360,79 @@ def mesh_simplify(mesh: dict, cell, origin=None, dims=None, return_cluster: bool
     if return_cluster:
         out["vertex_cluster"] = cluster
     return out
+
+
+# ---- vertex attributes: surface probes (mesh_attr.hip) -------------------------------------------------------------------------------------
+PROBE_SAMPLES = (4, 8, 16, 32)         # K of a vertex probe: what the label kernel takes as samples per row
+PROBE_GEO = 15                         # geometry channels per sample (network.py:94)
+
+
+def _probe_args(K, h, what):
+    K, h = int(K), float(h)
+    if K not in PROBE_SAMPLES:
+        raise ValueError(f"{what}: samples = {K} must be one of {PROBE_SAMPLES}")
+    if not (0.0 < h < float("inf")) or not (0.0 < float(torch.tensor(h, dtype=torch.float32)) < float("inf")):
+        raise ValueError(f"{what}: the probe step h = {h} must be positive and finite in fp32")
+    return K, h
+
+
+def vertex_probe_points(vertices: torch.Tensor, normals: torch.Tensor, samples: int, h: float, first: int = 0, count: int | None = None,
+                        contract: bool = False):
+    """(xyz [count,K,3], dirs [count,3]) of the surface probes of the vertices first .. first + count - 1 (default: to the end) of a mesh:
+    d = -n / |n| ((0, 0, -1) for a zero or non-finite normal), p_i = v + (i + 1/2 - K/2) h d, product and sum rounded separately, then --
+    contract=True -- through raymarching.contract's arithmetic.  K = samples in {4, 8, 16, 32}; h > 0."""
+    K, h = _probe_args(samples, h, "vertex_probe_points")
+    if normals is None:
+        raise ValueError("vertex_probe_points: the probes need the mesh normals")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or tuple(normals.shape) != tuple(vertices.shape):
+        raise RuntimeError(f"vertex_probe_points: vertices and normals are [V,3], got {tuple(vertices.shape)} and {tuple(normals.shape)}")
+    V = vertices.shape[0]
+    count = V - first if count is None else int(count)
+    first = int(first)
+    if first < 0 or count < 0 or first + count > V:
+        raise ValueError(f"vertex_probe_points: vertices {first} .. {first + count - 1} outside the mesh of {V}")
+    if V > ISOSURFACE_MAX_VERTICES or count * K >= 1 << 32:
+        raise ValueError(f"vertex_probe_points: {V} vertices / {count} x {K} samples exceed one call")
+    v, n = _f32(vertices), _f32(normals)
+    xyz = torch.empty(count, K, 3, device=v.device, dtype=torch.float32)
+    dirs = torch.empty(count, 3, device=v.device, dtype=torch.float32)
+    _lib.check(_lib.lib().sn_rm_vertex_probe_points(_lib.dev(v, "vertices"), _lib.dev(n, "normals"), V, first, count, K, h, int(bool(contract)),
+                                                    _lib.dev(xyz, "xyz"), _lib.dev(dirs, "dirs"), _lib.stream()), "sn_rm_vertex_probe_points")
+    return xyz, dirs
+
+
+def vertex_probe_composite(sigmas: torch.Tensor, geo_feat: torch.Tensor, dirs: torch.Tensor, h: float, labels=None, keep_mask: int = 0xFFFFFFFF,
+                           invert: bool = False, want_labels: bool = False):
+    """One launch: sigmas [V,K], geo_feat [V,K,15], dirs [V,3], labels [V,K] uint8 or None -> (f [V,31], coverage [V], vertex_label [V] uint8
+    or None).  gate = (label in keep_mask) xor invert (true without labels); y = gate ? h sigma : 0; w = (1 - exp(-y)) exp(-sum of the y in
+    front), NaN -> 0; coverage = sum w; f = [sum w geo / coverage | SH4(d / |d|)], with the plain mean of the K geo rows where the coverage is
+    below 2^-126.  want_labels (needs labels): the vertex label is the lowest id with the largest sum of w over its samples, 255 where no
+    vote is positive.  include/sanerf_hip.h states the definition, tests/mesh_attr_ref64.py its fp64 twin.  No autograd."""
+    if sigmas.dim() != 2:
+        raise RuntimeError(f"vertex_probe_composite: sigmas must be [V,K], got {tuple(sigmas.shape)}")
+    V, K = sigmas.shape
+    K, h = _probe_args(K, h, "vertex_probe_composite")
+    if tuple(geo_feat.shape) != (V, K, PROBE_GEO) or tuple(dirs.shape) != (V, 3):
+        raise RuntimeError(f"vertex_probe_composite: geo_feat {tuple(geo_feat.shape)} / dirs {tuple(dirs.shape)} do not match sigmas [{V},{K}] "
+                           f"(geo_feat has {PROBE_GEO} channels)")
+    if labels is not None and (labels.dtype != torch.uint8 or tuple(labels.shape) != (V, K)):
+        raise RuntimeError(f"vertex_probe_composite: labels must be uint8 [{V},{K}], got {labels.dtype} {tuple(labels.shape)}")
+    if want_labels and labels is None:
+        raise ValueError("vertex_probe_composite: vertex labels need the per-sample labels")
+    if not 0 <= int(keep_mask) < (1 << 32):
+        raise ValueError("vertex_probe_composite: keep_mask is a 32-bit mask")
+    if V * 16 >= 1 << 32:
+        raise ValueError(f"vertex_probe_composite: at most 2^28 - 1 vertices per call (got {V})")
+    sg, gf, dr = _f32(sigmas), _f32(geo_feat), _f32(dirs)
+    if gf.data_ptr() % 16:
+        gf = gf.clone()                    # (a view at an odd offset: the kernel reads 16-byte pieces)
+    lb = None if labels is None else labels.detach().contiguous()
+    dev = sg.device
+    f = torch.empty(V, 16 + PROBE_GEO, device=dev, dtype=torch.float32)
+    coverage = torch.empty(V, device=dev, dtype=torch.float32)
+    vlabel = torch.empty(V, device=dev, dtype=torch.uint8) if want_labels else None
+    _lib.check(_lib.lib().sn_rm_vertex_probe_composite(_lib.dev(lb, "labels", torch.uint8), _lib.dev(sg, "sigmas"), _lib.dev(gf, "geo_feat"),
+                                                       _lib.dev(dr, "dirs"), V, K, h, int(keep_mask), int(bool(invert)), _lib.dev(f, "f"),
+                                                       _lib.dev(coverage, "coverage"), _lib.dev(vlabel, "vertex_label", torch.uint8),
+                                                       _lib.stream()), "sn_rm_vertex_probe_composite")
+    return f, coverage, vlabel
