@@ -1092,6 +1092,73 @@ int sn_rm_mesh_simplify_emit(const float *vertices, const float *normals, const 
                              float *out_vertices, float *out_normals, int32_t *out_triangles, int32_t *vertex_cluster, uint32_t cap_v,
                              uint32_t cap_t, sn_stream_t stream);
 
+/* Mesh smoothing and geometric normals (raymarching.mesh_smooth, mesh_vertex_normals, NeRFRenderer.extract_mesh(smooth)): Taubin or plain
+ * Laplacian smoothing of an indexed triangle mesh with the uniform umbrella, carried out on integers (csrc/mesh_smooth.hip), and the
+ * area-weighted vertex normals of the result.  The definition is this project's; tests/mesh_smooth_ref.py restates it operation for
+ * operation in numpy.  Every sum that crosses lanes is a sum of integers, and everything else is the correctly rounded result of the
+ * stated operations, so the device's output EQUALS the restatement's: vertices and normals bit for bit, flags exactly.
+ *
+ * Input: vertices [V,3] fp32, triangles [T,3] int32 -- any indexed mesh -- origin[3] (fp32, finite; a HOST array) and ONE quantum (fp32,
+ * > 0 and finite): the integer space is isotropic.
+ *   Quantisation      per axis u = p - origin and s = u / quantum in fp32 (IEEE division; two roundings, no contraction), r = rintf(s).  A
+ *                     vertex is PLACED iff all three r are finite and 0 <= r < 4194304 (2^22); Q0 = (int32)r.  An unplaced vertex never
+ *                     moves and contributes to no sum and to no normal.
+ *   Valid triangle    all three indices in [0, V) and pairwise distinct (every index is range-tested before it is an address).  Any other
+ *                     row contributes nothing anywhere.
+ *   Corner pairs      a valid triangle (a, b, c) gives vertex a the pair (next = b, prev = c), b the pair (c, a) and c the pair (a, b).
+ *   Open vertex       mix(i) = the splitmix64 finaliser of (uint64)i + 1: x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) 0xBF58476D1CE4E5B9;
+ *                     x = (x ^ x >> 27) 0x94D049BB133111EB; x ^= x >> 31.  v is OPEN iff sum mix(next) != sum mix(prev) modulo 2^64 over
+ *                     its pairs.  mix is a bijection: on a consistently oriented mesh whose edges carry at most two triangles, a vertex
+ *                     with one triangle fan is open exactly when it lies on an edge that one triangle uses (no collision is possible
+ *                     there).  A vertex where the orientation is inconsistent is open too -- the safe side, open vertices being pinned.
+ *   Half-step, f      (f fp32, promoted to fp64.)  S (int64 per axis) = the sum of Q over the placed next and the placed prev of v's pairs,
+ *                     n = the number of those terms: in a closed manifold every neighbour counts twice, which is the uniform umbrella.
+ *                     v is FREE iff it is placed, n > 0, and it is not both open and pinned (pin_open).  A free vertex gets, per axis,
+ *                         d = (double)S / (double)n - (double)Q;  r = rint((double)f d), ties to even;  Q' = clamp(Q + (int64)r, 0, 2^22 - 1)
+ *                     every operation rounded on its own; any other vertex keeps Q.  All vertices update at once (Jacobi): a half-step
+ *                     reads one buffer and writes the other.
+ *   Iteration         a half-step with lambda, then one with mu; mu == 0 skips the second (plain Laplacian smoothing).  Accepted:
+ *                     0 < lambda <= 1, and mu == 0 or -1 <= mu < -lambda.  iterations = 0 moves nothing.
+ *   Output vertices   a vertex whose final Q equals Q0 -- unplaced, pinned, isolated, converged, zero iterations -- keeps its input BITS
+ *                     (the emit requantises `vertices` to decide; no copy of Q0 is kept).  Every other vertex gets, per axis,
+ *                     fp32((double)origin + (double)quantum (double)Q): product and sum rounded once each in fp64, then once to fp32.
+ *   Geometric normals (optional.)  S = the int64 sum, over v's pairs with all three corners placed, of (Q_next - Q_v) x (Q_prev - Q_v) on
+ *                     the FINAL integers: each component is a difference of two products below 2^44, so exact; area-weighted; the same
+ *                     vector from whichever corner of a triangle it is computed.  The sum wraps modulo 2^64 (no vertex of valence below
+ *                     2^18 gets there).  The normal is S / sqrt((Sx Sx + Sy Sy) + Sz Sz) in fp64 ((double)S is the conversion's one
+ *                     rounding), no contraction, rounded once to fp32; (0,0,0) when S is zero -- mesh_simplify's formula.  With the
+ *                     isosurface's orientation these point outward, like its -g/|g|.
+ *   Flags             vertex_flags [V] uint8 (optional): bit 0 placed, bit 1 open, bit 2 moved (placed and Q != Q0).
+ * No output depends on the order of accumulation, the launch shape, the order of the vertices or the run.
+ *
+ * sn_rm_mesh_smooth_workspace_bytes(V, T):
+ *     16 + 32V + up(8V) + 2 up(4V) + up(8 ceil(V / 1024)) + up(24T)                                        (up = rounded up to 16)
+ * i.e. 48 bytes per vertex (two [V,4] int32 buffers of Q and flags, a 64-bit row start, a degree and a cursor) and 24 per triangle (three
+ * int2 pairs).  0 (with a message) if V or T >= 2^31.
+ * sn_rm_mesh_smooth_build: counts the pairs of every vertex (integer atomic adds), ranks them by segments of 1024 vertices and scans the
+ * segment totals with one workgroup (64 bits: 3T passes 2^32), fills every vertex's row of int2 (next, prev) -- the slot inside a row comes
+ * from an integer atomic cursor, an order no output can see because every consumer of a row is an integer sum -- then quantises and
+ * derives the open flags: five launches behind one memset.  n is not stored: the half-step counts the placed neighbours it gathers.
+ * sn_rm_mesh_smooth_steps: `iterations` iterations on the integers in the workspace, ONE launch per half-step, one lane per vertex (a row
+ * of more than 128 pairs is summed by its owner's whole wave): the row, Q[next] and Q[prev] gathered from one buffer, Q' stored to the
+ * other; plain loads and stores, no atomics.  The workspace remembers which buffer is current, so calls compose: 3 then 2 iterations equal
+ * 5, for either kind of iteration.
+ * sn_rm_mesh_smooth_emit: out_vertices [V,3], out_normals [V,3] or NULL, vertex_flags [V] or NULL, from the workspace and `vertices`; the
+ * normals by the same gather over the rows.  It changes nothing in the workspace: steps may follow it.
+ * All three: SN_OK without touching a pointer when V == 0; triangles may be NULL when T == 0; workspace 16-byte aligned; V, T, origin and
+ * quantum must be the build's.  Errors before any launch: SN_ERR_INVALID (NULL pointer, misaligned workspace, a quantum that is not
+ * positive and finite, a non-finite origin, lambda or mu outside the ranges above), SN_ERR_UNSUPPORTED (V or T >= 2^31), SN_ERR_WORKSPACE.
+ * Every index read from a row is range-tested again and a row is read only inside the workspace's 3T pairs: a workspace that no build
+ * filled gives meaningless integers, never an access out of bounds.
+ * Not here: cotangent or other geometry-dependent weights (not exact in integers), feature-preserving smoothing. */
+size_t sn_rm_mesh_smooth_workspace_bytes(uint32_t V, uint32_t T);
+int sn_rm_mesh_smooth_build(const float *vertices, const int32_t *triangles, uint32_t V, uint32_t T, const float *origin, float quantum,
+                            void *workspace, size_t workspace_bytes, sn_stream_t stream);
+int sn_rm_mesh_smooth_steps(uint32_t V, uint32_t T, uint32_t iterations, float lambda, float mu, int pin_open, void *workspace,
+                            size_t workspace_bytes, sn_stream_t stream);
+int sn_rm_mesh_smooth_emit(const float *vertices, uint32_t V, uint32_t T, const float *origin, float quantum, const void *workspace,
+                           size_t workspace_bytes, float *out_vertices, float *out_normals, uint8_t *vertex_flags, sn_stream_t stream);
+
 /* Training-time forward of a bias-free perceptron with 256-wide hidden layers and no skip connections (nerf/network.py:31-66: F.linear +
  * activation per layer; the per-sample mask head in training, network.py:118-123, trainer.py:401-428) in ONE kernel, true fp32 products
  * and accumulation on the matrix cores (v_mfma_f32_32x32x2_f32; results differ from a BLAS GEMM only by summation order).

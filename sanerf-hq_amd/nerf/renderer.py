@@ -582,7 +582,7 @@ class NeRFRenderer(nn.Module):
 
     def extract_mesh(self, resolution=256, threshold=None, aabb=None, instance_ids=None, invert=False, normals=True,
                      min_component_triangles=0, keep_largest=0, simplify=0, vertex_colors=False, vertex_labels=False, probe_samples=8,
-                     probe_step=0.5):
+                     probe_step=0.5, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, smooth_pin_open=True):
         """The surface sigma = threshold (default self.density_thresh) of density_volume(resolution, aabb, instance_ids, invert) by marching
         tetrahedra on the device: {"vertices" [V,3] f32, "normals" [V,3] f32 or None, "triangles" [T,3] int32} in world coordinates -- the
         whole scene, or with instance_ids the object alone (invert: the scene without it).  The size of the result depends on the data
@@ -596,13 +596,22 @@ class NeRFRenderer(nn.Module):
         lattice (cell = k step, origin = lattice origin - step / 2, dims covering the lattice), so the result does not depend on where
         the object sits in its bounding box.  Clustering does not preserve manifoldness.
 
+        smooth = N >= 1 iterations (0: off, nothing is launched for it, and the result is the same bits as without the parameter): after
+        clean-up and simplification the mesh goes through raymarching.mesh_smooth -- Taubin smoothing in fixed point with smooth_lambda and
+        smooth_mu (mu = 0: plain Laplacian), vertices on open edges pinned with smooth_pin_open -- quantised over the extraction lattice's
+        own box (raymarching.smooth_quantisation), so the result does not depend on where the object sits and nothing is read back.  With
+        normals=True the result's normals are then the geometric ones of the smoothed triangles, and the probes below enter along them.
+
         vertex_colors, vertex_labels (both False: nothing is launched for them and the dict has the three keys above; either needs
-        normals=True): the FINAL mesh -- after clean-up and simplification -- goes through vertex_attributes with probe_samples samples
+        normals=True): the FINAL mesh -- after clean-up, simplification and smoothing -- goes through vertex_attributes with probe_samples samples
         probe_step lattice steps apart (h = probe_step min(step)) and the same instance_ids / invert, and the dict gains "colors" [V,3]
         and "coverage" [V] (vertex_colors) and "labels" [V] uint8 (vertex_labels).  save_mesh writes both."""
         simplify = float(simplify)
         if simplify != 0.0 and not (1.0 <= simplify < float("inf")):
             raise ValueError(f"extract_mesh: simplify = {simplify} must be 0 (off) or at least 1 lattice step")
+        smooth = rm.mesh._smooth_iterations(smooth, "extract_mesh: smooth")
+        if smooth:
+            rm.mesh._smooth_factors(smooth_lambda, smooth_mu, "extract_mesh")
         res, origin, step = self._lattice(resolution, aabb)
         attributes = bool(vertex_colors) or bool(vertex_labels)
         if attributes:
@@ -625,6 +634,11 @@ class NeRFRenderer(nn.Module):
             mesh = rm.mesh_simplify(mesh, cell=[float(np.float32(simplify * step[a])) for a in range(3)],
                                     origin=[float(np.float32(origin[a]) - np.float32(0.5) * np.float32(step[a])) for a in range(3)],
                                     dims=[int((res[a] - 0.5) // simplify) + 2 for a in range(3)])     # one spare cell for the rounding of the last vertex
+        if smooth:
+            quant = rm.smooth_quantisation(origin, [origin[a] + (res[a] - 1) * step[a] for a in range(3)])       # the lattice's box, in fp64
+            if quant is None:
+                raise ValueError("extract_mesh: smooth needs a lattice box of positive, finite extent")
+            mesh = rm.mesh_smooth(mesh, smooth, smooth_lambda, smooth_mu, smooth_pin_open, origin=quant[0], quantum=quant[1], normals=bool(normals))
         if attributes:
             attr = self.vertex_attributes(mesh, probe_h, samples=int(probe_samples), instance_ids=instance_ids, invert=invert,
                                           labels=bool(vertex_labels))

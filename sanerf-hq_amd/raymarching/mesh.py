@@ -1,16 +1,19 @@
-"""Geometry export (mesh.hip, mesh_clean.hip, mesh_simplify.hip, mesh_attr.hip): lattice positions, marching tetrahedra on a density lattice,
-the clean-up of the mesh, its simplification, and the surface probes that give its vertices a colour and an instance label.
+"""Geometry export (mesh.hip, mesh_clean.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_attr.hip): lattice positions, marching tetrahedra on a
+density lattice, the clean-up of the mesh, its simplification, its smoothing, and the surface probes that give its vertices a colour and an
+instance label.
 
     lattice_points     positions of a window of the vertices of an nx x ny x nz lattice, optionally contracted -- no meshgrid per chunk
     isosurface         volume [nx,ny,nz], iso -> {"vertices" [V,3], "normals" [V,3] or None, "triangles" [T,3] int32}
     mesh_components    triangles [T,3], V -> labels, triangle and vertex counts per connected component
     mesh_clean         a mesh without its small components (floaters, label noise): by triangle count and / or the largest k
     mesh_simplify      uniform vertex clustering: one vertex per occupied cell of a coarse lattice
+    mesh_smooth        Taubin / Laplacian smoothing on integers, and the geometric normals of the result; mesh_vertex_normals alone
     vertex_probe_points, vertex_probe_composite   K samples of a short ray into the surface at every vertex; their gated re-integration
                        into the colour head's input, the coverage and the voted label (tests/mesh_attr_ref64.py states it in fp64)
 include/sanerf_hip.h states the definitions (inside test, edge slots, Kuhn tetrahedra, orientation from the table, both orders, normals;
-valid triangles, components, keys, selection, the filtered mesh's order; cells, triangle classes, the integer sums); tests/mesh_ref.py,
-tests/mesh_clean_ref.py and tests/mesh_simplify_ref.py restate them in numpy."""
+valid triangles, components, keys, selection, the filtered mesh's order; cells, triangle classes, the integer sums; quantisation, corner
+pairs, open vertices, the half-step, the geometric normals); tests/mesh_ref.py, tests/mesh_clean_ref.py, tests/mesh_simplify_ref.py and
+tests/mesh_smooth_ref.py restate them in numpy."""
 from __future__ import annotations
 
 from typing import Sequence
@@ -360,6 +363,173 @@ def mesh_simplify(mesh: dict, cell, origin=None, dims=None, return_cluster: bool
     if return_cluster:
         out["vertex_cluster"] = cluster
     return out
+
+
+# ---- smoothing in fixed point, geometric normals (mesh_smooth.hip) --------------------------------------------------------------------------
+def smooth_quantisation(lo, hi):
+    """(origin [3], quantum) that put the box lo .. hi inside the integer range [0, 2^22): with E the longest side of the box in fp64,
+    quantum = fp32(E / 2^21) and origin_a = fp32(lo_a - 524288 quantum) (the product is exact, the difference one fp64 rounding).  The box
+    then spans 2^19 .. 2^19 + 2^21 along its longest side: at least a quarter of its extent stays free on each side for the negative mu
+    step.  None when E is 0, not finite, or too small for the quantum to be a positive fp32 number.  Host arithmetic only."""
+    import numpy as np
+    lo, hi = _triple(lo, "lo"), _triple(hi, "hi")
+    E = max(hi[a] - lo[a] for a in range(3))
+    with np.errstate(all="ignore"):
+        quantum = np.float32(E / 2097152.0)
+        origin = [np.float32(lo[a] - 524288.0 * float(quantum)) for a in range(3)]
+    if not (E > 0.0 and np.isfinite(quantum) and quantum > 0 and all(np.isfinite(o) for o in origin)):
+        return None
+    return [float(o) for o in origin], float(quantum)
+
+
+def _smooth_factors(lam, mu, what):
+    """lambda and mu as the fp32 values the library receives, tested the way it tests them."""
+    lam32, mu32 = (float(torch.tensor(float(x), dtype=torch.float32)) for x in (lam, mu))
+    if not (0.0 < lam32 <= 1.0):
+        raise ValueError(f"{what}: lambda = {lam} must be in (0, 1]")
+    if not (mu32 == 0.0 or -1.0 <= mu32 < -lam32):
+        raise ValueError(f"{what}: mu = {mu} must be 0 (plain Laplacian smoothing) or in [-1, -lambda)")
+    return lam32, mu32
+
+
+def _smooth_iterations(iterations, what):
+    import operator
+    try:
+        n = -1 if isinstance(iterations, bool) else operator.index(iterations)
+    except TypeError:
+        n = -1
+    if not 0 <= n < 1 << 32:
+        raise ValueError(f"{what}: {iterations!r} iterations: a non-negative integer is needed")
+    return n
+
+
+def _smooth_quant_args(origin, quantum, what):
+    origin, quantum = _triple(origin, "origin"), float(quantum)
+    q32 = float(torch.tensor(quantum, dtype=torch.float32))
+    if not (0.0 < q32 < float("inf")):
+        raise ValueError(f"{what}: quantum = {quantum} must be positive and finite in fp32")
+    if not all(abs(float(torch.tensor(o, dtype=torch.float32))) < float("inf") for o in origin):
+        raise ValueError(f"{what}: origin = {origin} must be finite in fp32")
+    return _lib.host_f32(origin), q32
+
+
+def _smooth_workspace(V, T, device):
+    L = _lib.lib()
+    need = int(L.sn_rm_mesh_smooth_workspace_bytes(V, T))
+    if need == 0:
+        raise RuntimeError("mesh_smooth: " + L.sn_last_error().decode())
+    return _buffers.scratch("mesh_smooth", device, need)
+
+
+def mesh_smooth_build(vertices: torch.Tensor, triangles: torch.Tensor, origin, quantum) -> torch.Tensor:
+    """The first phase of mesh_smooth(): quantises vertices [V,3] f32 to Q = rint((p - origin) / quantum) and inverts triangles [T,3] int32
+    into every vertex's row of (next, prev) pairs, with the open flags.  Returns the workspace that mesh_smooth_steps() and
+    mesh_smooth_emit() take -- the module's one "mesh_smooth" buffer per device: the next build on that device reuses it.  Nothing is read
+    back."""
+    tri, V, T = _triangles_i32(triangles, vertices.shape[0])
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError(f"mesh_smooth: vertices must be [V,3], got {tuple(vertices.shape)}")
+    p_v = _lib.dev(vertices, "vertices")
+    h_origin, q32 = _smooth_quant_args(origin, quantum, "mesh_smooth_build")
+    ws = _smooth_workspace(V, T, vertices.device)
+    _lib.check(_lib.lib().sn_rm_mesh_smooth_build(p_v, _lib.dev(tri, "triangles", torch.int32), V, T, h_origin, q32, ws.data_ptr(), ws.numel(),
+                                                  _lib.stream()), "sn_rm_mesh_smooth_build")
+    return ws
+
+
+def mesh_smooth_steps(n_vertices: int, n_triangles: int, workspace: torch.Tensor, iterations: int, lam: float = 0.5, mu: float = -0.53,
+                      pin_open: bool = True):
+    """The second phase: `iterations` iterations -- a half-step with lam, then (mu != 0) one with mu, one launch each -- on the integers
+    mesh_smooth_build() left in the workspace for a mesh of these sizes.  Calls compose: 3 then 2 iterations equal 5."""
+    iterations = _smooth_iterations(iterations, "mesh_smooth_steps")
+    lam32, mu32 = _smooth_factors(lam, mu, "mesh_smooth_steps")
+    _lib.check(_lib.lib().sn_rm_mesh_smooth_steps(int(n_vertices), int(n_triangles), iterations, lam32, mu32, int(bool(pin_open)),
+                                                  workspace.data_ptr(), workspace.numel(), _lib.stream()), "sn_rm_mesh_smooth_steps")
+
+
+def mesh_smooth_emit(vertices: torch.Tensor, n_triangles: int, origin, quantum, workspace: torch.Tensor, out_vertices: torch.Tensor,
+                     out_normals=None, vertex_flags=None):
+    """The third phase: fills out_vertices [V,3] f32, out_normals [V,3] f32 (or None) and vertex_flags [V] uint8 (or None; bit 0 placed,
+    bit 1 open, bit 2 moved) from the workspace and the vertices, origin and quantum the build was given.  It leaves the workspace as it
+    is: more steps may follow."""
+    V = vertices.shape[0]
+    if (tuple(out_vertices.shape) != (V, 3) or (out_normals is not None and tuple(out_normals.shape) != (V, 3))
+            or (vertex_flags is not None and tuple(vertex_flags.shape) != (V,))):
+        raise ValueError("mesh_smooth_emit: out_vertices and out_normals are [V,3], vertex_flags is [V]")
+    h_origin, q32 = _smooth_quant_args(origin, quantum, "mesh_smooth_emit")
+    _lib.check(_lib.lib().sn_rm_mesh_smooth_emit(_lib.dev(vertices, "vertices"), V, int(n_triangles), h_origin, q32, workspace.data_ptr(),
+                                                 workspace.numel(), _lib.dev(out_vertices, "out_vertices"), _lib.dev(out_normals, "out_normals"),
+                                                 _lib.dev(vertex_flags, "vertex_flags", torch.uint8), _lib.stream()), "sn_rm_mesh_smooth_emit")
+
+
+def _bounding_quantisation(vertices: torch.Tensor):
+    """smooth_quantisation of the bounding box of the finite vertices; None without one.  One aminmax on the device, its six values read back."""
+    finite = vertices[torch.isfinite(vertices).all(dim=1)]
+    if finite.shape[0] == 0:
+        return None
+    lo, hi = torch.aminmax(finite, dim=0)
+    box = torch.stack([lo, hi]).tolist()
+    return smooth_quantisation(box[0], box[1])
+
+
+def mesh_smooth(mesh: dict, iterations: int = 10, lam: float = 0.5, mu: float = -0.53, pin_open: bool = True, origin=None, quantum=None,
+                normals=None, return_flags: bool = False) -> dict:
+    """Taubin smoothing (mu = 0: plain Laplacian smoothing) of an indexed triangle mesh with the uniform umbrella, in fixed point on the
+    device, and the geometric normals of the result.  mesh: the keys of isosurface() ("vertices" [V,3] f32, "normals" [V,3] f32 or None,
+    "triangles" [T,3] int32; any indexed mesh on the device).  The result has the same keys; "triangles" is the input tensor; "normals" are
+    the area-weighted normals of the SMOOTHED triangles when `normals` is true (default: iff the input has normals; the input's values are
+    not read), else None.  return_flags: also "vertex_flags" [V] uint8 -- bit 0 placed, bit 1 open, bit 2 moved.
+
+    One iteration moves every vertex by lam times the difference to the mean of its neighbours, then by mu times the new difference
+    (mu < -lam: the step that undoes the shrinkage).  Positions are integers Q = rint((p - origin) / quantum) in [0, 2^22) per axis, so
+    every sum is exact: the result equals tests/mesh_smooth_ref.py bit for bit and depends on neither the order of the vertices nor the
+    run; include/sanerf_hip.h has the definition.  Vertices on an open edge stay where they are with pin_open; a vertex that does not
+    move keeps its input bits; a vertex outside the integer range, or with a non-finite coordinate, is left alone and ignored by its
+    neighbours.
+
+    origin (3 floats), quantum (one float): the quantisation; give both or neither.  With both given NOTHING is read back on the host --
+    the sizes of the outputs are the input's.  With neither, smooth_quantisation of the bounding box of the finite vertices is used (the
+    box well inside the range): one torch.aminmax, read back.  A mesh without a finite vertex or with a box of extent 0 is
+    returned with its vertices unchanged and all normals zero.  Deterministic: two calls give equal bits."""
+    iterations = _smooth_iterations(iterations, "mesh_smooth")
+    _smooth_factors(lam, mu, "mesh_smooth")
+    if (origin is None) != (quantum is None):
+        raise ValueError("mesh_smooth: give origin and quantum together, or neither")
+    if origin is not None:
+        _smooth_quant_args(origin, quantum, "mesh_smooth")
+    vertices, triangles = _f32(mesh["vertices"]), mesh["triangles"]
+    _, V, T = _triangles_i32(triangles, vertices.shape[0])
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError(f"mesh_smooth: vertices must be [V,3], got {tuple(vertices.shape)}")
+    _lib.dev(vertices, "vertices")
+    want_normals = (mesh.get("normals") is not None) if normals is None else bool(normals)
+    dev = vertices.device
+    quant = (origin, quantum) if origin is not None else (_bounding_quantisation(vertices) if V else None)
+    out = dict(mesh)
+    if quant is None or V == 0:
+        out["vertices"] = vertices.clone()
+        out["normals"] = torch.zeros(V, 3, device=dev, dtype=torch.float32) if want_normals else None
+        if return_flags:
+            out["vertex_flags"] = torch.zeros(V, device=dev, dtype=torch.uint8)
+        return out
+    origin, quantum = quant
+    ws = mesh_smooth_build(vertices, triangles, origin, quantum)
+    if iterations:
+        mesh_smooth_steps(V, T, ws, iterations, lam, mu, pin_open)
+    out["vertices"] = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    out["normals"] = torch.empty(V, 3, device=dev, dtype=torch.float32) if want_normals else None
+    flags = torch.empty(V, device=dev, dtype=torch.uint8) if return_flags else None
+    mesh_smooth_emit(vertices, T, origin, quantum, ws, out["vertices"], out["normals"], flags)
+    if return_flags:
+        out["vertex_flags"] = flags
+    return out
+
+
+def mesh_vertex_normals(mesh: dict, origin=None, quantum=None) -> torch.Tensor:
+    """[V,3] f32: the area-weighted normals of the mesh's own triangles at its vertices -- mesh_smooth's geometric normals with no step
+    taken (build + emit), on positions quantised as mesh_smooth quantises them.  (0,0,0) at a vertex without a valid triangle.  origin,
+    quantum: as for mesh_smooth."""
+    return mesh_smooth(mesh, iterations=0, origin=origin, quantum=quantum, normals=True)["normals"]
 
 
 # ---- vertex attributes: surface probes (mesh_attr.hip) -------------------------------------------------------------------------------------
