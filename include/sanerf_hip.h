@@ -1159,6 +1159,78 @@ int sn_rm_mesh_smooth_steps(uint32_t V, uint32_t T, uint32_t iterations, float l
 int sn_rm_mesh_smooth_emit(const float *vertices, uint32_t V, uint32_t T, const float *origin, float quantum, const void *workspace,
                            size_t workspace_bytes, float *out_vertices, float *out_normals, uint8_t *vertex_flags, sn_stream_t stream);
 
+/* Mesh rasteriser (raymarching.mesh_rasterize, NeRFRenderer.render_mesh): an indexed triangle mesh seen from one pinhole camera through a
+ * depth buffer (csrc/mesh_raster.hip) -- per pixel the triangle, its depth, the coverage and the interpolated vertex attributes.  The
+ * definition is this project's; tests/mesh_raster_ref.py restates it operation for operation in numpy.  Everything that decides a pixel is an
+ * integer or the correctly rounded result of the stated operations, and the depth test is a maximum, so the device's output EQUALS the
+ * restatement's bit for bit, whatever the order of the triangles, the launch shape or the run.
+ *
+ * Input: vertices [V,3] fp32, triangles [T,3] int32 -- any indexed mesh, the tensors extract_mesh returns -- pose [4,4] fp32 (row-major
+ * cam2world: R = its upper-left 3x3 block, o = its last column) and intrinsics [4] fp32 = {fx, fy, cx, cy}, both ON THE DEVICE (read when
+ * the kernels run: a captured graph replays with a new camera), in the convention of sn_rm_generate_rays: the camera looks along -z of its
+ * frame, x to the right, y up; the centre of pixel (i, j) -- column i, row j -- is at (i + 0.5, j + 0.5).  An image of H rows, W columns.
+ *   Camera            d = v - o per axis; c_j = (R[0][j] d_0 + R[1][j] d_1) + R[2][j] d_2 for j = 0, 1, 2 (c = R^T d): fp32, every product and
+ *                     sum rounded on its own.  z = -c_2: the depth, which is the field render's `depth` for the unnormalised ray directions
+ *                     of sn_rm_generate_rays.  r = 1 / z.  x = (fx c_0) / z + cx and y = -((fy c_1) / z) + cy, with the IEEE division.
+ *   Placed vertex     iff its three coordinates are finite, z >= near (near > 0), r is finite (it is unless z is below 2^-128), and the
+ *                     snapped coordinates X = rint(256 x), Y = rint(256 y) (ties to even; 256 x is exact) lie in [-2^22, 2^22] -- the guard
+ *                     band, 2^14 pixels either side of the pixel grid's origin.  No NaN passes.  X, Y are int32 with 8 sub-pixel bits.
+ *   Drawn triangle    iff its three indices are in [0, V) (each is range-tested before it is an address), its three vertices are placed, its
+ *                     doubled signed area A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) (int64) is not 0 and, with `cull`, A < 0.  On the
+ *                     sign: a triangle that is counter-clockwise seen from outside -- sn_rm_isosurface_emit's promise -- is counter-clockwise
+ *                     in the camera's (c_0, c_1) plane when its outside faces the camera; the screen's y points down, which turns it
+ *                     around: FRONT faces have A < 0.  There is no near-plane or guard-band clipping: a triangle with a corner that is not
+ *                     placed is dropped whole.  counts [4] int32 = triangles {drawn, dropped for a bad index or an unplaced corner,
+ *                     degenerate (A = 0), culled}, tested in that order; they sum to T.
+ *   Coverage          one sample per pixel at its centre P = (256 i + 128, 256 j + 128).  With s = sign(A): edge k runs from corner k + 1 to
+ *                     corner k + 2 (mod 3), (dx, dy) = s (that edge's vector), w_k = dx (P_y - Y_{k+1}) - dy (P_x - X_{k+1}): int64, exact
+ *                     (every product is below 2^47), w_0 + w_1 + w_2 = |A|, and w_k > 0 inside.  A pixel is covered iff for every k
+ *                     w_k > 0, or w_k == 0 and edge k is a top edge (dy == 0, dx > 0) or a left edge (dy < 0): the top-left rule, under
+ *                     which two triangles that share an edge cover every pixel on it exactly once, whatever their order or orientation.
+ *   Depth key         rho = (((double)w_0 r_0 + (double)w_1 r_1) + (double)w_2 r_2) / (double)|A| in fp64, every operation rounded on its own:
+ *                     the inverse depth, linear on the screen.  The pixel keeps the triangle with the LARGEST fp32(rho) (positive: its bits
+ *                     order as unsigned integers), on equal bits the LOWEST index t: the maximum of (bits(fp32 rho) << 32) | (0xFFFFFFFF - t)
+ *                     as one 64-bit unsigned integer, 0 = empty.  (The device's fp64 quotient is the correctly rounded one: the
+ *                     device equals numpy here.)
+ *   Resolve           per pixel with winner t, rho recomputed: triangle_id = t, depth = fp32(1.0 / rho) (fp64 division), mask = 1; empty:
+ *                     -1, 0, 0.  Perspective-correct weights mu_k = p_k / ((p_0 + p_1) + p_2) with p_k = (double)w_k r_k.
+ *                     colors [V,3] fp32 -> image [H,W,3] = fp32((mu_0 a_0 + mu_1 a_1) + mu_2 a_2) per channel in fp64, a_k the attribute
+ *                     of corner k; bg_color where empty.  normals [V,3] -> normal [H,W,3]: the same sum, NOT renormalised; 0 where empty.
+ *                     labels [V] uint8 -> label [H,W] uint8: the label of the corner with the largest mu, the first corner of the row
+ *                     winning ties; 255 where empty.
+ *
+ * sn_rm_mesh_raster_workspace_bytes(V, T, H, W):
+ *     16 + 16V + 8HW + up(4T)                                                                                (up = rounded up to 16)
+ * i.e. a head (the queue's length), a 16-byte row {X, Y, bits(r), placed} per vertex, the 64-bit depth buffer, and a queue of triangle
+ * indices.  0 (with a message) unless V, T < 2^31 and H, W are in [1, 8192].
+ * sn_rm_mesh_raster_project: one lane per vertex writes its row; the same launch clears the depth buffer, the queue's length and counts.
+ * sn_rm_mesh_raster_draw: two launches.  One lane per triangle classifies it and adds to counts (one atomic add per wave and counter);
+ * a triangle whose bounding box, clipped to the screen, holds at most small_max_pixels (< 2^31) pixel centres is scanned by its lane; the
+ * others are appended to the queue (ballot + mbcnt rank, one atomic add per wave).  Then a fixed grid of waves strides over the queue,
+ * whose length is read on the device: the 64 lanes of a wave share one triangle and walk its clipped bounding box in row segments.  The
+ * depth test is the plain 64-bit atomic maximum (global_atomic_umax_x2, no compare-and-swap loop).  small_max_pixels moves triangles
+ * between the two kernels and changes the time only: 0 (all through the queue) and 2^31 - 1 (none) give the same bits.
+ * sn_rm_mesh_raster_resolve: one lane per pixel; triangle_id [H,W] int32, depth [H,W] fp32, mask [H,W] uint8 always; colors with image,
+ * normals with normal, labels with label, each pair both given or both NULL (with V == 0 the attribute may be NULL beside its image).  It
+ * changes nothing in the workspace.
+ * All three: vertices may be NULL when V == 0 and triangles when T == 0 -- the project still clears and the resolve still writes the empty
+ * image; workspace 16-byte aligned; V, T, H, W must be the project's.  Errors before any launch: SN_ERR_INVALID (NULL pointer, misaligned
+ * workspace, a near that is not positive and finite, small_max_pixels >= 2^31, an attribute without its image or the reverse),
+ * SN_ERR_UNSUPPORTED (V or T >= 2^31, H or W outside [1, 8192]), SN_ERR_WORKSPACE.  Every index read from `triangles`, from the queue or
+ * from the depth buffer is range-tested before it is an address: a workspace that no project filled gives a meaningless image, never an
+ * access out of bounds.
+ * Not here: clipping (a triangle that crosses the near plane or leaves the guard band disappears), anti-aliasing, transparency, textures,
+ * gradients. */
+size_t sn_rm_mesh_raster_workspace_bytes(uint32_t V, uint32_t T, uint32_t H, uint32_t W);
+int sn_rm_mesh_raster_project(const float *vertices, uint32_t V, uint32_t T, const float *pose, const float *intrinsics, uint32_t H, uint32_t W,
+                              float near_plane, void *workspace, size_t workspace_bytes, int32_t *counts, sn_stream_t stream);
+int sn_rm_mesh_raster_draw(const int32_t *triangles, uint32_t V, uint32_t T, uint32_t H, uint32_t W, int cull, uint32_t small_max_pixels,
+                           void *workspace, size_t workspace_bytes, int32_t *counts, sn_stream_t stream);
+int sn_rm_mesh_raster_resolve(const int32_t *triangles, uint32_t V, uint32_t T, uint32_t H, uint32_t W, const float *colors,
+                              const float *normals, const uint8_t *labels, float bg_color, const void *workspace, size_t workspace_bytes,
+                              int32_t *triangle_id, float *depth, uint8_t *mask, float *image, float *normal, uint8_t *label,
+                              sn_stream_t stream);
+
 /* Training-time forward of a bias-free perceptron with 256-wide hidden layers and no skip connections (nerf/network.py:31-66: F.linear +
  * activation per layer; the per-sample mask head in training, network.py:118-123, trainer.py:401-428) in ONE kernel, true fp32 products
  * and accumulation on the matrix cores (v_mfma_f32_32x32x2_f32; results differ from a BLAS GEMM only by summation order).

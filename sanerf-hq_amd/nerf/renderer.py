@@ -649,6 +649,23 @@ class NeRFRenderer(nn.Module):
                 mesh["labels"] = attr["labels"]
         return mesh
 
+    def render_mesh(self, mesh, pose, intrinsics, H, W, cull=False, bg_color=1):
+        """The image of an extracted mesh from one camera: raymarching.mesh_rasterize of `mesh` (what extract_mesh returns, with its "colors" and
+        "labels" where it has them) for pose [4,4] and intrinsics [4] in get_rays' convention, with near = opt.min_near -- the plane at which
+        the field's rays start.  Returns "triangle_id", "depth", "mask" [H,W], "counts" [4] and, with the attribute, "image" [H,W,3] and
+        "label" [H,W].  (The geometry image that the reference's commented-out --render_mesh branch announced.)  No-grad only; nothing is
+        read back, and with pose and intrinsics as fp32 device tensors a warmed-up call can be captured as a HIP graph and replayed with a
+        new camera written into them.
+
+        Beside the field's renders of the same camera (rays from get_rays(pose, intrinsics, H, W), results reshaped to [H,W]):
+        "depth" is the camera-space -z of the surface and so is render()'s "depth" (get_rays' directions are not normalised; their -z
+        component is 1): where the surface is opaque and "mask" is 1 the two agree to the lattice step of the extraction, and "depth" is 0
+        where the mesh is not seen.  "mask" is the silhouette: set it beside render()'s or render_object()'s "weights_sum" /
+        "object_weights_sum" > 0.5 -- of the object's mesh (instance_ids) beside render_object() with the same ids."""
+        self._inference_only("render_mesh")
+        with torch.no_grad():
+            return rm.mesh_rasterize(mesh, pose, intrinsics, H, W, near=self.min_near, cull=cull, bg_color=float(bg_color))
+
     # ---------------------------------------------------------------------------------------
     fused_training_ops = True    # RGB-mode training: unit-cube positions, fused small MLPs, one-kernel per-ray head (False: the operator chain)
 

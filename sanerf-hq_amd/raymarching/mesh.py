@@ -1,6 +1,6 @@
-"""Geometry export (mesh.hip, mesh_clean.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_attr.hip): lattice positions, marching tetrahedra on a
-density lattice, the clean-up of the mesh, its simplification, its smoothing, and the surface probes that give its vertices a colour and an
-instance label.
+"""Geometry export (mesh.hip, mesh_clean.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_raster.hip, mesh_attr.hip): lattice positions, marching
+tetrahedra on a density lattice, the clean-up of the mesh, its simplification, its smoothing, its image from a camera, and the surface probes
+that give its vertices a colour and an instance label.
 
     lattice_points     positions of a window of the vertices of an nx x ny x nz lattice, optionally contracted -- no meshgrid per chunk
     isosurface         volume [nx,ny,nz], iso -> {"vertices" [V,3], "normals" [V,3] or None, "triangles" [T,3] int32}
@@ -8,12 +8,14 @@ instance label.
     mesh_clean         a mesh without its small components (floaters, label noise): by triangle count and / or the largest k
     mesh_simplify      uniform vertex clustering: one vertex per occupied cell of a coarse lattice
     mesh_smooth        Taubin / Laplacian smoothing on integers, and the geometric normals of the result; mesh_vertex_normals alone
+    mesh_rasterize     the mesh seen from one pinhole camera through a depth buffer: triangle id, depth, mask, interpolated attributes
     vertex_probe_points, vertex_probe_composite   K samples of a short ray into the surface at every vertex; their gated re-integration
                        into the colour head's input, the coverage and the voted label (tests/mesh_attr_ref64.py states it in fp64)
 include/sanerf_hip.h states the definitions (inside test, edge slots, Kuhn tetrahedra, orientation from the table, both orders, normals;
 valid triangles, components, keys, selection, the filtered mesh's order; cells, triangle classes, the integer sums; quantisation, corner
-pairs, open vertices, the half-step, the geometric normals); tests/mesh_ref.py, tests/mesh_clean_ref.py, tests/mesh_simplify_ref.py and
-tests/mesh_smooth_ref.py restate them in numpy."""
+pairs, open vertices, the half-step, the geometric normals; the camera, placed vertices, drawn triangles, the fill rule, the depth key, the
+resolve); tests/mesh_ref.py, tests/mesh_clean_ref.py, tests/mesh_simplify_ref.py, tests/mesh_smooth_ref.py and tests/mesh_raster_ref.py
+restate them in numpy."""
 from __future__ import annotations
 
 from typing import Sequence
@@ -530,6 +532,167 @@ def mesh_vertex_normals(mesh: dict, origin=None, quantum=None) -> torch.Tensor:
     taken (build + emit), on positions quantised as mesh_smooth quantises them.  (0,0,0) at a vertex without a valid triangle.  origin,
     quantum: as for mesh_smooth."""
     return mesh_smooth(mesh, iterations=0, origin=origin, quantum=quantum, normals=True)["normals"]
+
+
+# ---- the rasteriser: a mesh seen from one pinhole camera (mesh_raster.hip) -------------------------------------------------------------------
+RASTER_MAX_SIDE = 8192                 # H, W
+RASTER_SMALL_MAX_PIXELS = 16           # pixel centres in a triangle's clipped bounding box up to which its own lane scans it (DESIGN.md 5.7, the sweep in profiles/mesh_raster_bench.txt)
+RASTER_SMALL_MAX_LIMIT = (1 << 31) - 1
+
+
+def _raster_sizes(V, T, H, W, what):
+    import operator
+    try:
+        H, W = operator.index(H), operator.index(W)
+    except TypeError:
+        raise ValueError(f"{what}: H and W must be integers") from None
+    if not (1 <= H <= RASTER_MAX_SIDE and 1 <= W <= RASTER_MAX_SIDE):
+        raise ValueError(f"{what}: H = {H}, W = {W} must be in [1, {RASTER_MAX_SIDE}]")
+    return int(V), int(T), H, W
+
+
+def _raster_camera(pose, intrinsics, device, what):
+    """pose [4,4] and intrinsics [4] as contiguous fp32 tensors on the device.  A tensor that already is one is passed as it is, so that a
+    captured graph sees what is written into it later."""
+    def one(x, n, shape, name):
+        t = x if torch.is_tensor(x) else torch.as_tensor(x, dtype=torch.float32)
+        if t.numel() != n:
+            raise ValueError(f"{what}: {name} must have {n} entries ({shape}), got {tuple(t.shape)}")
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            t = t.to(device=device, dtype=torch.float32).contiguous()
+        return t
+    return one(pose, 16, "[4,4]", "pose"), one(intrinsics, 4, "[4]", "intrinsics")
+
+
+def _raster_near(near, what):
+    near32 = float(torch.tensor(float(near), dtype=torch.float32))
+    if not (0.0 < near32 < float("inf")):
+        raise ValueError(f"{what}: near = {near} must be positive and finite in fp32")
+    return near32
+
+
+def _raster_workspace(V, T, H, W, device):
+    L = _lib.lib()
+    need = int(L.sn_rm_mesh_raster_workspace_bytes(V, T, H, W))
+    if need == 0:
+        raise RuntimeError("mesh_raster: " + L.sn_last_error().decode())
+    return _buffers.scratch("mesh_raster", device, need)
+
+
+def mesh_raster_project(vertices: torch.Tensor, n_triangles: int, pose: torch.Tensor, intrinsics: torch.Tensor, H: int, W: int, near: float,
+                        counts: torch.Tensor) -> torch.Tensor:
+    """The first phase of mesh_rasterize(): every vertex of vertices [V,3] f32 into the camera (pose [4,4], intrinsics [4] = fx, fy, cx, cy:
+    fp32 tensors ON THE DEVICE, read when the kernel runs) as a row {X, Y, 1/z, placed} of the workspace; clears the H x W depth buffer,
+    the queue and counts (int32 [4]).  Returns the workspace that mesh_raster_draw() and mesh_raster_resolve() take -- the module's one
+    "mesh_raster" buffer per device: the next projection on that device reuses it.  Nothing is read back."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError(f"mesh_raster: vertices must be [V,3], got {tuple(vertices.shape)}")
+    V, T, H, W = _raster_sizes(vertices.shape[0], n_triangles, H, W, "mesh_raster_project")
+    if tuple(counts.shape) != (4,) or pose.numel() != 16 or intrinsics.numel() != 4:
+        raise ValueError("mesh_raster_project: pose is [4,4], intrinsics [4], counts int32 [4]")
+    near32 = _raster_near(near, "mesh_raster_project")
+    p_v = _lib.dev(vertices, "vertices")
+    ws = _raster_workspace(V, T, H, W, vertices.device)
+    _lib.check(_lib.lib().sn_rm_mesh_raster_project(p_v, V, T, _lib.dev(pose, "pose"), _lib.dev(intrinsics, "intrinsics"), H, W, near32,
+                                                    ws.data_ptr(), ws.numel(), _lib.dev(counts, "counts", torch.int32), _lib.stream()),
+               "sn_rm_mesh_raster_project")
+    return ws
+
+
+def mesh_raster_draw(triangles: torch.Tensor, n_vertices: int, H: int, W: int, workspace: torch.Tensor, counts: torch.Tensor, cull: bool = False,
+                     small_max_pixels: int | None = None):
+    """The second phase: the depth test of triangles [T,3] int32 against the rows mesh_raster_project() left, two launches.  A triangle whose
+    clipped bounding box holds at most small_max_pixels pixel centres (default RASTER_SMALL_MAX_PIXELS) is scanned by its own lane, the
+    others by a wave each from a queue on the device; the value changes the time only, never the result.  counts (int32 [4]) gains the
+    drawn, the dropped, the degenerate and the culled."""
+    tri, V, T = _triangles_i32(triangles, n_vertices)
+    V, T, H, W = _raster_sizes(V, T, H, W, "mesh_raster_draw")
+    small = RASTER_SMALL_MAX_PIXELS if small_max_pixels is None else int(small_max_pixels)
+    if not 0 <= small <= RASTER_SMALL_MAX_LIMIT:
+        raise ValueError(f"mesh_raster_draw: small_max_pixels = {small_max_pixels} must be in [0, 2^31)")
+    if tuple(counts.shape) != (4,):
+        raise ValueError("mesh_raster_draw: counts is int32 [4]")
+    _lib.check(_lib.lib().sn_rm_mesh_raster_draw(_lib.dev(tri, "triangles", torch.int32), V, T, H, W, int(bool(cull)), small, workspace.data_ptr(),
+                                                 workspace.numel(), _lib.dev(counts, "counts", torch.int32), _lib.stream()), "sn_rm_mesh_raster_draw")
+
+
+def mesh_raster_resolve(triangles: torch.Tensor, n_vertices: int, H: int, W: int, workspace: torch.Tensor, triangle_id: torch.Tensor,
+                        depth: torch.Tensor, mask: torch.Tensor, colors=None, image=None, normals=None, normal=None, labels=None, label=None,
+                        bg_color: float = 1.0):
+    """The third phase: one lane per pixel turns the depth buffer into triangle_id [H,W] int32 (-1 where empty), depth [H,W] f32 (0) and
+    mask [H,W] uint8, and interpolates the attributes that are given, perspective-correct in fp64: colors [V,3] f32 -> image [H,W,3] f32
+    (bg_color where empty), normals [V,3] f32 -> normal [H,W,3] (not renormalised; 0), labels [V] uint8 -> label [H,W] uint8 (the corner
+    with the largest weight; 255).  An attribute and its image come together."""
+    tri, V, T = _triangles_i32(triangles, n_vertices)
+    V, T, H, W = _raster_sizes(V, T, H, W, "mesh_raster_resolve")
+    if any(tuple(x.shape) != (H, W) for x in (triangle_id, depth, mask)):
+        raise ValueError("mesh_raster_resolve: triangle_id, depth and mask are [H,W]")
+    for a, o, name, a_shape, o_shape in ((colors, image, "colors / image", (V, 3), (H, W, 3)), (normals, normal, "normals / normal", (V, 3), (H, W, 3)),
+                                         (labels, label, "labels / label", (V,), (H, W))):
+        if (a is None) != (o is None):
+            raise ValueError(f"mesh_raster_resolve: {name} come together")
+        if a is not None and (tuple(a.shape) != a_shape or tuple(o.shape) != o_shape):
+            raise ValueError(f"mesh_raster_resolve: {name} must be {list(a_shape)} and {list(o_shape)}")
+    _lib.check(_lib.lib().sn_rm_mesh_raster_resolve(_lib.dev(tri, "triangles", torch.int32), V, T, H, W, _lib.dev(colors, "colors"),
+                                                    _lib.dev(normals, "normals"), _lib.dev(labels, "labels", torch.uint8), float(bg_color),
+                                                    workspace.data_ptr(), workspace.numel(), _lib.dev(triangle_id, "triangle_id", torch.int32),
+                                                    _lib.dev(depth, "depth"), _lib.dev(mask, "mask", torch.uint8), _lib.dev(image, "image"),
+                                                    _lib.dev(normal, "normal"), _lib.dev(label, "label", torch.uint8), _lib.stream()),
+               "sn_rm_mesh_raster_resolve")
+
+
+def mesh_rasterize(mesh: dict, pose, intrinsics, H: int, W: int, near: float = 0.05, cull: bool = False, colors=None, labels=None, normals=None,
+                   bg_color: float = 1.0, small_max_pixels: int | None = None) -> dict:
+    """The mesh seen from one pinhole camera, with a depth buffer, exact to the bit: {"triangle_id" [H,W] int32 (-1 where empty), "depth" [H,W]
+    f32 (the camera-space -z of the surface, the field render's `depth` for get_rays' unnormalised directions; 0 where empty), "mask" [H,W]
+    uint8, "counts" int32 [4] = triangles drawn / dropped (a corner that is not placed, or a bad index) / degenerate / culled} and, with the
+    attribute, "image" [H,W,3] f32 from colors [V,3], "label" [H,W] uint8 from labels [V] uint8, "normal" [H,W,3] f32 from normals [V,3].
+
+    mesh: "vertices" [V,3] f32 and "triangles" [T,3] int32 on the device -- what isosurface() and NeRFRenderer.extract_mesh() return;
+    colors and labels default to the dict's own "colors" / "labels" where it has them; normals are taken only when given.  pose [4,4]
+    (cam2world) and intrinsics [4] = (fx, fy, cx, cy) in get_rays' convention: the pixel (i, j) has its centre at (i + 0.5, j + 0.5), the
+    camera looks along -z, y up.  Given as contiguous fp32 device tensors they are read by the kernels when they run: a captured graph
+    replays with whatever camera they hold then.  Anything else is copied to the device first.
+
+    A vertex nearer than `near`, outside the guard band of 2^14 pixels around the origin of the pixel grid, or not finite is not placed, and
+    a triangle with such a corner is dropped whole: there is no clipping.  cull drops the faces whose outside (counter-clockwise, as
+    isosurface() orients them) looks away.  One sample per pixel at its centre, the top-left rule on shared edges, nearest surface wins,
+    the lower triangle index at equal depth bits: the result depends on neither the order of the triangles nor the run, and equals
+    tests/mesh_raster_ref.py bit for bit; include/sanerf_hip.h has the definition.  Four launches, nothing is read back."""
+    vertices, triangles = _f32(mesh["vertices"]), mesh["triangles"]
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError(f"mesh_rasterize: vertices must be [V,3], got {tuple(vertices.shape)}")
+    tri, V, T = _triangles_i32(triangles, vertices.shape[0])
+    V, T, H, W = _raster_sizes(V, T, H, W, "mesh_rasterize")
+    near = _raster_near(near, "mesh_rasterize")
+    bg = float(bg_color)
+    if small_max_pixels is not None and not 0 <= int(small_max_pixels) <= RASTER_SMALL_MAX_LIMIT:
+        raise ValueError(f"mesh_rasterize: small_max_pixels = {small_max_pixels} must be in [0, 2^31)")
+    _lib.dev(vertices, "vertices")
+    dev = vertices.device
+    colors = mesh.get("colors") if colors is None else colors
+    labels = mesh.get("labels") if labels is None else labels
+    colors = None if colors is None else _f32(colors)
+    normals = None if normals is None else _f32(normals)
+    for a, name, shape in ((colors, "colors", (V, 3)), (normals, "normals", (V, 3)), (labels, "labels", (V,))):
+        if a is not None and tuple(a.shape) != shape:
+            raise ValueError(f"mesh_rasterize: {name} must be {list(shape)}, got {tuple(a.shape)}")
+    if labels is not None and labels.dtype != torch.uint8:
+        raise ValueError(f"mesh_rasterize: labels must be uint8, got {labels.dtype}")
+    pose, intrinsics = _raster_camera(pose, intrinsics, dev, "mesh_rasterize")
+    out = {"triangle_id": torch.empty(H, W, device=dev, dtype=torch.int32), "depth": torch.empty(H, W, device=dev, dtype=torch.float32),
+           "mask": torch.empty(H, W, device=dev, dtype=torch.uint8), "counts": torch.empty(4, device=dev, dtype=torch.int32)}
+    if colors is not None:
+        out["image"] = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+    if normals is not None:
+        out["normal"] = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+    if labels is not None:
+        out["label"] = torch.empty(H, W, device=dev, dtype=torch.uint8)
+    ws = mesh_raster_project(vertices, T, pose, intrinsics, H, W, near, out["counts"])
+    mesh_raster_draw(tri, V, H, W, ws, out["counts"], cull, small_max_pixels)
+    mesh_raster_resolve(tri, V, H, W, ws, out["triangle_id"], out["depth"], out["mask"], colors, out.get("image"), normals, out.get("normal"),
+                        labels.contiguous() if labels is not None else None, out.get("label"), bg)
+    return out
 
 
 # ---- vertex attributes: surface probes (mesh_attr.hip) -------------------------------------------------------------------------------------
