@@ -642,7 +642,8 @@ typedef struct sn_mlp_desc {
  * instead).  All zero = the defaults.  None of these changes WHAT is computed beyond fp32 round-off; the notes say which are bit-neutral. */
 enum { SN_MLP_AUTO = 0, SN_MLP_F16X3 = 1, SN_MLP_MFMA32 = 2, SN_MLP_VALU = 3, SN_MLP_F16X1 = 5 };
 enum { SN_EXP_NONE = 0, SN_EXP_ROLE_SPLIT = 1, SN_EXP_LDS_LEVEL0 = 2, SN_EXP_FINAL_ONE_WG = 3,
-       SN_EXP_MATRIX_CLUMPED = 4     /* linear-tail last stage: the matrix phase in its order before round 9 (tile by tile, vector work in clumps); bit-identical */ };
+       SN_EXP_MATRIX_CLUMPED = 4,    /* linear-tail last stage: the matrix phase in its order before round 9 (tile by tile, vector work in clumps); bit-identical */
+       SN_EXP_GATHER_CANONICAL = 5   /* last stage on packed levels: hashed-level gathers in the canonical corner order instead of grouped by cell parity (round 10); bit-identical */ };
 typedef struct sn_render_tuning {
     int32_t mlp_mode;            /* SN_MLP_AUTO: split-fp16 on the matrix cores unless cfg.mlp_exact_fp32; SN_MLP_F16X3 forces it (overrides the
                                   * range guard); SN_MLP_MFMA32: exact fp32 v_mfma_f32_32x32x2_f32; SN_MLP_VALU: vector-ALU fallback (A/B of the layouts);

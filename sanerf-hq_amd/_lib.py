@@ -35,7 +35,7 @@ class MlpDesc(C.Structure):
 
 
 MLP_AUTO, MLP_F16X3, MLP_MFMA32, MLP_VALU, MLP_F16X1 = 0, 1, 2, 3, 5              # sn_render_tuning.mlp_mode
-EXP_NONE, EXP_ROLE_SPLIT, EXP_LDS_LEVEL0, EXP_FINAL_ONE_WG, EXP_MATRIX_CLUMPED = 0, 1, 2, 3, 4                  # sn_render_tuning.experiment (experiments builds only)
+EXP_NONE, EXP_ROLE_SPLIT, EXP_LDS_LEVEL0, EXP_FINAL_ONE_WG, EXP_MATRIX_CLUMPED, EXP_GATHER_CANONICAL = 0, 1, 2, 3, 4, 5              # sn_render_tuning.experiment (experiments builds only)
 BUILD_EXPERIMENTS, BUILD_POISON_LDS = 1, 2                           # sn_build_flags()
 ADAM_ZERO_GRAD, ADAM_LAZY = 1, 2                                     # sn_adam_step flags
 ADAM_MULTI_MAX_TENSORS, ADAM_MULTI_MAX_GROUPS = 32, 8                # sn_adam_step_multi: per call

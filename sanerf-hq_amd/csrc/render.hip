@@ -216,6 +216,63 @@ constexpr bool xswap_level() {
                              // fewer quad-line pairs but 40 % more distinct lines per instruction and a select per swap: 6.43-6.45 ms); 2 = 16-lane rows
                              // (v_permlane16_swap: 6.19-6.20 ms, inside the noise of the default)
 #endif
+// PARITY (round 10, hashed levels of the FinalLv path): instruction (dy, dz) of a level used to fetch the corner (cell.y + dy, cell.z + dz),
+// so two rays in y-adjacent cells asked for the hash row they share in two different instructions.  Instead every lane puts into
+// instruction (a, b) the corner whose ABSOLUTE y has parity a and whose absolute z has parity b: lanes with an odd cell coordinate
+// exchange their two slots along that axis.  Requests for one row then meet in one instruction, where the address unit merges them
+// (n consecutive cells along an axis: n + 1 distinct rows instead of 2n).  The exchange is a lane-wise permutation of a lane's eight
+// requests, undone on the landed values before the blend (blend_level_par): every corner value reaches the same slot of the same
+// corner-ascending fma chain, so results are bit-identical.  The parity bits travel from issue to blend in the sign bits of the level's
+// pos[1] / pos[2] (fract never sets a sign), which costs no register.
+#ifndef SN_PARITY_FIRST
+#define SN_PARITY_FIRST 12   // first hashed level issued by parity: 9 / 11 / 12 / 13 / 14 measured (profiles/r10/README.md); levels 7-11 sit at the 8-line floor of
+                             // the address unit already (tools/gather_parity_table.py) and the exchange costs ~18 vector instructions per level
+#endif
+#ifndef SN_PARITY_AXES
+#define SN_PARITY_AXES 2     // 2 = y and z, 1 = z only
+#endif
+template <typename T, int AXIS, int l>
+constexpr bool parity_level() {
+    return l >= SN_PARITY_FIRST && (AXIS == 2 || (AXIS == 1 && SN_PARITY_AXES == 2));
+}
+__device__ __forceinline__ float parity_tag(float frac, uint32_t cell) {     // frac >= 0 with the cell's parity as its sign
+    return __uint_as_float(__float_as_uint(frac) | (cell << 31));
+}
+__device__ __forceinline__ bool parity_of(float tagged) { return (__float_as_uint(tagged) >> 31) != 0u; }
+#ifndef SN_PARITY_UNDO
+#define SN_PARITY_UNDO 1     // how odd lanes trade two registers (address terms at issue, landed values at the blend): 0 = two selects per pair (26 vector instructions per
+                             // level: slower than the canonical order, profiles/r10/undo_by_selects_ab.json), 1 = one v_swap_b32 per pair with the odd lanes as the exec mask (18)
+#endif
+// lanes with `odd` set trade a and b
+__device__ __forceinline__ void swap_if(bool odd, uint32_t &a, uint32_t &b) {
+#if SN_PARITY_UNDO == 1
+    const uint64_t m = __builtin_amdgcn_ballot_w64(odd);
+    uint64_t sv;
+    asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_swap_b32 %[a], %[b]\n\ts_mov_b64 exec, %[sv]" : [a] "+v"(a), [b] "+v"(b), [sv] "=&s"(sv) : [m] "s"(m) : "scc");
+#else
+    const uint32_t t = a;
+    a = odd ? b : a; b = odd ? t : b;
+#endif
+}
+__device__ __forceinline__ void swap_if4(bool odd, uint32_t &a0, uint32_t &b0, uint32_t &a1, uint32_t &b1, uint32_t &a2, uint32_t &b2, uint32_t &a3, uint32_t &b3) {
+#if SN_PARITY_UNDO == 1
+    const uint64_t m = __builtin_amdgcn_ballot_w64(odd);
+    uint64_t sv;
+    asm("s_and_saveexec_b64 %[sv], %[m]\n\t"
+        "v_swap_b32 %[a0], %[b0]\n\tv_swap_b32 %[a1], %[b1]\n\tv_swap_b32 %[a2], %[b2]\n\tv_swap_b32 %[a3], %[b3]\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [a0] "+v"(a0), [b0] "+v"(b0), [a1] "+v"(a1), [b1] "+v"(b1), [a2] "+v"(a2), [b2] "+v"(b2), [a3] "+v"(a3), [b3] "+v"(b3), [sv] "=&s"(sv)
+        : [m] "s"(m)
+        : "scc");
+#else
+    uint32_t t;
+    t = a0; a0 = odd ? b0 : a0; b0 = odd ? t : b0;
+    t = a1; a1 = odd ? b1 : a1; b1 = odd ? t : b1;
+    t = a2; a2 = odd ? b2 : a2; b2 = odd ? t : b2;
+    t = a3; a3 = odd ? b3 : a3; b3 = odd ? t : b3;
+#endif
+}
+
 __device__ __forceinline__ void half_wave_swap(uint32_t &a, uint32_t &b) {
 #if SN_XSWAP_MODE == 0
     // a' = [a.lanes0-31 | b.lanes0-31], b' = [a.lanes32-63 | b.lanes32-63]
@@ -393,6 +450,44 @@ __device__ __forceinline__ void blend_level_x(const float (&pos)[3], const Corne
     blend_level<T, C, PKW>(pos, own, acc);
 }
 
+// blend of a hashed FinalLv level issued with XSWAP and by parity (issue_level_lv<..., PY, PZ>): the half-wave exchange back, then lanes
+// whose cell was odd along z trade the landed values of slots i and i + 4, then those odd along y the slots i and i + 2 -- the issue
+// order undone in reverse -- and the unchanged blend on |pos| (the signs of pos[1] / pos[2] carried the parities)
+template <typename T, bool PY, bool PZ>
+__device__ __forceinline__ void blend_level_par(const float (&pos)[3], const Corner<T, 2> (&cv)[8], float (&acc)[2]) {
+    constexpr int NW = sizeof(T) == 2 ? 1 : 2;          // dwords per landed row: fp16 rows stay packed in v[0]
+    uint32_t w[8][NW];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+#pragma unroll
+        for (int c = 0; c < NW; ++c) {
+            uint32_t a = __float_as_uint(cv[2 * p].v[c]), b = __float_as_uint(cv[2 * p + 1].v[c]);
+            half_wave_swap(a, b);
+            w[2 * p][c] = a; w[2 * p + 1][c] = b;
+        }
+    }
+    float ap[3] = {pos[0], pos[1], pos[2]};
+    if constexpr (PZ) {
+        const bool odd = parity_of(pos[2]);
+        ap[2] = __builtin_fabsf(pos[2]);
+#pragma unroll
+        for (int c = 0; c < NW; ++c) swap_if4(odd, w[0][c], w[4][c], w[1][c], w[5][c], w[2][c], w[6][c], w[3][c], w[7][c]);
+    }
+    if constexpr (PY) {
+        const bool odd = parity_of(pos[1]);
+        ap[1] = __builtin_fabsf(pos[1]);
+#pragma unroll
+        for (int c = 0; c < NW; ++c) swap_if4(odd, w[0][c], w[2][c], w[1][c], w[3][c], w[4][c], w[6][c], w[5][c], w[7][c]);
+    }
+    Corner<T, 2> own[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if constexpr (sizeof(T) == 2) corner_set_half2(own[i], w[i][0]);
+        else { own[i].v[0] = __uint_as_float(w[i][0]); own[i].v[1] = __uint_as_float(w[i][1]); }
+    }
+    blend_level<T, 2, true>(ap, own, acc);
+}
+
 // Encodes all L levels; `emit(l, acc)` receives each level's C features (zeros when out of range).
 // K = number of leading dense levels (levels >= K are hashed); K < 0: level kind decided at run time.
 // Returns true for lanes whose coordinate is outside [0,1] (gridencoder.cu:105-130 writes zeros for them): the
@@ -489,8 +584,9 @@ struct FinalLv {
     const char *pair_base, *hash_base;
 };
 
-template <typename T, bool DENSE, bool FAST, bool XSWAP, int l>
+template <typename T, bool DENSE, bool FAST, bool XSWAP, int l, bool PY = false, bool PZ = false>
 __device__ __forceinline__ void issue_level_lv(const FinalLv &lv, const float (&x01)[3], float (&pos)[3], Corner<T, 2> (&cv)[8]) {
+    static_assert(!(PY || PZ) || (!DENSE && XSWAP), "parity grouping: hashed levels, in front of the half-wave exchange");
     constexpr uint32_t RB = 2u * (uint32_t)sizeof(T);              // bytes per table row (C = 2)
     const float rf = lv.res_f[l];
     uint32_t cell[3];
@@ -531,7 +627,18 @@ __device__ __forceinline__ void issue_level_lv(const FinalLv &lv, const float (&
             const uint32_t top = (uint32_t)lv.top_f[l];
             X1 = cell[0] < top ? X1 : X0; Y1 = cell[1] < top ? Y1 : Y0; Z1 = cell[2] < top ? Z1 : Z0;
         }
-        const uint32_t X0m = (X0 & mask) | ho, X1m = (X1 & mask) | ho, Y0m = Y0 & mask, Y1m = Y1 & mask, Z0m = Z0 & mask, Z1m = Z1 & mask;
+        const uint32_t X0m = (X0 & mask) | ho, X1m = (X1 & mask) | ho;
+        uint32_t Y0m = Y0 & mask, Y1m = Y1 & mask, Z0m = Z0 & mask, Z1m = Z1 & mask;
+        // PARITY: slot a of an axis takes the corner whose absolute coordinate has parity a -- odd cells trade their two terms (with the
+        // clamped neighbour both terms are equal: the rule is only a grouping); the parity rides in the sign of pos[d] to the blend
+        if constexpr (PY) {
+            pos[1] = parity_tag(pos[1], cell[1]);
+            swap_if(parity_of(pos[1]), Y0m, Y1m);
+        }
+        if constexpr (PZ) {
+            pos[2] = parity_tag(pos[2], cell[2]);
+            swap_if(parity_of(pos[2]), Z0m, Z1m);
+        }
         uint32_t offs[8];
 #pragma unroll
         for (uint32_t i = 0; i < 8; ++i) offs[i] = ((i & 1u) ? X1m : X0m) ^ ((i & 2u) ? Y1m : Y0m) ^ ((i & 4u) ? Z1m : Z0m);
@@ -555,28 +662,32 @@ __device__ __forceinline__ void issue_level_lv(const FinalLv &lv, const float (&
 }
 
 // levels L0 .. L0+G-1 (a "span": the gather groups of the final stage need not be equally long)
-template <typename T, int L0, int G, int K, bool FAST>
+// PAR = false: the canonical corner order on every level (the A/B partner of the parity order, experiments builds: SN_EXP_GATHER_CANONICAL)
+template <typename T, int L0, int G, int K, bool FAST, bool PAR = true>
 __device__ __forceinline__ void issue_span_lv(const FinalLv &lv, const float (&x01)[3], GroupRegs<T, 2, G> &r) {
     r.oob = false;
     static_for<0, G>([&](auto kk) {
         constexpr int k = decltype(kk)::value;
         constexpr int l = L0 + k;
         constexpr bool DENSE = l < K;
-        issue_level_lv<T, DENSE, FAST, xswap_level<T, DENSE ? 0 : 1, l>(), l>(lv, x01, r.pos[k], r.cv[k]);
+        issue_level_lv<T, DENSE, FAST, xswap_level<T, DENSE ? 0 : 1, l>(), l, PAR && !DENSE && parity_level<T, 1, l>(), PAR && !DENSE && parity_level<T, 2, l>()>(
+            lv, x01, r.pos[k], r.cv[k]);
     });
 }
-template <typename T, int G, int K, int GRP, bool FAST>
+template <typename T, int G, int K, int GRP, bool FAST, bool PAR = true>
 __device__ __forceinline__ void issue_group_lv(const FinalLv &lv, const float (&x01)[3], GroupRegs<T, 2, G> &r) {
-    issue_span_lv<T, GRP * G, G, K, FAST>(lv, x01, r);
+    issue_span_lv<T, GRP * G, G, K, FAST, PAR>(lv, x01, r);
 }
-template <typename T, int L0, int G, int K, typename Emit>
+template <typename T, int L0, int G, int K, bool PAR = true, typename Emit>
 __device__ __forceinline__ void blend_span(const GroupRegs<T, 2, G> &r, Emit emit) {
     static_for<0, G>([&](auto kk) {
         constexpr int k = decltype(kk)::value;
         constexpr int l = L0 + k;
         constexpr int KIND = K < 0 ? -1 : (l < K ? 0 : 1);
+        constexpr bool PY = PAR && KIND == 1 && parity_level<T, 1, l>(), PZ = PAR && KIND == 1 && parity_level<T, 2, l>();
         float acc[2];
-        if constexpr (xswap_level<T, KIND, l>()) blend_level_x<T, 2, true>(r.pos[k], r.cv[k], acc);
+        if constexpr (PY || PZ) blend_level_par<T, PY, PZ>(r.pos[k], r.cv[k], acc);
+        else if constexpr (xswap_level<T, KIND, l>()) blend_level_x<T, 2, true>(r.pos[k], r.cv[k], acc);
         else blend_level<T, 2, true>(r.pos[k], r.cv[k], acc);
         emit(l, acc);
     });
@@ -1835,7 +1946,10 @@ enum { MLP_VALU = 0, MLP_F32 = 1, MLP_F16X3 = 2 };
 // the plain one carries neither (one spilled register less in the march of the headline configuration)
 // PORD: the matrix phase of the linear-tail form in the order it had before grid_mlp_mfma16_l12_spread (tile by tile, vector work in clumps):
 // the A/B partner of the spread order, instantiated by experiments builds only (SN_EXP_MATRIX_CLUMPED)
-template <typename TT, int L, int C, int H1, int H2, int NOUT, int VH, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3, bool PORD = false>
+// CANON: the hashed levels of the FinalLv path in the canonical corner order instead of by cell parity (round 10): the A/B partner of the parity
+// order, instantiated by experiments builds only (SN_EXP_GATHER_CANONICAL)
+template <typename TT, int L, int C, int H1, int H2, int NOUT, int VH, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3, bool PORD = false,
+          bool CANON = false>
 __global__ __launch_bounds__(256, MODE == MLP_VALU ? 1 : SN_FINAL_WAVES) void k_final_stage(FinalArgs a) {
     SN_POISON_ALL();
     static_assert(NP == 3 || (LT && !L0L && !AUX), "reduced-product MLP forms: plain linear-tail instantiations only");
@@ -2001,9 +2115,9 @@ __global__ __launch_bounds__(256, MODE == MLP_VALU ? 1 : SN_FINAL_WAVES) void k_
                     static_for<1, SP::N>([&](auto gg) {
                         constexpr int SPAN = decltype(gg)::value, L0 = SP::B[SPAN], G = SP::B[SPAN + 1] - L0;
                         GroupRegs<TT, 2, G> gr;
-                        issue_span_lv<TT, L0, G, K, FAST>(a.lv, x01, gr);
+                        issue_span_lv<TT, L0, G, K, FAST, !CANON>(a.lv, x01, gr);
                         __builtin_amdgcn_sched_barrier(0);
-                        blend_span<TT, L0, G, K>(gr, emit);
+                        blend_span<TT, L0, G, K, !CANON>(gr, emit);
                         __builtin_amdgcn_sched_barrier(0);
                     });
                 };
@@ -2480,7 +2594,7 @@ __global__ __launch_bounds__(256) void k_final_stage_any(FinalArgs a, AnyShape s
 // padding dwords of the wave's two feature-slab images, the per-sample records reuse the slab rows: no extra LDS.
 constexpr uint32_t CMP_KMAX = 4;
 
-template <typename TT, int K>
+template <typename TT, int K, bool CANON = false>
 __global__ __launch_bounds__(256, 2) void k_final_stage_cmp(FinalArgs a) {
     SN_POISON_ALL();
     constexpr int L = 16, GEO = 15, NSH = 16, NCOL = GEO + NSH, VH = 32, PG = 4, IN = 32;
@@ -2590,9 +2704,9 @@ __global__ __launch_bounds__(256, 2) void k_final_stage_cmp(FinalArgs a) {
             static_for<1, L / PG>([&](auto gg) {
                 constexpr int GRP = decltype(gg)::value;
                 GroupRegs<TT, 2, PG> gr;
-                issue_group_lv<TT, PG, K, GRP, FAST>(a.lv, x01, gr);
+                issue_group_lv<TT, PG, K, GRP, FAST, !CANON>(a.lv, x01, gr);
                 __builtin_amdgcn_sched_barrier(0);
-                blend_group<TT, 2, PG, K, GRP>(gr, emit);
+                blend_span<TT, GRP * PG, PG, K, !CANON>(gr, emit);
                 __builtin_amdgcn_sched_barrier(0);
             });
         };
@@ -3547,6 +3661,7 @@ struct FinalRoute {
     bool aux = false, eo = false;          // AUX (last-stage weights out / early stop), EO (exact early-out)
     int np = 3;                            // products per split multiply
     bool clumped = false;                  // LT: the matrix phase in its clumped order (SN_EXP_MATRIX_CLUMPED, experiments builds)
+    bool canon = false;                    // FinalLv kernels: hashed levels in the canonical corner order (SN_EXP_GATHER_CANONICAL, experiments builds)
     uint32_t grid = 0, block = 256;
     size_t lds = 0;                        // dynamic LDS bytes of the launch
     const char *name = "";                 // what sn_launch_info reports, with the two figures below
@@ -3648,6 +3763,9 @@ static void plan_final(const sn_render_cfg *cfg, const sn_render_io *io, RenderR
     f.eo = cfg->tuning.exact_early_out == 2;
     const int xp = experiment_of(cfg);
     const bool f16x3 = r->mlp_mode == MLP_F16X3;
+    // SN_EXP_GATHER_CANONICAL (round 10): the A/B partner of the parity order of the hashed-level gathers, same bits; the linear-tail (full
+    // product form), per-sample K = 5 and compaction kernels carry it
+    f.canon = xp == SN_EXP_GATHER_CANONICAL;
     if (r->is_any) {      // sizes at run time.  (io->head_stride is accepted here although this kernel never writes the rgb | depth columns:
                           //  ADVICE.md; plan_render's head_stride check is the place to refuse it)
         f.family = FinalRoute::ANY; f.name = "k_final_stage_any";
@@ -3899,12 +4017,16 @@ static PropKern prop_kernel(const PropRoute &p) {
 
 using FinalKern = void (*)(FinalArgs);
 // k_final_stage at the reference network's sizes
-template <typename TT, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3, bool PORD = false>
-static FinalKern fs() { return k_final_stage<TT, 16, 2, 64, 64, 16, 32, MODE, K, AUX, LT, L0L, EO, NP, PORD>; }
+template <typename TT, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3, bool PORD = false, bool CANON = false>
+static FinalKern fs() { return k_final_stage<TT, 16, 2, 64, 64, 16, 32, MODE, K, AUX, LT, L0L, EO, NP, PORD, CANON>; }
 template <typename TT> static FinalKern final_kernel_of(const FinalRoute &f) {
     constexpr bool half = std::is_same<TT, __half>::value;
     switch (f.family) {
+#ifdef SN_EXPERIMENTS
+        case FinalRoute::CMP: return f.canon ? k_final_stage_cmp<TT, 5, true> : k_final_stage_cmp<TT, 5>;
+#else
         case FinalRoute::CMP: return k_final_stage_cmp<TT, 5>;
+#endif
 #ifdef SN_EXPERIMENTS
         case FinalRoute::RS: return k_final_stage_rs<TT, 5>;
         case FinalRoute::LT_L0:
@@ -3921,11 +4043,19 @@ template <typename TT> static FinalKern final_kernel_of(const FinalRoute &f) {
                 if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, true, true, false, true, 3, true>() : fs<TT, MLP_F16X3, 5, true, true, false, false, 3, true>();
                 return f.eo ? fs<TT, MLP_F16X3, 5, false, true, false, true, 3, true>() : fs<TT, MLP_F16X3, 5, false, true, false, false, 3, true>();
             }
+            if (f.canon && f.np == 3) {
+                if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, false, true, false, true, 3, false, true>() : fs<TT, MLP_F16X3, 7, false, true, false, false, 3, false, true>();
+                if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, true, true, false, true, 3, false, true>() : fs<TT, MLP_F16X3, 5, true, true, false, false, 3, false, true>();
+                return f.eo ? fs<TT, MLP_F16X3, 5, false, true, false, true, 3, false, true>() : fs<TT, MLP_F16X3, 5, false, true, false, false, 3, false, true>();
+            }
 #endif
             if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, false, true, false, true>() : fs<TT, MLP_F16X3, 7, false, true, false, false>();
             if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, true, true, false, true>() : fs<TT, MLP_F16X3, 5, true, true, false, false>();
             return f.eo ? fs<TT, MLP_F16X3, 5, false, true, false, true>() : fs<TT, MLP_F16X3, 5, false, true, false, false>();
         case FinalRoute::PER_SAMPLE:      // the plain instantiation unless the extras are on
+#ifdef SN_EXPERIMENTS
+            if (f.canon && f.K == 5) return f.aux ? fs<TT, MLP_F16X3, 5, true, false, false, false, 3, false, true>() : fs<TT, MLP_F16X3, 5, false, false, false, false, 3, false, true>();
+#endif
             if (f.K == 5) return f.aux ? fs<TT, MLP_F16X3, 5, true>() : fs<TT, MLP_F16X3, 5, false>();
             return f.aux ? fs<TT, MLP_F16X3, -1, true>() : fs<TT, MLP_F16X3, -1, false>();
         case FinalRoute::MFMA32: return fs<TT, MLP_F32, -1, true>();

@@ -138,7 +138,7 @@ __device__ __forceinline__ void issue_span_into(const FinalLv &lv, const float (
         constexpr int k = decltype(kk)::value;
         constexpr int l = L0 + k;
         constexpr bool DENSE = l < K;
-        issue_level_lv<T, DENSE, FAST, xswap_level<T, DENSE ? 0 : 1, l>(), l>(lv, x01, r.pos[k], r.cv[k]);
+        issue_level_lv<T, DENSE, FAST, xswap_level<T, DENSE ? 0 : 1, l>(), l, !DENSE && parity_level<T, 1, l>(), !DENSE && parity_level<T, 2, l>()>(lv, x01, r.pos[k], r.cv[k]);
     });
 }
 template <typename T, int L0, int G, int K, int MG, typename Emit>
@@ -147,8 +147,10 @@ __device__ __forceinline__ void blend_span_from(const GroupRegs<T, 2, MG> &r, Em
         constexpr int k = decltype(kk)::value;
         constexpr int l = L0 + k;
         constexpr int KIND = l < K ? 0 : 1;
+        constexpr bool PY = KIND == 1 && parity_level<T, 1, l>(), PZ = KIND == 1 && parity_level<T, 2, l>();
         float acc[2];
-        if constexpr (xswap_level<T, KIND, l>()) blend_level_x<T, 2, true>(r.pos[k], r.cv[k], acc);
+        if constexpr (PY || PZ) blend_level_par<T, PY, PZ>(r.pos[k], r.cv[k], acc);
+        else if constexpr (xswap_level<T, KIND, l>()) blend_level_x<T, 2, true>(r.pos[k], r.cv[k], acc);
         else blend_level<T, 2, true>(r.pos[k], r.cv[k], acc);
         emit(std::integral_constant<int, l>{}, acc);
     });
