@@ -7,7 +7,8 @@
 // tetrahedron and their orientation come from a 6 x 16 table generated at compile time (mesh_table.h).  Mesh vertices are numbered by owning
 // lattice vertex then slot, triangles by cell then tetrahedron then triangle.
 //
-// Launch plan (two launches for the count, one for the emit; no workgroup waits on another, nothing is placed by an atomic):
+// Launch plan: the segment pattern of mesh_common.h with two totals a segment (two launches for the count, one for the emit; no workgroup
+// waits on another, nothing is placed by an atomic):
 //   k_iso_classify  one wave per SEGMENT of 1024 consecutive lattice vertices (z fastest: coalesced rows), 16 steps of 64.  A lane loads the
 //                   column of its vertex -- f at (x,y), (x,y+1), (x+1,y), (x+1,y+1), same z -- and takes the z+1 column's inside bits from the
 //                   next lane (lane 63: from lane 0 of the next step, whose loads were issued two steps earlier): 4 loads per lattice
@@ -19,15 +20,10 @@
 //                   crossing edges (f_a, f_b; the gradients).  id(v, e) = segment base + rank[v] + popcount(byte[v] & ((1 << e) - 1)).
 // Every store of the emit is guarded by cap_v / cap_t; every load stays inside the lattice by the kernel's own range tests.
 // Workspace: 8 bytes per segment, 4 bytes + 1 byte per lattice vertex.  Plain vector loads and stores.
-#include "sn_common.h"
-#include "sn_wave.h"
+#include "mesh_common.h"
 #include "mesh_table.h"
 
 namespace sn {
-
-constexpr uint32_t ISO_SEG = 1024u;        // lattice vertices per wave = the unit of the scan
-constexpr uint32_t ISO_SEG_LOG2 = 10u;
-constexpr uint32_t ISO_WAVES = 4u;         // waves (segments) per workgroup
 
 constexpr TetTable H_TET = make_tet_table();
 static_assert(!H_TET.bad, "a triangle of the marching-tetrahedra table has no orientation (zero dot product)");
@@ -36,8 +32,6 @@ __constant__ TetTable c_tet = H_TET;
 struct IsoDims { uint32_t nx, ny, nz, sx, V; };      // sx = ny * nz (the x stride); V = nx * ny * nz < 2^31
 
 struct IsoLayout { size_t totals, base, mask, bytes; uint32_t nseg; };
-
-static inline size_t align16(size_t n) { return (n + 15u) & ~(size_t)15u; }
 
 static inline bool iso_dims(uint32_t nx, uint32_t ny, uint32_t nz, IsoDims *d) {
     if (nx < 2u || ny < 2u || nz < 2u) return false;
@@ -49,7 +43,7 @@ static inline bool iso_dims(uint32_t nx, uint32_t ny, uint32_t nz, IsoDims *d) {
 
 static inline IsoLayout iso_layout(const IsoDims &d) {
     IsoLayout l;
-    l.nseg = div_up(d.V, ISO_SEG);
+    l.nseg = div_up(d.V, MESH_SEG);
     l.totals = 0;
     l.base = align16((size_t)l.nseg * 8u);
     l.mask = l.base + (size_t)d.V * 4u;
@@ -117,12 +111,12 @@ __device__ __forceinline__ uint32_t block_state(const BlockLoads &l, float iso) 
 __global__ __launch_bounds__(256) void k_iso_classify(const float *__restrict__ f, IsoDims d, float iso, uint8_t *__restrict__ mask,
                                                       uint32_t *__restrict__ rank, uint2 *__restrict__ totals, uint32_t nseg) {
     SN_POISON_ALL();
-    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * ISO_WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * MESH_WAVES + (threadIdx.x >> 6);
     if (seg >= nseg) return;               // wave-uniform; the kernel has no barrier
-    const uint32_t v0 = seg * ISO_SEG + lane;
+    const uint32_t v0 = seg * MESH_SEG + lane;
     uint32_t vb = 0u, tb = 0u;
     uint32_t cur = block_state(block_issue(f, v0, d), iso), nxt = block_state(block_issue(f, v0 + 64u, d), iso);
-    for (uint32_t it = 0; it < ISO_SEG / 64u; ++it) {
+    for (uint32_t it = 0; it < MESH_SEG / 64u; ++it) {
         const uint32_t v = v0 + it * 64u;
         const BlockLoads ahead = block_issue(f, v + 128u, d);              // two blocks ahead (past the segment's end: the next segment's, unused)
         // the z+1 column: the next lane's, and for lane 63 the next block's lane 0 (same x, y wherever z+1 is in range)
@@ -156,34 +150,12 @@ __global__ __launch_bounds__(256) void k_iso_classify(const float *__restrict__ 
 // Exclusive scan of the segment totals, in place; one workgroup of 1024.  counts[0..1] = the grand totals, saturated at 2^32 - 1.
 __global__ __launch_bounds__(1024) void k_iso_scan(uint2 *__restrict__ totals, uint32_t nseg, uint32_t *__restrict__ counts) {
     SN_POISON_ALL();
-    __shared__ uint32_t wv[16], wt[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint64_t carry_v = 0ull, carry_t = 0ull;
-    for (uint32_t s0 = 0; s0 < nseg; s0 += 1024u) {                      // whole tiles: every lane reaches the shuffles and the barriers
-        const uint32_t i = s0 + tid;
-        const uint2 c = i < nseg ? totals[i] : make_uint2(0u, 0u);
-        uint32_t sv = c.x, st = c.y;
-#pragma unroll
-        for (int dlt = 1; dlt < 64; dlt <<= 1) {
-            const uint32_t uv = (uint32_t)__shfl_up((int)sv, dlt), ut = (uint32_t)__shfl_up((int)st, dlt);
-            if (lane >= (uint32_t)dlt) { sv += uv; st += ut; }
-        }
-        if (lane == 63u) { wv[wave] = sv; wt[wave] = st; }
-        __syncthreads();
-        uint32_t ov = 0u, ot = 0u, tv = 0u, tt = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < 16u; ++w) {
-            const uint32_t a = wv[w], b = wt[w];
-            if (w < wave) { ov += a; ot += b; }
-            tv += a; tt += b;
-        }
-        if (i < nseg) totals[i] = make_uint2((uint32_t)(carry_v + ov + (sv - c.x)), (uint32_t)(carry_t + ot + (st - c.y)));
-        carry_v += tv; carry_t += tt;
-        __syncthreads();
-    }
-    if (tid == 0u) {
-        counts[0] = carry_v > 0xffffffffull ? 0xffffffffu : (uint32_t)carry_v;
-        counts[1] = carry_t > 0xffffffffull ? 0xffffffffu : (uint32_t)carry_t;
+    __shared__ uint32_t ws[2 * 16];
+    uint64_t total[2];
+    workgroup_exclusive_scan<2>(&totals->x, nseg, ws, total);
+    if (threadIdx.x == 0u) {
+        counts[0] = total[0] > 0xffffffffull ? 0xffffffffu : (uint32_t)total[0];
+        counts[1] = total[1] > 0xffffffffull ? 0xffffffffu : (uint32_t)total[1];
     }
 }
 
@@ -203,16 +175,16 @@ __global__ __launch_bounds__(256) void k_iso_emit(const float *__restrict__ f, I
                                                   const uint2 *__restrict__ segbase, uint32_t nseg, float *__restrict__ vertices,
                                                   float *__restrict__ normals, int32_t *__restrict__ triangles, uint32_t cap_v, uint32_t cap_t) {
     SN_POISON_ALL();
-    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * ISO_WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * MESH_WAVES + (threadIdx.x >> 6);
     if (seg >= nseg) return;               // wave-uniform; the kernel has no barrier
     const uint2 sb = segbase[seg];
     uint32_t tb = sb.y;
-    const uint32_t v0 = seg * ISO_SEG + lane;
+    const uint32_t v0 = seg * MESH_SEG + lane;
     uint32_t byte_next = v0 < d.V ? (uint32_t)mask[v0] : 0u;
-    for (uint32_t it = 0; it < ISO_SEG / 64u; ++it) {
+    for (uint32_t it = 0; it < MESH_SEG / 64u; ++it) {
         const uint32_t v = v0 + it * 64u;
         const uint32_t byte = byte_next;
-        byte_next = (it + 1u < ISO_SEG / 64u && v + 64u < d.V) ? (uint32_t)mask[v + 64u] : 0u;      // one block ahead of the ballots
+        byte_next = (it + 1u < MESH_SEG / 64u && v + 64u < d.V) ? (uint32_t)mask[v + 64u] : 0u;      // one block ahead of the ballots
         const uint32_t m = byte & 0x7fu;
         uint32_t x = 0u, y = 0u, z = 0u;
         bool rx = false, ry = false, rz = false;
@@ -271,7 +243,7 @@ __global__ __launch_bounds__(256) void k_iso_emit(const float *__restrict__ f, I
                     for (int q = 0; q < 3; ++q) {
                         const uint32_t ed = (w >> (6 * q)) & 63u, oc = ed & 7u, sl = ed >> 3;
                         const uint32_t o = v + (oc & 1u) * d.sx + ((oc >> 1) & 1u) * d.nz + ((oc >> 2) & 1u);
-                        tri[q] = (int32_t)(segbase[o >> ISO_SEG_LOG2].x + rank[o] + (uint32_t)__popc((uint32_t)mask[o] & ((1u << sl) - 1u)));
+                        tri[q] = (int32_t)(segbase[o >> MESH_SEG_LOG2].x + rank[o] + (uint32_t)__popc((uint32_t)mask[o] & ((1u << sl) - 1u)));
                     }
                 }
                 ++my_t;
@@ -326,9 +298,7 @@ static int iso_check(const char *who, const void *volume, uint32_t nx, uint32_t 
     SN_UNSUPPORTED(iso_dims(nx, ny, nz, d), "%s: a lattice of %u x %u x %u is not supported (every dimension >= 2, fewer than 2^31 vertices)", who,
                    nx, ny, nz);
     *l = iso_layout(*d);
-    if (bytes < l->bytes) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, bytes, l->bytes); return SN_ERR_WORKSPACE; }
-    SN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, "%s: the workspace must be 16-byte aligned", who);
-    return SN_OK;
+    return workspace_check(who, workspace, bytes, l->bytes);
 }
 
 extern "C" int sn_rm_isosurface_count(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void *workspace, size_t workspace_bytes,
@@ -340,7 +310,7 @@ extern "C" int sn_rm_isosurface_count(const float *volume, uint32_t nx, uint32_t
     if (rc != SN_OK) return rc;
     uint8_t *ws = (uint8_t *)workspace;
     uint2 *totals = (uint2 *)(ws + l.totals);
-    hipLaunchKernelGGL(k_iso_classify, dim3(div_up(l.nseg, ISO_WAVES)), dim3(256), 0, (hipStream_t)stream, volume, d, iso, ws + l.mask,
+    hipLaunchKernelGGL(k_iso_classify, dim3(div_up(l.nseg, MESH_WAVES)), dim3(256), 0, (hipStream_t)stream, volume, d, iso, ws + l.mask,
                        (uint32_t *)(ws + l.base), totals, l.nseg);
     SN_LAUNCH_CHECK("k_iso_classify");
     hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(1024), 0, (hipStream_t)stream, totals, l.nseg, counts);
@@ -360,7 +330,7 @@ extern "C" int sn_rm_isosurface_emit(const float *volume, uint32_t nx, uint32_t 
     const int rc = iso_check("isosurface_emit", volume, nx, ny, nz, workspace, workspace_bytes, &d, &l);
     if (rc != SN_OK) return rc;
     const uint8_t *ws = (const uint8_t *)workspace;
-    hipLaunchKernelGGL(k_iso_emit, dim3(div_up(l.nseg, ISO_WAVES)), dim3(256), 0, (hipStream_t)stream, volume, d, iso, origin[0], origin[1],
+    hipLaunchKernelGGL(k_iso_emit, dim3(div_up(l.nseg, MESH_WAVES)), dim3(256), 0, (hipStream_t)stream, volume, d, iso, origin[0], origin[1],
                        origin[2], step[0], step[1], step[2], ws + l.mask, (const uint32_t *)(ws + l.base), (const uint2 *)(ws + l.totals), l.nseg,
                        vertices, cap_v ? normals : nullptr, triangles, cap_v, cap_t);
     SN_LAUNCH_CHECK("k_iso_emit");

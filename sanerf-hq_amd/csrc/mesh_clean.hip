@@ -27,36 +27,29 @@
 // Statistics.  Integer atomicAdd at the root (order-independent, so deterministic), aggregated per wave: on a real mesh nearly every lane
 // of a wave has the same root, so the wave's lanes are grouped by root and one lane per group adds the group's size.
 //
-// Filter.  The segment pattern of k_iso_classify / k_iso_scan, once over the vertices (keep = the root of labels[v] is selected) and once
-// over the triangles (valid, and its first corner is kept): one wave per 1024 elements writes [keep << 31 | rank inside the segment] and
-// the segment's total; one workgroup scans both lists of totals and writes counts = {V', T'}.  The emit reads the keep flags, the ranks
+// Filter.  The segment pattern of mesh_common.h, once over the vertices (keep = the root of labels[v] is selected) and once over the
+// triangles (valid, and its first corner is kept); one workgroup scans both lists of totals and writes counts = {V', T'} (both below
+// 2^31).  The emit reads the keep flags, the ranks
 // and the scanned totals from the workspace, and `triangles`; never `labels`.  Nothing is placed by an atomic; every store of the emit is
 // guarded by cap_v / cap_t and every index is range-tested before it addresses anything.
 // Plain vector loads, plain vector stores and integer atomics only.
-#include "sn_common.h"
-#include "sn_wave.h"
+#include "mesh_common.h"
 
 namespace sn {
 
-constexpr uint32_t CLEAN_SEG = 1024u;      // elements per wave = the unit of the scan
-constexpr uint32_t CLEAN_SEG_LOG2 = 10u;
-constexpr uint32_t CLEAN_WAVES = 4u;       // waves (segments) per workgroup
-constexpr uint32_t CLEAN_KEEP = 0x80000000u;
 constexpr uint32_t CLEAN_MAX_ROUNDS = 4096u;
 
 struct CleanLayout { size_t vtot, ttot, vrank, trank, bytes; uint32_t nsegv, nsegt; };
 
-static inline size_t clean_align16(size_t n) { return (n + 15u) & ~(size_t)15u; }
-
 static inline CleanLayout clean_layout(uint32_t V, uint32_t T) {
     CleanLayout l;
-    l.nsegv = div_up(V, CLEAN_SEG);
-    l.nsegt = div_up(T, CLEAN_SEG);
+    l.nsegv = div_up(V, MESH_SEG);
+    l.nsegt = div_up(T, MESH_SEG);
     l.vtot = 0;
-    l.ttot = l.vtot + clean_align16((size_t)l.nsegv * 4u);
-    l.vrank = l.ttot + clean_align16((size_t)l.nsegt * 4u);
-    l.trank = l.vrank + clean_align16((size_t)V * 4u);
-    l.bytes = l.trank + clean_align16((size_t)T * 4u);
+    l.ttot = l.vtot + align16((size_t)l.nsegv * 4u);
+    l.vrank = l.ttot + align16((size_t)l.nsegt * 4u);
+    l.trank = l.vrank + align16((size_t)V * 4u);
+    l.bytes = l.trank + align16((size_t)T * 4u);
     return l;
 }
 
@@ -78,9 +71,8 @@ __global__ __launch_bounds__(256) void k_cc_hook(const int32_t *__restrict__ tri
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     bool lowered = false;
     if (t < T) {
-        const int32_t *tri = triangles + (size_t)t * 3u;
-        const uint32_t x[3] = {(uint32_t)tri[0], (uint32_t)tri[1], (uint32_t)tri[2]};
-        if (x[0] < V && x[1] < V && x[2] < V) {
+        uint32_t x[3];
+        if (triangle_corners(triangles, t, V, x)) {
             const uint32_t l[3] = {label_of(labels, x[0]), label_of(labels, x[1]), label_of(labels, x[2])};
             const uint32_t m = umin(l[0], umin(l[1], l[2]));
 #pragma unroll
@@ -140,10 +132,9 @@ __global__ __launch_bounds__(256) void k_cc_triangle_counts(const int32_t *__res
     bool valid = false;
     uint32_t root = 0u;
     if (t < T) {
-        const int32_t *tri = triangles + (size_t)t * 3u;
-        const uint32_t a = (uint32_t)tri[0], b = (uint32_t)tri[1], c = (uint32_t)tri[2];
-        valid = a < V && b < V && c < V;
-        if (valid) root = label_of(labels, a);
+        uint32_t c[3];
+        valid = triangle_corners(triangles, t, V, c);
+        if (valid) root = label_of(labels, c[0]);
     }
     wave_add_by_key(triangle_counts, root, valid);
 }
@@ -169,24 +160,13 @@ __global__ __launch_bounds__(256) void k_clean_rank_vertices(uint32_t V, const i
                                                              uint32_t min_triangles, const uint64_t *__restrict__ min_key,
                                                              uint32_t *__restrict__ rank, uint32_t *__restrict__ totals, uint32_t nseg) {
     SN_POISON_ALL();
-    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * CLEAN_WAVES + (threadIdx.x >> 6);
-    if (seg >= nseg) return;               // wave-uniform; the kernel has no barrier
     const uint64_t mk = *min_key;
     const uint32_t mt = min_triangles > 1u ? min_triangles : 1u;
-    uint32_t base = 0u;
-    for (uint32_t it = 0; it < CLEAN_SEG / 64u; ++it) {
-        const uint32_t v = seg * CLEAN_SEG + it * 64u + lane;
-        bool keep = false;
-        if (v < V) {
-            const uint32_t r = label_of(labels, v);
-            const int32_t tc = triangle_counts[r];
-            keep = tc > 0 && (uint32_t)tc >= mt && (((uint64_t)(uint32_t)tc << 32) | (uint64_t)(0xFFFFFFFFu - r)) >= mk;
-        }
-        const uint64_t m = __ballot(keep);
-        if (v < V) rank[v] = (keep ? CLEAN_KEEP : 0u) | (base + lanes_below(m));
-        base += (uint32_t)__popcll(m);
-    }
-    if (lane == 0u) totals[seg] = base;
+    segment_flag_rank(V, nseg, rank, totals, [&](uint32_t v) {
+        const uint32_t r = label_of(labels, v);
+        const int32_t tc = triangle_counts[r];
+        return tc > 0 && (uint32_t)tc >= mt && (((uint64_t)(uint32_t)tc << 32) | (uint64_t)(0xFFFFFFFFu - r)) >= mk;
+    });
 }
 
 // The same over the triangles: kept iff valid and its first corner is kept (vrank is the finished output of the launch before).
@@ -194,59 +174,18 @@ __global__ __launch_bounds__(256) void k_clean_rank_triangles(const int32_t *__r
                                                               const uint32_t *__restrict__ vrank, uint32_t *__restrict__ rank,
                                                               uint32_t *__restrict__ totals, uint32_t nseg) {
     SN_POISON_ALL();
-    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * CLEAN_WAVES + (threadIdx.x >> 6);
-    if (seg >= nseg) return;               // wave-uniform; the kernel has no barrier
-    uint32_t base = 0u;
-    for (uint32_t it = 0; it < CLEAN_SEG / 64u; ++it) {
-        const uint32_t t = seg * CLEAN_SEG + it * 64u + lane;
-        bool keep = false;
-        if (t < T) {
-            const int32_t *tri = triangles + (size_t)t * 3u;
-            const uint32_t a = (uint32_t)tri[0], b = (uint32_t)tri[1], c = (uint32_t)tri[2];
-            if (a < V && b < V && c < V) keep = (vrank[a] & CLEAN_KEEP) != 0u;
-        }
-        const uint64_t m = __ballot(keep);
-        if (t < T) rank[t] = (keep ? CLEAN_KEEP : 0u) | (base + lanes_below(m));
-        base += (uint32_t)__popcll(m);
-    }
-    if (lane == 0u) totals[seg] = base;
-}
-
-// Exclusive scan of n totals in place by the whole workgroup of 1024 (every lane calls it); returns the grand total (< 2^31).
-__device__ __forceinline__ uint32_t clean_scan_list(uint32_t *__restrict__ totals, uint32_t n, uint32_t *ws) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t carry = 0u;
-    for (uint32_t s0 = 0; s0 < n; s0 += 1024u) {       // whole tiles: every lane reaches the shuffles and the barriers
-        const uint32_t i = s0 + tid;
-        const uint32_t c = i < n ? totals[i] : 0u;
-        uint32_t s = c;
-#pragma unroll
-        for (int dlt = 1; dlt < 64; dlt <<= 1) {
-            const uint32_t u = (uint32_t)__shfl_up((int)s, dlt);
-            if (lane >= (uint32_t)dlt) s += u;
-        }
-        if (lane == 63u) ws[wave] = s;
-        __syncthreads();
-        uint32_t before = 0u, all = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < 16u; ++w) {
-            const uint32_t a = ws[w];
-            if (w < wave) before += a;
-            all += a;
-        }
-        if (i < n) totals[i] = carry + before + (s - c);
-        carry += all;
-        __syncthreads();
-    }
-    return carry;
+    segment_flag_rank(T, nseg, rank, totals, [&](uint32_t t) {
+        uint32_t c[3];
+        return triangle_corners(triangles, t, V, c) && (vrank[c[0]] & MESH_KEEP) != 0u;
+    });
 }
 
 __global__ __launch_bounds__(1024) void k_clean_scan(uint32_t *__restrict__ vtot, uint32_t nsegv, uint32_t *__restrict__ ttot, uint32_t nsegt,
                                                      uint32_t *__restrict__ counts) {
     SN_POISON_ALL();
     __shared__ uint32_t ws[16];
-    const uint32_t nv = clean_scan_list(vtot, nsegv, ws);
-    const uint32_t nt = clean_scan_list(ttot, nsegt, ws);
+    const uint32_t nv = (uint32_t)workgroup_exclusive_scan(vtot, nsegv, ws);
+    const uint32_t nt = (uint32_t)workgroup_exclusive_scan(ttot, nsegt, ws);
     if (threadIdx.x == 0u) { counts[0] = nv; counts[1] = nt; }
 }
 
@@ -258,8 +197,8 @@ __global__ __launch_bounds__(256) void k_clean_emit_vertices(uint32_t V, const u
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;
     if (v >= V) return;
     const uint32_t w = vrank[v];
-    if (!(w & CLEAN_KEEP)) return;
-    const uint32_t id = vbase[v >> CLEAN_SEG_LOG2] + (w & ~CLEAN_KEEP);
+    if (!(w & MESH_KEEP)) return;
+    const uint32_t id = segment_index(vbase, w, v);
     if (id >= cap_v) return;
     const uint32_t *p = vertices + (size_t)v * 3u;
     uint32_t *q = out_vertices + (size_t)id * 3u;
@@ -280,29 +219,26 @@ __global__ __launch_bounds__(256) void k_clean_emit_triangles(const int32_t *__r
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= T) return;
     const uint32_t w = trank[t];
-    if (!(w & CLEAN_KEEP)) return;
-    const uint32_t id = tbase[t >> CLEAN_SEG_LOG2] + (w & ~CLEAN_KEEP);
+    if (!(w & MESH_KEEP)) return;
+    const uint32_t id = segment_index(tbase, w, t);
     if (id >= cap_t) return;
-    const int32_t *tri = triangles + (size_t)t * 3u;
+    uint32_t x[3];
+    triangle_corners(triangles, t, V, x);
     int32_t *out = out_triangles + (size_t)id * 3u;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const uint32_t x = (uint32_t)tri[q];           // range-tested again: `triangles` may have changed since the count
-        out[q] = x < V ? (int32_t)(vbase[x >> CLEAN_SEG_LOG2] + (vrank[x] & ~CLEAN_KEEP)) : -1;
-    }
+    for (int q = 0; q < 3; ++q)                        // range-tested again, corner by corner: `triangles` may have changed since the count
+        out[q] = x[q] < V ? (int32_t)segment_index(vbase, vrank[x[q]], x[q]) : -1;
 }
 
 }  // namespace sn
 
 using namespace sn;
 
-static bool clean_sizes_ok(uint32_t V, uint32_t T) { return V < (1u << 31) && T < (1u << 31); }
-
-#define CLEAN_SIZES(who) SN_UNSUPPORTED(clean_sizes_ok(V, T), "%s: V = %u, T = %u is not supported (both below 2^31)", who, V, T)
+#define CLEAN_SIZES(who) SN_UNSUPPORTED(mesh_sizes_ok(V, T), MESH_SIZES_MSG, who, V, T)
 
 extern "C" size_t sn_rm_mesh_clean_workspace_bytes(uint32_t V, uint32_t T) {
-    if (!clean_sizes_ok(V, T)) {
-        set_error("mesh_clean: V = %u, T = %u is not supported (both below 2^31)", V, T);
+    if (!mesh_sizes_ok(V, T)) {
+        set_error(MESH_SIZES_MSG, "mesh_clean", V, T);
         return 0;
     }
     return clean_layout(V, T).bytes;
@@ -350,9 +286,7 @@ static int clean_check(const char *who, uint32_t V, uint32_t T, const void *work
     SN_REQUIRE(workspace, "%s: NULL pointer", who);
     CLEAN_SIZES(who);
     *l = clean_layout(V, T);
-    if (bytes < l->bytes) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, bytes, l->bytes); return SN_ERR_WORKSPACE; }
-    SN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, "%s: the workspace must be 16-byte aligned", who);
-    return SN_OK;
+    return workspace_check(who, workspace, bytes, l->bytes);
 }
 
 extern "C" int sn_rm_mesh_filter_count(const int32_t *triangles, uint32_t T, uint32_t V, const int32_t *labels, const int32_t *triangle_counts,
@@ -366,9 +300,9 @@ extern "C" int sn_rm_mesh_filter_count(const int32_t *triangles, uint32_t T, uin
     if (rc != SN_OK) return rc;
     uint8_t *ws = (uint8_t *)workspace;
     uint32_t *vtot = (uint32_t *)(ws + l.vtot), *ttot = (uint32_t *)(ws + l.ttot), *vrank = (uint32_t *)(ws + l.vrank), *trank = (uint32_t *)(ws + l.trank);
-    hipLaunchKernelGGL(k_clean_rank_vertices, dim3(div_up(l.nsegv, CLEAN_WAVES)), dim3(256), 0, st, V, labels, triangle_counts, min_triangles,
+    hipLaunchKernelGGL(k_clean_rank_vertices, dim3(div_up(l.nsegv, MESH_WAVES)), dim3(256), 0, st, V, labels, triangle_counts, min_triangles,
                        min_key, vrank, vtot, l.nsegv);
-    if (T) hipLaunchKernelGGL(k_clean_rank_triangles, dim3(div_up(l.nsegt, CLEAN_WAVES)), dim3(256), 0, st, triangles, T, V, vrank, trank, ttot,
+    if (T) hipLaunchKernelGGL(k_clean_rank_triangles, dim3(div_up(l.nsegt, MESH_WAVES)), dim3(256), 0, st, triangles, T, V, vrank, trank, ttot,
                               l.nsegt);
     hipLaunchKernelGGL(k_clean_scan, dim3(1), dim3(1024), 0, st, vtot, l.nsegv, ttot, l.nsegt, counts);
     SN_LAUNCH_CHECK("k_clean_rank / k_clean_scan");

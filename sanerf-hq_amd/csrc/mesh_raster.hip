@@ -21,8 +21,7 @@
 //   k_raster_resolve  one lane per pixel.
 // The atomics: the 64-bit maximum (global_atomic_umax_x2; no return value is used, no compare-and-swap loop) and integer adds on the
 // counters.  Every index read from `triangles`, from the queue or from the depth buffer is range-tested before it is an address.
-#include "sn_common.h"
-#include "sn_wave.h"
+#include "mesh_common.h"
 
 #include <cmath>
 
@@ -35,15 +34,13 @@ constexpr uint32_t RASTER_LARGE_BLOCKS = 1024u;        // x 4 waves: the fixed g
 // Parts in order, each rounded up to 16 bytes.  head[0] = the queue's length.
 struct RasterLayout { size_t head, rows, zbuf, queue, bytes; };
 
-static inline size_t raster_align16(size_t n) { return (n + 15u) & ~(size_t)15u; }
-
 static inline RasterLayout raster_layout(uint32_t V, uint32_t T, uint32_t H, uint32_t W) {
     RasterLayout l;
     l.head = 0;
     l.rows = l.head + 16u;
     l.zbuf = l.rows + (size_t)V * 16u;
     l.queue = l.zbuf + (size_t)H * W * 8u;
-    l.bytes = l.queue + raster_align16((size_t)T * 4u);
+    l.bytes = l.queue + align16((size_t)T * 4u);
     return l;
 }
 
@@ -92,10 +89,9 @@ struct RasterTri {
 
 __device__ __forceinline__ int raster_setup(const int32_t *__restrict__ triangles, uint32_t t, uint32_t V, const int4 *__restrict__ rows,
                                             int cull, uint32_t H, uint32_t W, RasterTri &s) {
-    const int32_t *tri = triangles + (size_t)t * 3u;
-    const uint32_t a = (uint32_t)tri[0], b = (uint32_t)tri[1], c = (uint32_t)tri[2];
-    if (a >= V || b >= V || c >= V) return RASTER_DROPPED;
-    const int4 q[3] = {rows[a], rows[b], rows[c]};
+    uint32_t c[3];
+    if (!triangle_corners(triangles, t, V, c)) return RASTER_DROPPED;
+    const int4 q[3] = {rows[c[0]], rows[c[1]], rows[c[2]]};
     if (!(q[0].w & q[1].w & q[2].w & 1)) return RASTER_DROPPED;
     const int64_t A = (int64_t)(q[1].x - q[0].x) * (int64_t)(q[2].y - q[0].y) - (int64_t)(q[1].y - q[0].y) * (int64_t)(q[2].x - q[0].x);
     if (A == 0) return RASTER_DEGENERATE;
@@ -252,8 +248,8 @@ __global__ __launch_bounds__(256) void k_raster_resolve(const int32_t *__restric
     o.mask[n] = 1u;
     if (!(o.image || o.normal || o.label)) return;
     const double mu[3] = {p[0] / sum, p[1] / sum, p[2] / sum};
-    const int32_t *tri = triangles + (size_t)t * 3u;
-    const uint32_t c[3] = {(uint32_t)tri[0], (uint32_t)tri[1], (uint32_t)tri[2]};      // in [0, V): the setup tested them
+    uint32_t c[3];
+    triangle_corners(triangles, t, V, c);              // in [0, V): the setup tested them
     if (o.image) raster_blend(o.colors, c, mu, o.image + (size_t)n * 3u);
     if (o.normal) raster_blend(o.normals, c, mu, o.normal + (size_t)n * 3u);
     if (o.label) {
@@ -269,7 +265,7 @@ __global__ __launch_bounds__(256) void k_raster_resolve(const int32_t *__restric
 using namespace sn;
 
 static bool raster_sizes_ok(uint32_t V, uint32_t T, uint32_t H, uint32_t W) {
-    return V < (1u << 31) && T < (1u << 31) && H >= 1u && H <= RASTER_MAX_SIDE && W >= 1u && W <= RASTER_MAX_SIDE;
+    return mesh_sizes_ok(V, T) && H >= 1u && H <= RASTER_MAX_SIDE && W >= 1u && W <= RASTER_MAX_SIDE;
 }
 
 #define RASTER_SIZES_MSG "%s: V = %u, T = %u, H = %u, W = %u is not supported (V, T below 2^31; H, W in [1, 8192])"
@@ -287,9 +283,7 @@ static int raster_check(const char *who, uint32_t V, uint32_t T, uint32_t H, uin
     SN_REQUIRE(workspace, "%s: NULL pointer", who);
     SN_UNSUPPORTED(raster_sizes_ok(V, T, H, W), RASTER_SIZES_MSG, who, V, T, H, W);
     *l = raster_layout(V, T, H, W);
-    if (bytes < l->bytes) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, bytes, l->bytes); return SN_ERR_WORKSPACE; }
-    SN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, "%s: the workspace must be 16-byte aligned", who);
-    return SN_OK;
+    return workspace_check(who, workspace, bytes, l->bytes);
 }
 
 extern "C" int sn_rm_mesh_raster_project(const float *vertices, uint32_t V, uint32_t T, const float *pose, const float *intrinsics, uint32_t H,

@@ -35,17 +35,12 @@
 // The emit entry reads the workspace and `triangles`: one lane per output row evaluates position and normal; one lane per triangle and one
 // per input vertex remap.  Nothing is placed by an atomic; every store is guarded by cap_v / cap_t / V and every index and key is
 // range-tested before it addresses anything.  Plain vector loads, plain vector stores and integer atomics only.
-#include "sn_common.h"
-#include "sn_wave.h"
+#include "mesh_common.h"
 
 #include <cmath>
 
 namespace sn {
 
-constexpr uint32_t SIMP_SEG = 1024u;       // elements per wave = the unit of the scan
-constexpr uint32_t SIMP_SEG_LOG2 = 10u;
-constexpr uint32_t SIMP_WAVES = 4u;        // waves (segments) per workgroup
-constexpr uint32_t SIMP_KEEP = 0x80000000u;
 constexpr uint32_t SIMP_EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t SIMP_ROW = 8u;          // u64 words per output row: key, n, sum q[3], sum Q[3]
 
@@ -53,8 +48,6 @@ struct SimpLattice { float origin[3], cell[3]; uint32_t dims[3]; };
 
 // Parts in order, each rounded up to 16 bytes.  `head` holds {V', T'} for the emit; bits .. acc is one range that the count zeroes.
 struct SimpLayout { size_t head, vkey, tslot, trank, ttot, table, cwrank, ctot, bits, acc, bytes; uint32_t nsegt, nwords, nsegc; uint64_t cap; };
-
-static inline size_t simp_align16(size_t n) { return (n + 15u) & ~(size_t)15u; }
 
 static inline uint64_t simp_table_capacity(uint32_t T) {
     uint64_t cap = 1u;
@@ -64,20 +57,20 @@ static inline uint64_t simp_table_capacity(uint32_t T) {
 
 static inline SimpLayout simp_layout(uint32_t V, uint32_t T, uint32_t cells) {
     SimpLayout l;
-    l.nsegt = div_up(T, SIMP_SEG);
+    l.nsegt = div_up(T, MESH_SEG);
     l.nwords = div_up(cells, 32u);
-    l.nsegc = div_up(l.nwords, SIMP_SEG);
+    l.nsegc = div_up(l.nwords, MESH_SEG);
     l.cap = simp_table_capacity(T);
     l.head = 0;
     l.vkey = l.head + 16u;
-    l.tslot = l.vkey + simp_align16((size_t)V * 4u);
-    l.trank = l.tslot + simp_align16((size_t)T * 4u);
-    l.ttot = l.trank + simp_align16((size_t)T * 4u);
-    l.table = l.ttot + simp_align16((size_t)l.nsegt * 4u);
-    l.cwrank = l.table + simp_align16((size_t)l.cap * 4u);
-    l.ctot = l.cwrank + simp_align16((size_t)l.nwords * 4u);
-    l.bits = l.ctot + simp_align16((size_t)l.nsegc * 4u);
-    l.acc = l.bits + simp_align16((size_t)l.nwords * 4u);
+    l.tslot = l.vkey + align16((size_t)V * 4u);
+    l.trank = l.tslot + align16((size_t)T * 4u);
+    l.ttot = l.trank + align16((size_t)T * 4u);
+    l.table = l.ttot + align16((size_t)l.nsegt * 4u);
+    l.cwrank = l.table + align16((size_t)l.cap * 4u);
+    l.ctot = l.cwrank + align16((size_t)l.nwords * 4u);
+    l.bits = l.ctot + align16((size_t)l.nsegc * 4u);
+    l.acc = l.bits + align16((size_t)l.nwords * 4u);
     l.bytes = l.acc + (size_t)V * (SIMP_ROW * 8u);
     return l;
 }
@@ -116,13 +109,12 @@ __global__ __launch_bounds__(256) void k_simp_keys(const float *__restrict__ ver
 // vkey, every key before it is believed.
 __device__ __forceinline__ bool simp_triangle_keys(const int32_t *__restrict__ triangles, uint32_t t, uint32_t V, uint32_t cells,
                                                    const int32_t *__restrict__ vkey, uint32_t k[3], uint32_t sorted[3]) {
-    const int32_t *tri = triangles + (size_t)t * 3u;
-    const uint32_t a = (uint32_t)tri[0], b = (uint32_t)tri[1], c = (uint32_t)tri[2];
-    if (!(a < V && b < V && c < V)) return false;
-    k[0] = (uint32_t)vkey[a]; k[1] = (uint32_t)vkey[b]; k[2] = (uint32_t)vkey[c];
-    if (!(k[0] < cells && k[1] < cells && k[2] < cells)) return false;          // -1 reads as 2^32 - 1
-    if (k[0] == k[1] || k[1] == k[2] || k[0] == k[2]) return false;
+    uint32_t c[3];
+    if (!triangle_corners(triangles, t, V, c)) return false;
+    k[0] = (uint32_t)vkey[c[0]]; k[1] = (uint32_t)vkey[c[1]]; k[2] = (uint32_t)vkey[c[2]];
     const uint32_t lo = umin(k[0], umin(k[1], k[2])), hi = ~umin(~k[0], umin(~k[1], ~k[2]));
+    if (hi >= cells) return false;                                              // -1 reads as 2^32 - 1; the largest key is tested, so the three loads fly together
+    if (k[0] == k[1] || k[1] == k[2] || k[0] == k[2]) return false;
     sorted[0] = lo; sorted[2] = hi; sorted[1] = (k[0] ^ k[1] ^ k[2]) ^ lo ^ hi;
     return true;
 }
@@ -160,34 +152,27 @@ __global__ __launch_bounds__(256) void k_simp_keep(const int32_t *__restrict__ t
                                                    const uint32_t *__restrict__ tslot, uint32_t *bits, uint32_t *__restrict__ rank,
                                                    uint32_t *__restrict__ totals, uint32_t nseg) {
     SN_POISON_ALL();
-    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * SIMP_WAVES + (threadIdx.x >> 6);
-    if (seg >= nseg) return;               // wave-uniform; the kernel has no barrier
-    uint32_t base = 0u;
-    for (uint32_t it = 0; it < SIMP_SEG / 64u; ++it) {
-        const uint32_t t = seg * SIMP_SEG + it * 64u + lane;
-        bool keep = false;
+    segment_flag_rank(T, nseg, rank, totals, [&](uint32_t t) {
         uint32_t k[3], sorted[3];
-        if (t < T && simp_triangle_keys(triangles, t, V, cells, vkey, k, sorted)) keep = table[tslot[t] & mask] == t;
+        bool keep = false;
+        if (simp_triangle_keys(triangles, t, V, cells, vkey, k, sorted)) keep = table[tslot[t] & mask] == t;
         if (keep) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) atomicOr(&bits[k[c] >> 5], 1u << (k[c] & 31u));
         }
-        const uint64_t m = __ballot(keep);
-        if (t < T) rank[t] = (keep ? SIMP_KEEP : 0u) | (base + lanes_below(m));
-        base += (uint32_t)__popcll(m);
-    }
-    if (lane == 0u) totals[seg] = base;
+        return keep;
+    });
 }
 
 // One wave per segment of 1024 bitmap words: wrank[w] = used cells before word w inside the segment; totals[seg].
 __global__ __launch_bounds__(256) void k_simp_rank_cells(const uint32_t *__restrict__ bits, uint32_t nwords, uint32_t *__restrict__ wrank,
                                                          uint32_t *__restrict__ totals, uint32_t nseg) {
     SN_POISON_ALL();
-    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * SIMP_WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * MESH_WAVES + (threadIdx.x >> 6);
     if (seg >= nseg) return;               // wave-uniform; the kernel has no barrier
     uint32_t base = 0u;
-    for (uint32_t it = 0; it < SIMP_SEG / 64u; ++it) {
-        const uint32_t w = seg * SIMP_SEG + it * 64u + lane;
+    for (uint32_t it = 0; it < MESH_SEG / 64u; ++it) {
+        const uint32_t w = seg * MESH_SEG + it * 64u + lane;
         const uint32_t cnt = w < nwords ? (uint32_t)__popc(bits[w]) : 0u;      // 0 .. 32: six bits
         uint32_t prefix, total;
         wave_rank<6>(cnt, prefix, total);
@@ -197,41 +182,12 @@ __global__ __launch_bounds__(256) void k_simp_rank_cells(const uint32_t *__restr
     if (lane == 0u) totals[seg] = base;
 }
 
-// Exclusive scan of n totals in place by the whole workgroup of 1024 (every lane calls it); returns the grand total (< 2^31).
-__device__ __forceinline__ uint32_t simp_scan_list(uint32_t *__restrict__ totals, uint32_t n, uint32_t *ws) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t carry = 0u;
-    for (uint32_t s0 = 0; s0 < n; s0 += 1024u) {       // whole tiles: every lane reaches the shuffles and the barriers
-        const uint32_t i = s0 + tid;
-        const uint32_t c = i < n ? totals[i] : 0u;
-        uint32_t s = c;
-#pragma unroll
-        for (int dlt = 1; dlt < 64; dlt <<= 1) {
-            const uint32_t u = (uint32_t)__shfl_up((int)s, dlt);
-            if (lane >= (uint32_t)dlt) s += u;
-        }
-        if (lane == 63u) ws[wave] = s;
-        __syncthreads();
-        uint32_t before = 0u, all = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < 16u; ++w) {
-            const uint32_t a = ws[w];
-            if (w < wave) before += a;
-            all += a;
-        }
-        if (i < n) totals[i] = carry + before + (s - c);
-        carry += all;
-        __syncthreads();
-    }
-    return carry;
-}
-
 __global__ __launch_bounds__(1024) void k_simp_scan(uint32_t *__restrict__ ctot, uint32_t nsegc, uint32_t *__restrict__ ttot, uint32_t nsegt,
                                                     uint32_t *__restrict__ head, uint32_t *__restrict__ counts) {
     SN_POISON_ALL();
     __shared__ uint32_t ws[16];
-    const uint32_t nv = simp_scan_list(ctot, nsegc, ws);
-    const uint32_t nt = simp_scan_list(ttot, nsegt, ws);
+    const uint32_t nv = (uint32_t)workgroup_exclusive_scan(ctot, nsegc, ws);       // both below 2^31
+    const uint32_t nt = (uint32_t)workgroup_exclusive_scan(ttot, nsegt, ws);
     if (threadIdx.x == 0u) { counts[0] = nv; counts[1] = nt; head[0] = nv; head[1] = nt; }
 }
 
@@ -239,16 +195,11 @@ __global__ __launch_bounds__(1024) void k_simp_scan(uint32_t *__restrict__ ctot,
 __device__ __forceinline__ uint32_t simp_cell_rank(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ wrank,
                                                    const uint32_t *__restrict__ cbase, uint32_t key) {
     const uint32_t w = key >> 5;
-    return cbase[w >> SIMP_SEG_LOG2] + wrank[w] + (uint32_t)__popc(bits[w] & ((1u << (key & 31u)) - 1u));
+    return cbase[w >> MESH_SEG_LOG2] + wrank[w] + (uint32_t)__popc(bits[w] & ((1u << (key & 31u)) - 1u));
 }
 
 __device__ __forceinline__ bool simp_cell_used(const uint32_t *__restrict__ bits, uint32_t key, uint32_t cells) {
     return key < cells && ((bits[key >> 5] >> (key & 31u)) & 1u) != 0u;
-}
-
-__device__ __forceinline__ int64_t simp_shfl_up64(int64_t x, int d) {
-    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)(uint64_t)x, d), hi = (uint32_t)__shfl_up((int)(uint32_t)((uint64_t)x >> 32), d);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 // Q of one normal component: rint(n 2^20) where that is finite and below 2^31 in magnitude, else 0 (so that no sum of < 2^31 of them overflows).
@@ -296,7 +247,7 @@ __global__ __launch_bounds__(256) void k_simp_accumulate(const float *__restrict
         if (NORMALS) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const int64_t uq = simp_shfl_up64(Q[a], d);
+                const int64_t uq = shfl_up64(Q[a], d);
                 if (take) Q[a] += uq;
             }
         }
@@ -351,15 +302,15 @@ __global__ __launch_bounds__(256) void k_simp_emit_triangles(const int32_t *__re
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= T) return;
     const uint32_t w = trank[t];
-    if (!(w & SIMP_KEEP)) return;
-    const uint32_t id = tbase[t >> SIMP_SEG_LOG2] + (w & ~SIMP_KEEP);
+    if (!(w & MESH_KEEP)) return;
+    const uint32_t id = segment_index(tbase, w, t);
     if (id >= cap_t) return;
-    const int32_t *tri = triangles + (size_t)t * 3u;
+    uint32_t x[3];
+    triangle_corners(triangles, t, V, x);
     int32_t *out = out_triangles + (size_t)id * 3u;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const uint32_t x = (uint32_t)tri[c];           // range-tested again: `triangles` may have changed since the count
-        const uint32_t key = x < V ? (uint32_t)vkey[x] : SIMP_EMPTY;
+    for (int c = 0; c < 3; ++c) {                      // range-tested again, corner by corner: `triangles` may have changed since the count
+        const uint32_t key = x[c] < V ? (uint32_t)vkey[x[c]] : SIMP_EMPTY;
         out[c] = simp_cell_used(bits, key, cells) ? (int32_t)simp_cell_rank(bits, wrank, cbase, key) : -1;
     }
 }
@@ -378,10 +329,8 @@ __global__ __launch_bounds__(256) void k_simp_emit_cluster(uint32_t V, uint32_t 
 
 using namespace sn;
 
-static bool simp_sizes_ok(uint32_t V, uint32_t T, uint32_t cells) { return V < (1u << 31) && T < (1u << 31) && cells < (1u << 31); }
-
 extern "C" size_t sn_rm_mesh_simplify_workspace_bytes(uint32_t V, uint32_t T, uint32_t cells) {
-    if (!simp_sizes_ok(V, T, cells)) {
+    if (!(mesh_sizes_ok(V, T) && cells < (1u << 31))) {
         set_error("mesh_simplify: V = %u, T = %u, cells = %u is not supported (all below 2^31)", V, T, cells);
         return 0;
     }
@@ -402,12 +351,10 @@ static int simp_check(const char *who, uint32_t V, uint32_t T, const float *orig
         SN_UNSUPPORTED(n < (1ull << 31), "%s: %u x %u x %u cells is not supported (the product below 2^31)", who, dims[0], dims[1], dims[2]);
         lat->origin[a] = origin[a]; lat->cell[a] = cell[a]; lat->dims[a] = dims[a];
     }
-    SN_UNSUPPORTED(simp_sizes_ok(V, T, (uint32_t)n), "%s: V = %u, T = %u is not supported (both below 2^31)", who, V, T);
-    *cells = (uint32_t)n;
+    SN_UNSUPPORTED(mesh_sizes_ok(V, T), MESH_SIZES_MSG, who, V, T);
+    *cells = (uint32_t)n;                  // below 2^31: the loop tested it
     *l = simp_layout(V, T, *cells);
-    if (bytes < l->bytes) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, bytes, l->bytes); return SN_ERR_WORKSPACE; }
-    SN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, "%s: the workspace must be 16-byte aligned", who);
-    return SN_OK;
+    return workspace_check(who, workspace, bytes, l->bytes);
 }
 
 extern "C" int sn_rm_mesh_simplify_count(const float *vertices, const float *normals, const int32_t *triangles, uint32_t V, uint32_t T,
@@ -433,10 +380,10 @@ extern "C" int sn_rm_mesh_simplify_count(const float *vertices, const float *nor
     hipLaunchKernelGGL(k_simp_keys, dim3(div_up(V, 256)), dim3(256), 0, st, vertices, V, lat, vkey);
     if (T) {
         hipLaunchKernelGGL(k_simp_insert, dim3(div_up(T, 256)), dim3(256), 0, st, triangles, T, V, cells, vkey, table, mask, tslot);
-        hipLaunchKernelGGL(k_simp_keep, dim3(div_up(l.nsegt, SIMP_WAVES)), dim3(256), 0, st, triangles, T, V, cells, vkey, table, mask, tslot, bits,
+        hipLaunchKernelGGL(k_simp_keep, dim3(div_up(l.nsegt, MESH_WAVES)), dim3(256), 0, st, triangles, T, V, cells, vkey, table, mask, tslot, bits,
                            trank, ttot, l.nsegt);
     }
-    hipLaunchKernelGGL(k_simp_rank_cells, dim3(div_up(l.nsegc, SIMP_WAVES)), dim3(256), 0, st, bits, l.nwords, cwrank, ctot, l.nsegc);
+    hipLaunchKernelGGL(k_simp_rank_cells, dim3(div_up(l.nsegc, MESH_WAVES)), dim3(256), 0, st, bits, l.nwords, cwrank, ctot, l.nsegc);
     hipLaunchKernelGGL(k_simp_scan, dim3(1), dim3(1024), 0, st, ctot, l.nsegc, ttot, l.nsegt, head, counts);
     if (T) {                               // without a triangle no cell is used and no row exists
         if (normals) hipLaunchKernelGGL(k_simp_accumulate<true>, dim3(div_up(V, 256)), dim3(256), 0, st, vertices, normals, V, lat, cells, bits, cwrank, ctot, acc);

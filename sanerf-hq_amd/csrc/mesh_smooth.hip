@@ -26,16 +26,12 @@
 // sums added across the wave -- integers again, so the result equals the one-lane sum.
 // Integer atomics appear in the build only (degree counts and cursors).  Every index read from `triangles` or from a row is range-tested
 // before it is an address, and a row is read only if it lies inside the 3T pairs of the workspace.
-#include "sn_common.h"
-#include "sn_wave.h"
+#include "mesh_common.h"
 
 #include <cmath>
 
 namespace sn {
 
-constexpr uint32_t SMOOTH_SEG = 1024u;         // vertices per wave = the unit of the scan
-constexpr uint32_t SMOOTH_SEG_LOG2 = 10u;
-constexpr uint32_t SMOOTH_WAVES = 4u;          // waves (segments) per workgroup
 #ifndef SN_SMOOTH_LONG
 #define SN_SMOOTH_LONG 128u                    // (tools/mesh_smooth_bench.py --fan times a build with another value)
 #endif
@@ -48,20 +44,18 @@ struct SmoothQuant { float origin[3], quantum; };
 // Parts in order, each rounded up to 16 bytes.  head[0] = which of qa / qb is current.
 struct SmoothLayout { size_t head, qa, qb, rank, deg, cursor, base, pairs, bytes; uint32_t nseg; };
 
-static inline size_t smooth_align16(size_t n) { return (n + 15u) & ~(size_t)15u; }
-
 static inline SmoothLayout smooth_layout(uint32_t V, uint32_t T) {
     SmoothLayout l;
-    l.nseg = div_up(V, SMOOTH_SEG);
+    l.nseg = div_up(V, MESH_SEG);
     l.head = 0;
     l.qa = l.head + 16u;
     l.qb = l.qa + (size_t)V * 16u;
     l.rank = l.qb + (size_t)V * 16u;
-    l.deg = l.rank + smooth_align16((size_t)V * 8u);
-    l.cursor = l.deg + smooth_align16((size_t)V * 4u);
-    l.base = l.cursor + smooth_align16((size_t)V * 4u);
-    l.pairs = l.base + smooth_align16((size_t)l.nseg * 8u);
-    l.bytes = l.pairs + smooth_align16((size_t)T * 24u);
+    l.deg = l.rank + align16((size_t)V * 8u);
+    l.cursor = l.deg + align16((size_t)V * 4u);
+    l.base = l.cursor + align16((size_t)V * 4u);
+    l.pairs = l.base + align16((size_t)l.nseg * 8u);
+    l.bytes = l.pairs + align16((size_t)T * 24u);
     return l;
 }
 
@@ -93,9 +87,7 @@ __device__ __forceinline__ uint64_t smooth_mix(uint32_t i) {       // the finali
 
 // The three indices of triangle t; false unless all lie in [0, V) and are pairwise distinct.
 __device__ __forceinline__ bool smooth_triangle(const int32_t *__restrict__ triangles, uint32_t t, uint32_t V, uint32_t c[3]) {
-    const int32_t *tri = triangles + (size_t)t * 3u;
-    c[0] = (uint32_t)tri[0]; c[1] = (uint32_t)tri[1]; c[2] = (uint32_t)tri[2];
-    return c[0] < V && c[1] < V && c[2] < V && c[0] != c[1] && c[1] != c[2] && c[0] != c[2];
+    return triangle_corners(triangles, t, V, c) && c[0] != c[1] && c[1] != c[2] && c[0] != c[2];
 }
 
 __global__ __launch_bounds__(256) void k_smooth_degree(const int32_t *__restrict__ triangles, uint32_t T, uint32_t V, uint32_t *deg) {
@@ -107,39 +99,19 @@ __global__ __launch_bounds__(256) void k_smooth_degree(const int32_t *__restrict
     for (int k = 0; k < 3; ++k) atomicAdd(&deg[c[k]], 1u);
 }
 
-__device__ __forceinline__ uint64_t smooth_shfl_up64(uint64_t x, int d) {
-    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, d), hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), d);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t smooth_shfl64(uint64_t x, int lane) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, lane), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), lane);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t smooth_shfl_xor64(uint64_t x, int m) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, m), hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), m);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 // One wave per segment of 1024 vertices: rank[v] = the pairs of the segment's vertices before v; totals[seg].  64 bits: 3T passes 2^32.
 __global__ __launch_bounds__(256) void k_smooth_rank(const uint32_t *__restrict__ deg, uint32_t V, uint64_t *__restrict__ rank,
                                                      uint64_t *__restrict__ totals, uint32_t nseg) {
     SN_POISON_ALL();
-    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * SMOOTH_WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u, seg = blockIdx.x * MESH_WAVES + (threadIdx.x >> 6);
     if (seg >= nseg) return;               // wave-uniform; the kernel has no barrier
     uint64_t base = 0u;
-    for (uint32_t it = 0; it < SMOOTH_SEG / 64u; ++it) {
-        const uint32_t v = seg * SMOOTH_SEG + it * 64u + lane;
+    for (uint32_t it = 0; it < MESH_SEG / 64u; ++it) {
+        const uint32_t v = seg * MESH_SEG + it * 64u + lane;
         const uint64_t c = v < V ? (uint64_t)deg[v] : 0u;
-        uint64_t s = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t u = smooth_shfl_up64(s, d);
-            if (lane >= (uint32_t)d) s += u;
-        }
+        const uint64_t s = wave_inclusive_sum(c);
         if (v < V) rank[v] = base + (s - c);
-        base += smooth_shfl64(s, 63);
+        base += shfl64(s, 63);
     }
     if (lane == 0u) totals[seg] = base;
 }
@@ -148,30 +120,7 @@ __global__ __launch_bounds__(256) void k_smooth_rank(const uint32_t *__restrict_
 __global__ __launch_bounds__(1024) void k_smooth_scan(uint64_t *__restrict__ totals, uint32_t n) {
     SN_POISON_ALL();
     __shared__ uint64_t ws[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint64_t carry = 0u;
-    for (uint32_t s0 = 0; s0 < n; s0 += 1024u) {       // whole tiles: every lane reaches the shuffles and the barriers
-        const uint32_t i = s0 + tid;
-        const uint64_t c = i < n ? totals[i] : 0u;
-        uint64_t s = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t u = smooth_shfl_up64(s, d);
-            if (lane >= (uint32_t)d) s += u;
-        }
-        if (lane == 63u) ws[wave] = s;
-        __syncthreads();
-        uint64_t before = 0u, all = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < 16u; ++w) {
-            const uint64_t a = ws[w];
-            if (w < wave) before += a;
-            all += a;
-        }
-        if (i < n) totals[i] = carry + before + (s - c);
-        carry += all;
-        __syncthreads();
-    }
+    workgroup_exclusive_scan(totals, n, ws);
 }
 
 __global__ __launch_bounds__(256) void k_smooth_fill(const int32_t *__restrict__ triangles, uint32_t T, uint32_t V,
@@ -185,7 +134,7 @@ __global__ __launch_bounds__(256) void k_smooth_fill(const int32_t *__restrict__
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const uint32_t v = c[k];
-        const uint64_t slot = base[v >> SMOOTH_SEG_LOG2] + rank[v] + atomicAdd(&cursor[v], 1u);
+        const uint64_t slot = base[v >> MESH_SEG_LOG2] + rank[v] + atomicAdd(&cursor[v], 1u);
         if (slot < cap) pairs[slot] = make_int2((int32_t)c[(k + 1) % 3], (int32_t)c[(k + 2) % 3]);      // (`triangles` may have changed since the count)
     }
 }
@@ -199,7 +148,7 @@ struct SmoothRows {
 };
 
 __device__ __forceinline__ void smooth_row(const SmoothRows &rows, uint32_t v, uint64_t &begin, uint32_t &d) {
-    begin = rows.base[v >> SMOOTH_SEG_LOG2] + rows.rank[v];
+    begin = rows.base[v >> MESH_SEG_LOG2] + rows.rank[v];
     d = rows.deg[v];
     if (begin > rows.cap || (uint64_t)d > rows.cap - begin) { begin = 0u; d = 0u; }
 }
@@ -219,7 +168,7 @@ __device__ __forceinline__ void smooth_row_sum(const int2 *__restrict__ pairs, u
     while (todo) {                         // wave-uniform
         const int owner = __ffsll((unsigned long long)todo) - 1;
         todo &= todo - 1u;
-        const uint64_t b = smooth_shfl64(begin, owner);
+        const uint64_t b = shfl64(begin, owner);
         const uint32_t n = (uint32_t)__shfl((int)d, owner);
         const F g = f.from_lane(owner);
         uint64_t part[K];
@@ -229,7 +178,7 @@ __device__ __forceinline__ void smooth_row_sum(const int2 *__restrict__ pairs, u
 #pragma unroll
         for (int k = 0; k < K; ++k) {
 #pragma unroll
-            for (int m = 1; m < 64; m <<= 1) part[k] += smooth_shfl_xor64(part[k], m);
+            for (int m = 1; m < 64; m <<= 1) part[k] += shfl_xor64(part[k], m);
             if (lane == (uint32_t)owner) acc[k] += part[k];
         }
     }
@@ -371,11 +320,9 @@ __global__ __launch_bounds__(256) void k_smooth_emit(const float *__restrict__ v
 
 using namespace sn;
 
-static bool smooth_sizes_ok(uint32_t V, uint32_t T) { return V < (1u << 31) && T < (1u << 31); }
-
 extern "C" size_t sn_rm_mesh_smooth_workspace_bytes(uint32_t V, uint32_t T) {
-    if (!smooth_sizes_ok(V, T)) {
-        set_error("mesh_smooth: V = %u, T = %u is not supported (both below 2^31)", V, T);
+    if (!mesh_sizes_ok(V, T)) {
+        set_error(MESH_SIZES_MSG, "mesh_smooth", V, T);
         return 0;
     }
     return smooth_layout(V, T).bytes;
@@ -384,11 +331,9 @@ extern "C" size_t sn_rm_mesh_smooth_workspace_bytes(uint32_t V, uint32_t T) {
 // The checks the three entries share; fills the layout.
 static int smooth_check(const char *who, uint32_t V, uint32_t T, const void *workspace, size_t bytes, SmoothLayout *l) {
     SN_REQUIRE(workspace, "%s: NULL pointer", who);
-    SN_UNSUPPORTED(smooth_sizes_ok(V, T), "%s: V = %u, T = %u is not supported (both below 2^31)", who, V, T);
+    SN_UNSUPPORTED(mesh_sizes_ok(V, T), MESH_SIZES_MSG, who, V, T);
     *l = smooth_layout(V, T);
-    if (bytes < l->bytes) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, bytes, l->bytes); return SN_ERR_WORKSPACE; }
-    SN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, "%s: the workspace must be 16-byte aligned", who);
-    return SN_OK;
+    return workspace_check(who, workspace, bytes, l->bytes);
 }
 
 static int smooth_quant(const char *who, const float *origin, float quantum, SmoothQuant *qt) {
@@ -423,7 +368,7 @@ extern "C" int sn_rm_mesh_smooth_build(const float *vertices, const int32_t *tri
     uint32_t *deg = (uint32_t *)(ws + l.deg), *cursor = (uint32_t *)(ws + l.cursor);
     SN_HIP_OK(hipMemsetAsync(deg, 0, l.base - l.deg, st));                     // the degrees and the cursors
     if (T) hipLaunchKernelGGL(k_smooth_degree, dim3(div_up(T, 256)), dim3(256), 0, st, triangles, T, V, deg);
-    hipLaunchKernelGGL(k_smooth_rank, dim3(div_up(l.nseg, SMOOTH_WAVES)), dim3(256), 0, st, deg, V, rank, base, l.nseg);
+    hipLaunchKernelGGL(k_smooth_rank, dim3(div_up(l.nseg, MESH_WAVES)), dim3(256), 0, st, deg, V, rank, base, l.nseg);
     hipLaunchKernelGGL(k_smooth_scan, dim3(1), dim3(1024), 0, st, base, l.nseg);
     if (T) hipLaunchKernelGGL(k_smooth_fill, dim3(div_up(T, 256)), dim3(256), 0, st, triangles, T, V, rank, base, cursor, (int2 *)(ws + l.pairs));
     hipLaunchKernelGGL(k_smooth_init, dim3(div_up(V, 256)), dim3(256), 0, st, vertices, V, qt, smooth_rows(ws, l, T), (int4 *)(ws + l.qa),

@@ -35,6 +35,45 @@ def _triple(v, name, kind=float):
     return v
 
 
+# ---- what the count / emit families share -------------------------------------------------------------------------------------------------
+def _workspace(name, need, device, empty_ok=False):
+    """The module's one scratch buffer `name` of this device with `need` bytes; need = 0 is the library's refusal of the sizes."""
+    if need == 0 and not empty_ok:
+        raise RuntimeError(f"{name}: " + _lib.lib().sn_last_error().decode())
+    return _buffers.scratch(name, device, max(need, 16))
+
+
+def _read_counts(counts):
+    """The two uint32 totals of a count entry, read back from their int32 tensor."""
+    return tuple(int(c) & 0xFFFFFFFF for c in counts.tolist())
+
+
+def _capacities(what, cap_v, cap_t, per_vertex, out_triangles):
+    """cap_v, cap_t defaulted to the rows of per_vertex[0] and of out_triangles; every buffer of per_vertex (None: one that is needed and
+    missing) has at least cap_v rows, out_triangles at least cap_t."""
+    cap_v = per_vertex[0].shape[0] if cap_v is None else int(cap_v)
+    cap_t = out_triangles.shape[0] if cap_t is None else int(cap_t)
+    if cap_t > out_triangles.shape[0] or any(b is None or b.shape[0] < cap_v for b in per_vertex):
+        raise ValueError(f"{what}: a capacity exceeds its buffer")
+    return cap_v, cap_t
+
+
+def _rows3(what, *tensors):
+    if any(t is not None and tuple(t.shape[1:]) != (3,) for t in tensors):
+        raise RuntimeError(f"{what}: vertices, normals and triangles are [n,3]")
+
+
+def _vertices_v3(vertices, what):
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError(f"{what}: vertices must be [V,3], got {tuple(vertices.shape)}")
+
+
+def _empty_mesh(nv, nt, device, normals):
+    return {"vertices": torch.empty(nv, 3, device=device, dtype=torch.float32),
+            "normals": torch.empty(nv, 3, device=device, dtype=torch.float32) if normals else None,
+            "triangles": torch.empty(nt, 3, device=device, dtype=torch.int32)}
+
+
 def lattice_points(origin: Sequence[float], step: Sequence[float], shape: Sequence[int], first: int = 0, count: int | None = None,
                    contract: bool = False, device=None) -> torch.Tensor:
     """xyz [count,3] of the lattice vertices first .. first + count - 1 (default: to the end) of a lattice of `shape` = (nx, ny, nz); linear
@@ -62,10 +101,7 @@ def isosurface_counts(volume: torch.Tensor, iso: float):
         raise RuntimeError(f"isosurface: volume must be [nx,ny,nz], got {tuple(vol.shape)}")
     nx, ny, nz = vol.shape
     L = _lib.lib()
-    need = int(L.sn_rm_isosurface_workspace_bytes(nx, ny, nz))
-    if need == 0:
-        raise RuntimeError("isosurface: " + L.sn_last_error().decode())
-    ws = _buffers.scratch("isosurface", vol.device, need)
+    ws = _workspace("isosurface", int(L.sn_rm_isosurface_workspace_bytes(nx, ny, nz)), vol.device)
     counts = torch.empty(2, device=vol.device, dtype=torch.int32)
     _lib.check(L.sn_rm_isosurface_count(_lib.dev(vol, "volume"), nx, ny, nz, float(iso), ws.data_ptr(), ws.numel(),
                                         _lib.dev(counts, "counts", torch.int32), _lib.stream()), "sn_rm_isosurface_count")
@@ -78,12 +114,8 @@ def isosurface_emit(volume: torch.Tensor, iso: float, origin, step, workspace: t
     isosurface_counts() left.  Capacities below the counts truncate: the stored prefix is the full result's."""
     vol = _f32(volume)
     nx, ny, nz = vol.shape
-    cap_v = vertices.shape[0] if cap_v is None else int(cap_v)
-    cap_t = triangles.shape[0] if cap_t is None else int(cap_t)
-    if cap_v > vertices.shape[0] or cap_t > triangles.shape[0] or (normals is not None and normals.shape[0] < cap_v):
-        raise ValueError("isosurface_emit: a capacity exceeds its buffer")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3 or (normals is not None and tuple(normals.shape[1:]) != (3,)):
-        raise RuntimeError("isosurface_emit: vertices, normals and triangles are [n,3]")
+    cap_v, cap_t = _capacities("isosurface_emit", cap_v, cap_t, [vertices] + ([] if normals is None else [normals]), triangles)
+    _rows3("isosurface_emit", vertices, triangles, normals)
     _lib.check(_lib.lib().sn_rm_isosurface_emit(_lib.dev(vol, "volume"), nx, ny, nz, float(iso), _lib.host_f32(_triple(origin, "origin")),
                                                 _lib.host_f32(_triple(step, "step")), workspace.data_ptr(), workspace.numel(),
                                                 _lib.dev(vertices, "vertices"), _lib.dev(normals, "normals"),
@@ -101,16 +133,13 @@ def isosurface(volume: torch.Tensor, iso: float, origin=(0.0, 0.0, 0.0), step=(1
     Deterministic: vertex and triangle order are fixed by the definition, and two calls give equal bits."""
     vol = _f32(volume)
     counts, ws = isosurface_counts(vol, iso)
-    nv, nt = (int(c) & 0xFFFFFFFF for c in counts.tolist())
+    nv, nt = _read_counts(counts)
     if nv > ISOSURFACE_MAX_VERTICES or nt > ISOSURFACE_MAX_VERTICES:
         raise RuntimeError(f"isosurface: {nv} vertices / {nt} triangles exceed the int32 indices of the result")
-    dev = vol.device
-    vertices = torch.empty(nv, 3, device=dev, dtype=torch.float32)
-    nrm = torch.empty(nv, 3, device=dev, dtype=torch.float32) if normals else None
-    triangles = torch.empty(nt, 3, device=dev, dtype=torch.int32)
+    out = _empty_mesh(nv, nt, vol.device, normals)
     if nv or nt:
-        isosurface_emit(vol, iso, origin, step, ws, vertices, nrm, triangles)
-    return {"vertices": vertices, "normals": nrm, "triangles": triangles}
+        isosurface_emit(vol, iso, origin, step, ws, out["vertices"], out["normals"], out["triangles"])
+    return out
 
 
 # ---- clean-up: connected components, floater removal (mesh_clean.hip) -------------------------------------------------------------------
@@ -174,10 +203,7 @@ def mesh_filter_counts(triangles: torch.Tensor, n_vertices: int, components: dic
     dev = tri.device
     counts = torch.zeros(2, device=dev, dtype=torch.int32)
     L = _lib.lib()
-    need = int(L.sn_rm_mesh_clean_workspace_bytes(V, T))
-    if need == 0 and V:
-        raise RuntimeError("mesh_clean: " + L.sn_last_error().decode())
-    ws = _buffers.scratch("mesh_clean", dev, max(need, 16))
+    ws = _workspace("mesh_clean", int(L.sn_rm_mesh_clean_workspace_bytes(V, T)), dev, empty_ok=V == 0)
     if V == 0:
         return counts, ws
     tc = components["triangle_counts"]
@@ -198,13 +224,10 @@ def mesh_filter_emit(triangles: torch.Tensor, vertices: torch.Tensor, normals, w
     int32 and source_vertex [>= cap_v] int32 (or None) from the workspace mesh_filter_counts() left.  Capacities below the counts truncate:
     the stored prefix is the full result's."""
     tri, V, T = _triangles_i32(triangles, vertices.shape[0])
-    cap_v = out_vertices.shape[0] if cap_v is None else int(cap_v)
-    cap_t = out_triangles.shape[0] if cap_t is None else int(cap_t)
-    if (cap_v > out_vertices.shape[0] or cap_t > out_triangles.shape[0] or (normals is not None and (out_normals is None or out_normals.shape[0] < cap_v))
-            or (source_vertex is not None and source_vertex.shape[0] < cap_v)):
-        raise ValueError("mesh_filter_emit: a capacity exceeds its buffer")
-    if (tuple(vertices.shape[1:]) != (3,) or tuple(out_vertices.shape[1:]) != (3,) or tuple(out_triangles.shape[1:]) != (3,)
-            or (normals is not None and (tuple(normals.shape) != tuple(vertices.shape) or tuple(out_normals.shape[1:]) != (3,)))):
+    per_vertex = [out_vertices] + ([] if normals is None else [out_normals]) + ([] if source_vertex is None else [source_vertex])
+    cap_v, cap_t = _capacities("mesh_filter_emit", cap_v, cap_t, per_vertex, out_triangles)
+    _rows3("mesh_filter_emit", vertices, out_vertices, out_triangles, out_normals if normals is not None else None)
+    if normals is not None and tuple(normals.shape) != tuple(vertices.shape):
         raise RuntimeError("mesh_filter_emit: vertices, normals and triangles are [n,3]")
     _lib.check(_lib.lib().sn_rm_mesh_filter_emit(_lib.dev(tri, "triangles", torch.int32), T, V, _lib.dev(vertices, "vertices"),
                                                  _lib.dev(normals, "normals"), workspace.data_ptr(), workspace.numel(),
@@ -234,10 +257,8 @@ def mesh_clean(mesh: dict, min_triangles: int = 0, keep_largest: int = 0, return
     V, dev = vertices.shape[0], vertices.device
     comp = mesh_components(triangles, V)
     counts, ws = mesh_filter_counts(triangles, V, comp, min_triangles, keep_largest)
-    nv, nt = (int(c) & 0xFFFFFFFF for c in counts.tolist())
-    out = {"vertices": torch.empty(nv, 3, device=dev, dtype=torch.float32),
-           "normals": None if normals is None else torch.empty(nv, 3, device=dev, dtype=torch.float32),
-           "triangles": torch.empty(nt, 3, device=dev, dtype=torch.int32)}
+    nv, nt = _read_counts(counts)
+    out = _empty_mesh(nv, nt, dev, normals is not None)
     source = torch.empty(nv, device=dev, dtype=torch.int32) if return_source else None
     if nv or nt:
         mesh_filter_emit(triangles, vertices, normals, ws, out["vertices"], out["normals"], out["triangles"], source)
@@ -271,10 +292,7 @@ def mesh_simplify_counts(vertices: torch.Tensor, normals, triangles: torch.Tenso
     dev = vertices.device
     counts = torch.zeros(2, device=dev, dtype=torch.int32)
     L = _lib.lib()
-    need = int(L.sn_rm_mesh_simplify_workspace_bytes(V, T, cells))
-    if need == 0:
-        raise RuntimeError("mesh_simplify: " + L.sn_last_error().decode())
-    ws = _buffers.scratch("mesh_simplify", dev, need)
+    ws = _workspace("mesh_simplify", int(L.sn_rm_mesh_simplify_workspace_bytes(V, T, cells)), dev)
     _lib.check(L.sn_rm_mesh_simplify_count(p_v, p_n, _lib.dev(tri, "triangles", torch.int32), V, T, h_origin, h_cell, h_dims, ws.data_ptr(),
                                            ws.numel(), counts.data_ptr(), _lib.stream()), "sn_rm_mesh_simplify_count")
     return counts, ws
@@ -289,14 +307,10 @@ def mesh_simplify_emit(vertices: torch.Tensor, normals, triangles: torch.Tensor,
     tri, V, T = _triangles_i32(triangles, vertices.shape[0])
     p_v, p_n = _mesh_f32(vertices, normals)
     h_origin, h_cell, h_dims, _ = _cell_lattice(origin, cell, dims)
-    cap_v = out_vertices.shape[0] if cap_v is None else int(cap_v)
-    cap_t = out_triangles.shape[0] if cap_t is None else int(cap_t)
-    if (cap_v > out_vertices.shape[0] or cap_t > out_triangles.shape[0] or (normals is not None and (out_normals is None or out_normals.shape[0] < cap_v))
-            or (vertex_cluster is not None and vertex_cluster.shape[0] < V)):
+    cap_v, cap_t = _capacities("mesh_simplify_emit", cap_v, cap_t, [out_vertices] + ([] if normals is None else [out_normals]), out_triangles)
+    if vertex_cluster is not None and vertex_cluster.shape[0] < V:
         raise ValueError("mesh_simplify_emit: a capacity exceeds its buffer")
-    if (tuple(out_vertices.shape[1:]) != (3,) or tuple(out_triangles.shape[1:]) != (3,)
-            or (normals is not None and tuple(out_normals.shape[1:]) != (3,))):
-        raise RuntimeError("mesh_simplify_emit: vertices, normals and triangles are [n,3]")
+    _rows3("mesh_simplify_emit", out_vertices, out_triangles, out_normals if normals is not None else None)
     _lib.check(_lib.lib().sn_rm_mesh_simplify_emit(p_v, p_n, _lib.dev(tri, "triangles", torch.int32), V, T, h_origin, h_cell, h_dims,
                                                    workspace.data_ptr(), workspace.numel(), _lib.dev(out_vertices, "out_vertices"),
                                                    _lib.dev(out_normals if normals is not None else None, "out_normals"),
@@ -355,10 +369,8 @@ def mesh_simplify(mesh: dict, cell, origin=None, dims=None, return_cluster: bool
     if V and lattice is not None:
         origin, dims = lattice
         counts, ws = mesh_simplify_counts(vertices, normals, triangles, origin, cell, dims)
-        nv, nt = (int(c) & 0xFFFFFFFF for c in counts.tolist())
-    out = {"vertices": torch.empty(nv, 3, device=dev, dtype=torch.float32),
-           "normals": None if normals is None else torch.empty(nv, 3, device=dev, dtype=torch.float32),
-           "triangles": torch.empty(nt, 3, device=dev, dtype=torch.int32)}
+        nv, nt = _read_counts(counts)
+    out = _empty_mesh(nv, nt, dev, normals is not None)
     cluster = torch.full((V,), -1, device=dev, dtype=torch.int32) if return_cluster else None
     if nv or nt:
         mesh_simplify_emit(vertices, normals, triangles, origin, cell, dims, ws, out["vertices"], out["normals"], out["triangles"], cluster)
@@ -415,25 +427,16 @@ def _smooth_quant_args(origin, quantum, what):
     return _lib.host_f32(origin), q32
 
 
-def _smooth_workspace(V, T, device):
-    L = _lib.lib()
-    need = int(L.sn_rm_mesh_smooth_workspace_bytes(V, T))
-    if need == 0:
-        raise RuntimeError("mesh_smooth: " + L.sn_last_error().decode())
-    return _buffers.scratch("mesh_smooth", device, need)
-
-
 def mesh_smooth_build(vertices: torch.Tensor, triangles: torch.Tensor, origin, quantum) -> torch.Tensor:
     """The first phase of mesh_smooth(): quantises vertices [V,3] f32 to Q = rint((p - origin) / quantum) and inverts triangles [T,3] int32
     into every vertex's row of (next, prev) pairs, with the open flags.  Returns the workspace that mesh_smooth_steps() and
     mesh_smooth_emit() take -- the module's one "mesh_smooth" buffer per device: the next build on that device reuses it.  Nothing is read
     back."""
     tri, V, T = _triangles_i32(triangles, vertices.shape[0])
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise RuntimeError(f"mesh_smooth: vertices must be [V,3], got {tuple(vertices.shape)}")
+    _vertices_v3(vertices, "mesh_smooth")
     p_v = _lib.dev(vertices, "vertices")
     h_origin, q32 = _smooth_quant_args(origin, quantum, "mesh_smooth_build")
-    ws = _smooth_workspace(V, T, vertices.device)
+    ws = _workspace("mesh_smooth", int(_lib.lib().sn_rm_mesh_smooth_workspace_bytes(V, T)), vertices.device)
     _lib.check(_lib.lib().sn_rm_mesh_smooth_build(p_v, _lib.dev(tri, "triangles", torch.int32), V, T, h_origin, q32, ws.data_ptr(), ws.numel(),
                                                   _lib.stream()), "sn_rm_mesh_smooth_build")
     return ws
@@ -501,8 +504,7 @@ def mesh_smooth(mesh: dict, iterations: int = 10, lam: float = 0.5, mu: float = 
         _smooth_quant_args(origin, quantum, "mesh_smooth")
     vertices, triangles = _f32(mesh["vertices"]), mesh["triangles"]
     _, V, T = _triangles_i32(triangles, vertices.shape[0])
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise RuntimeError(f"mesh_smooth: vertices must be [V,3], got {tuple(vertices.shape)}")
+    _vertices_v3(vertices, "mesh_smooth")
     _lib.dev(vertices, "vertices")
     want_normals = (mesh.get("normals") is not None) if normals is None else bool(normals)
     dev = vertices.device
@@ -571,28 +573,19 @@ def _raster_near(near, what):
     return near32
 
 
-def _raster_workspace(V, T, H, W, device):
-    L = _lib.lib()
-    need = int(L.sn_rm_mesh_raster_workspace_bytes(V, T, H, W))
-    if need == 0:
-        raise RuntimeError("mesh_raster: " + L.sn_last_error().decode())
-    return _buffers.scratch("mesh_raster", device, need)
-
-
 def mesh_raster_project(vertices: torch.Tensor, n_triangles: int, pose: torch.Tensor, intrinsics: torch.Tensor, H: int, W: int, near: float,
                         counts: torch.Tensor) -> torch.Tensor:
     """The first phase of mesh_rasterize(): every vertex of vertices [V,3] f32 into the camera (pose [4,4], intrinsics [4] = fx, fy, cx, cy:
     fp32 tensors ON THE DEVICE, read when the kernel runs) as a row {X, Y, 1/z, placed} of the workspace; clears the H x W depth buffer,
     the queue and counts (int32 [4]).  Returns the workspace that mesh_raster_draw() and mesh_raster_resolve() take -- the module's one
     "mesh_raster" buffer per device: the next projection on that device reuses it.  Nothing is read back."""
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise RuntimeError(f"mesh_raster: vertices must be [V,3], got {tuple(vertices.shape)}")
+    _vertices_v3(vertices, "mesh_raster")
     V, T, H, W = _raster_sizes(vertices.shape[0], n_triangles, H, W, "mesh_raster_project")
     if tuple(counts.shape) != (4,) or pose.numel() != 16 or intrinsics.numel() != 4:
         raise ValueError("mesh_raster_project: pose is [4,4], intrinsics [4], counts int32 [4]")
     near32 = _raster_near(near, "mesh_raster_project")
     p_v = _lib.dev(vertices, "vertices")
-    ws = _raster_workspace(V, T, H, W, vertices.device)
+    ws = _workspace("mesh_raster", int(_lib.lib().sn_rm_mesh_raster_workspace_bytes(V, T, H, W)), vertices.device)
     _lib.check(_lib.lib().sn_rm_mesh_raster_project(p_v, V, T, _lib.dev(pose, "pose"), _lib.dev(intrinsics, "intrinsics"), H, W, near32,
                                                     ws.data_ptr(), ws.numel(), _lib.dev(counts, "counts", torch.int32), _lib.stream()),
                "sn_rm_mesh_raster_project")
@@ -660,8 +653,7 @@ def mesh_rasterize(mesh: dict, pose, intrinsics, H: int, W: int, near: float = 0
     the lower triangle index at equal depth bits: the result depends on neither the order of the triangles nor the run, and equals
     tests/mesh_raster_ref.py bit for bit; include/sanerf_hip.h has the definition.  Four launches, nothing is read back."""
     vertices, triangles = _f32(mesh["vertices"]), mesh["triangles"]
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise RuntimeError(f"mesh_rasterize: vertices must be [V,3], got {tuple(vertices.shape)}")
+    _vertices_v3(vertices, "mesh_rasterize")
     tri, V, T = _triangles_i32(triangles, vertices.shape[0])
     V, T, H, W = _raster_sizes(V, T, H, W, "mesh_rasterize")
     near = _raster_near(near, "mesh_rasterize")
