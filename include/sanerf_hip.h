@@ -1180,8 +1180,8 @@ int sn_rm_mesh_smooth_emit(const float *vertices, uint32_t V, uint32_t T, const 
  *                     doubled signed area A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) (int64) is not 0 and, with `cull`, A < 0.  On the
  *                     sign: a triangle that is counter-clockwise seen from outside -- sn_rm_isosurface_emit's promise -- is counter-clockwise
  *                     in the camera's (c_0, c_1) plane when its outside faces the camera; the screen's y points down, which turns it
- *                     around: FRONT faces have A < 0.  There is no near-plane or guard-band clipping: a triangle with a corner that is not
- *                     placed is dropped whole.  counts [4] int32 = triangles {drawn, dropped for a bad index or an unplaced corner,
+ *                     around: FRONT faces have A < 0.  Without clip (sn_rm_mesh_raster_draw / _resolve) there is no clipping: a triangle
+ *                     with a corner that is not placed is dropped whole.  counts [4] int32 = triangles {drawn, dropped for a bad index or an unplaced corner,
  *                     degenerate (A = 0), culled}, tested in that order; they sum to T.
  *   Coverage          one sample per pixel at its centre P = (256 i + 128, 256 j + 128).  With s = sign(A): edge k runs from corner k + 1 to
  *                     corner k + 2 (mod 3), (dx, dy) = s (that edge's vector), w_k = dx (P_y - Y_{k+1}) - dy (P_x - X_{k+1}): int64, exact
@@ -1200,6 +1200,38 @@ int sn_rm_mesh_smooth_emit(const float *vertices, uint32_t V, uint32_t T, const 
  *                     labels [V] uint8 -> label [H,W] uint8: the label of the corner with the largest mu, the first corner of the row
  *                     winning ties; 255 where empty.
  *
+ *
+ * Near-plane clipping (sn_rm_mesh_raster_draw_clip / _resolve_clip, opt-in; tests/mesh_raster_clip_ref.py restates it).  The rows, the
+ * projection and the workspace are the ones above; a clipped triangle recomputes the fp32 camera frame c, z of its corners from vertices
+ * and pose with the Camera line's expressions in its order.
+ *   Corner roles      FRONT: its row is placed.  BEHIND: not placed, its three coordinates finite and z < near (z <= 0 included).  Any other
+ *                     corner that is not placed (NaN, guard band, overflowed 1 / z) is BAD.
+ *   Triangle classes  three front corners: the triangle above, bit for bit.  A bad index, a bad corner or no front corner: dropped, as
+ *                     above.  Otherwise it has one or two behind corners and is CLIPPED.
+ *   Crossing point    of an edge between a front corner P and a behind corner Q -- the roles come from the vertices, not from the order in
+ *                     the triangle, so two triangles that share the edge compute the same bits.  In fp64 from the fp32 values, every
+ *                     operation rounded on its own: s = (z_P - near) / (z_P - z_Q); x = c_P.x + s (c_Q.x - c_P.x), y likewise;
+ *                     px = (fx x) / near + cx, py = -((fy y) / near) + cy; X = rint(256 px), Y = rint(256 py) (ties to even);
+ *                     r = 1.0f / near in fp32.  Unless |X| <= 2^22 and |Y| <= 2^22 (no NaN passes) the whole triangle is dropped:
+ *                     only the near plane clips, the guard band does not.
+ *   Polygon           walk the corners k = 0, 1, 2: emit corner k if it is front, then the crossing point of the edge (k, k + 1 mod 3) if
+ *                     exactly one of its ends is front.  Three or four points p0 .. in the triangle's winding; the PIECES are
+ *                     (p0, p1, p2) and, of four points, (p0, p2, p3).
+ *   Pieces            each is set up as a Drawn triangle is from its three {X, Y, r}: A, the edge functions, the top-left rule, rho from
+ *                     the piece's three r.  A piece with A = 0 is skipped, one with A > 0 is skipped under `cull`.  Every piece writes the
+ *                     Depth key of its PARENT's t with the same 64-bit maximum: the image stays independent of the order of the triangles
+ *                     and of the run.  counts: the parent counts once -- drawn if a piece is drawn, else culled if a piece was culled, else
+ *                     degenerate.  clip_counts [2] int32 = {clipped triangles (their crossing points inside the guard band), the pieces of
+ *                     them that were drawn}.
+ *   Resolve           of a winner whose corners are not all front: its pieces are rebuilt (every piece with A != 0; cull plays no part).
+ *                     The piece that covers the pixel centre is taken; if both do -- only in a sliver that the snapping made non-convex --
+ *                     the one with the larger fp32(rho) bits, then the first.  p_k, their sum, rho and mu_k are that piece's, as above;
+ *                     depth = fp32(1.0 / rho).  The attributes go through the parent's corners: lambda_i = ((0.0 + mu_0 B[0][i]) +
+ *                     mu_1 B[1][i]) + mu_2 B[2][i], where the row B[k] of the piece's point k is the unit vector of a front corner, or
+ *                     1.0 - s at P, s at Q and 0 at the third corner for a crossing point.  colors and normals: the Resolve line's sum of
+ *                     the parent's three rows with lambda for mu; label: the parent's corner with the largest lambda, the first winning
+ *                     ties.  A winner with three front corners is resolved as above.
+ *
  * sn_rm_mesh_raster_workspace_bytes(V, T, H, W):
  *     16 + 16V + 8HW + up(4T)                                                                                (up = rounded up to 16)
  * i.e. a head (the queue's length), a 16-byte row {X, Y, bits(r), placed} per vertex, the 64-bit depth buffer, and a queue of triangle
@@ -1214,14 +1246,21 @@ int sn_rm_mesh_smooth_emit(const float *vertices, uint32_t V, uint32_t T, const 
  * sn_rm_mesh_raster_resolve: one lane per pixel; triangle_id [H,W] int32, depth [H,W] fp32, mask [H,W] uint8 always; colors with image,
  * normals with normal, labels with label, each pair both given or both NULL (with V == 0 the attribute may be NULL beside its image).  It
  * changes nothing in the workspace.
+ * sn_rm_mesh_raster_draw_clip, sn_rm_mesh_raster_resolve_clip: the clipped instantiations of the same three kernels, after the same
+ * sn_rm_mesh_raster_project and in the same workspace; vertices, pose, intrinsics and near_plane must be the project's, and pose and
+ * intrinsics are again read on the device.  draw_clip clears clip_counts on the stream (an 8-byte memset node in a captured graph); a lane
+ * of the first kernel scans its own pieces one after the other; a clipped triangle is queued ONCE if either piece's box exceeds
+ * small_max_pixels, and the wave that takes it walks both pieces.  The same checks and refusals as their siblings, and near_plane positive
+ * and finite.  The unclipped entries launch the unclipped instantiations, which read none of this.  A draw and its resolve go together:
+ * both clipped or neither.
  * All three: vertices may be NULL when V == 0 and triangles when T == 0 -- the project still clears and the resolve still writes the empty
  * image; workspace 16-byte aligned; V, T, H, W must be the project's.  Errors before any launch: SN_ERR_INVALID (NULL pointer, misaligned
  * workspace, a near that is not positive and finite, small_max_pixels >= 2^31, an attribute without its image or the reverse),
  * SN_ERR_UNSUPPORTED (V or T >= 2^31, H or W outside [1, 8192]), SN_ERR_WORKSPACE.  Every index read from `triangles`, from the queue or
  * from the depth buffer is range-tested before it is an address: a workspace that no project filled gives a meaningless image, never an
  * access out of bounds.
- * Not here: clipping (a triangle that crosses the near plane or leaves the guard band disappears), anti-aliasing, transparency, textures,
- * gradients. */
+ * Not here: guard-band or screen clipping (a triangle with a corner or a crossing point outside the guard band disappears, clipped or
+ * not), anti-aliasing, transparency, textures, gradients. */
 size_t sn_rm_mesh_raster_workspace_bytes(uint32_t V, uint32_t T, uint32_t H, uint32_t W);
 int sn_rm_mesh_raster_project(const float *vertices, uint32_t V, uint32_t T, const float *pose, const float *intrinsics, uint32_t H, uint32_t W,
                               float near_plane, void *workspace, size_t workspace_bytes, int32_t *counts, sn_stream_t stream);
@@ -1231,6 +1270,13 @@ int sn_rm_mesh_raster_resolve(const int32_t *triangles, uint32_t V, uint32_t T, 
                               const float *normals, const uint8_t *labels, float bg_color, const void *workspace, size_t workspace_bytes,
                               int32_t *triangle_id, float *depth, uint8_t *mask, float *image, float *normal, uint8_t *label,
                               sn_stream_t stream);
+int sn_rm_mesh_raster_draw_clip(const float *vertices, const int32_t *triangles, uint32_t V, uint32_t T, const float *pose, const float *intrinsics,
+                                uint32_t H, uint32_t W, float near_plane, int cull, uint32_t small_max_pixels, void *workspace,
+                                size_t workspace_bytes, int32_t *counts, int32_t *clip_counts, sn_stream_t stream);
+int sn_rm_mesh_raster_resolve_clip(const float *vertices, const int32_t *triangles, uint32_t V, uint32_t T, const float *pose,
+                                   const float *intrinsics, uint32_t H, uint32_t W, float near_plane, const float *colors, const float *normals,
+                                   const uint8_t *labels, float bg_color, const void *workspace, size_t workspace_bytes, int32_t *triangle_id,
+                                   float *depth, uint8_t *mask, float *image, float *normal, uint8_t *label, sn_stream_t stream);
 
 /* Training-time forward of a bias-free perceptron with 256-wide hidden layers and no skip connections (nerf/network.py:31-66: F.linear +
  * activation per layer; the per-sample mask head in training, network.py:118-123, trainer.py:401-428) in ONE kernel, true fp32 products

@@ -212,6 +212,9 @@ _SIGNATURES = {
     "sn_rm_mesh_raster_project": (_int, [_vp, _u32, _u32, _vp, _vp, _u32, _u32, _f32, _vp, C.c_size_t, _vp, _vp]),
     "sn_rm_mesh_raster_draw": (_int, [_vp, _u32, _u32, _u32, _u32, _i32, _u32, _vp, C.c_size_t, _vp, _vp]),
     "sn_rm_mesh_raster_resolve": (_int, [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _f32, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sn_rm_mesh_raster_draw_clip": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _f32, _i32, _u32, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "sn_rm_mesh_raster_resolve_clip": (_int, [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp, _f32, _vp, C.c_size_t, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _vp]),
     "sn_adam_step": (_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _u32, _vp, _int, _int, _vp]),
     "sn_adam_step_multi": (_int, [C.POINTER(AdamTensor), _u32, C.POINTER(AdamGroup), _u32, _vp, _vp, _vp]),
     "sn_ema_update_multi": (_int, [C.POINTER(EmaTensor), _u32, C.c_double, _vp, _vp, _int, _vp]),

@@ -666,6 +666,15 @@ class NeRFRenderer(nn.Module):
         with torch.no_grad():
             return rm.mesh_rasterize(mesh, pose, intrinsics, H, W, near=self.min_near, cull=cull, bg_color=float(bg_color))
 
+    def render_mesh_clip(self, mesh, pose, intrinsics, H, W, cull=False, bg_color=1):
+        """render_mesh() for a camera inside the mesh -- a training view of a scene mesh: raymarching.mesh_rasterize_clip, which cuts the
+        triangles that cross the plane z = opt.min_near there instead of dropping them, so a floor or a wall that passes the camera ends
+        where the field's render() of that camera starts.  The same arguments and outputs, and "clip_counts" [2]: the triangles that were
+        cut and their drawn pieces.  A mesh wholly in front of the plane gives render_mesh()'s bits."""
+        self._inference_only("render_mesh_clip")
+        with torch.no_grad():
+            return rm.mesh_rasterize_clip(mesh, pose, intrinsics, H, W, near=self.min_near, cull=cull, bg_color=float(bg_color))
+
     # ---------------------------------------------------------------------------------------
     fused_training_ops = True    # RGB-mode training: unit-cube positions, fused small MLPs, one-kernel per-ray head (False: the operator chain)
 

@@ -21,6 +21,7 @@ code in nerf/utils.py and nerf/renderer.py.  This package is that operator surfa
               mesh_smooth          Taubin / Laplacian smoothing in fixed point, with the geometric normals of the result, exact to the bit
               mesh_vertex_normals  the area-weighted vertex normals of a mesh's own triangles
               mesh_rasterize       the mesh seen from one pinhole camera: triangle id, depth, mask and interpolated attributes, exact to the bit
+              mesh_rasterize_clip  the same with the near plane cutting the triangles that cross it: a camera inside the mesh
               vertex_probe_points  the K sample positions of a short ray into the surface at every mesh vertex, and its direction
               vertex_probe_composite  the probes' gated re-integration: colour-head input, coverage and instance label per vertex
     render    render_rays         nerf/renderer.py:221-357 + nerf/network.py:146-186, fused
@@ -48,6 +49,6 @@ from .mesh import lattice_points, isosurface, isosurface_counts, isosurface_emit
 from .mesh import mesh_components, mesh_clean, mesh_filter_counts, mesh_filter_emit  # noqa: F401
 from .mesh import mesh_simplify, mesh_simplify_counts, mesh_simplify_emit  # noqa: F401
 from .mesh import mesh_smooth, mesh_vertex_normals, mesh_smooth_build, mesh_smooth_steps, mesh_smooth_emit, smooth_quantisation  # noqa: F401
-from .mesh import mesh_rasterize, mesh_raster_project, mesh_raster_draw, mesh_raster_resolve, RASTER_SMALL_MAX_PIXELS, RASTER_MAX_SIDE  # noqa: F401
+from .mesh import mesh_rasterize, mesh_rasterize_clip, mesh_raster_project, mesh_raster_draw, mesh_raster_resolve, RASTER_SMALL_MAX_PIXELS, RASTER_MAX_SIDE  # noqa: F401
 from .mesh import vertex_probe_points, vertex_probe_composite, PROBE_SAMPLES  # noqa: F401
 from .render import RenderPlan, Tuning, tuning, last_launch_info, route_info, tile_order_info, render_rays, FP16_SPLIT_LIMIT  # noqa: F401

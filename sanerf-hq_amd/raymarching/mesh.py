@@ -592,12 +592,29 @@ def mesh_raster_project(vertices: torch.Tensor, n_triangles: int, pose: torch.Te
     return ws
 
 
+def _raster_clip_args(what, V, vertices, pose, intrinsics, near):
+    """What the clipped kernels read beside the rows -- the projection's own vertices [V,3], pose, intrinsics and near -- as the pointers and
+    the fp32 value the library takes."""
+    if vertices is None or pose is None or intrinsics is None or near is None:
+        raise ValueError(f"{what}: clip=True needs the projection's vertices, pose, intrinsics and near")
+    _vertices_v3(vertices, what)
+    if vertices.shape[0] != V or pose.numel() != 16 or intrinsics.numel() != 4:
+        raise ValueError(f"{what}: vertices are [{V},3], pose is [4,4], intrinsics [4]")
+    near32 = _raster_near(near, what)
+    return _lib.dev(vertices, "vertices"), _lib.dev(pose, "pose"), _lib.dev(intrinsics, "intrinsics"), near32
+
+
 def mesh_raster_draw(triangles: torch.Tensor, n_vertices: int, H: int, W: int, workspace: torch.Tensor, counts: torch.Tensor, cull: bool = False,
-                     small_max_pixels: int | None = None):
+                     small_max_pixels: int | None = None, clip: bool = False, vertices=None, pose=None, intrinsics=None, near=None,
+                     clip_counts=None):
     """The second phase: the depth test of triangles [T,3] int32 against the rows mesh_raster_project() left, two launches.  A triangle whose
     clipped bounding box holds at most small_max_pixels pixel centres (default RASTER_SMALL_MAX_PIXELS) is scanned by its own lane, the
     others by a wave each from a queue on the device; the value changes the time only, never the result.  counts (int32 [4]) gains the
-    drawn, the dropped, the degenerate and the culled."""
+    drawn, the dropped, the degenerate and the culled.
+
+    clip=True cuts the triangles that cross the near plane instead of dropping them (sn_rm_mesh_raster_draw_clip): it needs the
+    projection's vertices, pose, intrinsics (device tensors, read when the kernels run) and near, and clip_counts (int32 [2]), which it
+    clears and fills with the clipped triangles and their drawn pieces."""
     tri, V, T = _triangles_i32(triangles, n_vertices)
     V, T, H, W = _raster_sizes(V, T, H, W, "mesh_raster_draw")
     small = RASTER_SMALL_MAX_PIXELS if small_max_pixels is None else int(small_max_pixels)
@@ -605,17 +622,29 @@ def mesh_raster_draw(triangles: torch.Tensor, n_vertices: int, H: int, W: int, w
         raise ValueError(f"mesh_raster_draw: small_max_pixels = {small_max_pixels} must be in [0, 2^31)")
     if tuple(counts.shape) != (4,):
         raise ValueError("mesh_raster_draw: counts is int32 [4]")
+    if clip:
+        if clip_counts is None or tuple(clip_counts.shape) != (2,):
+            raise ValueError("mesh_raster_draw: clip=True needs clip_counts, int32 [2]")
+        p_v, p_pose, p_intr, near32 = _raster_clip_args("mesh_raster_draw", V, vertices, pose, intrinsics, near)
+        _lib.check(_lib.lib().sn_rm_mesh_raster_draw_clip(p_v, _lib.dev(tri, "triangles", torch.int32), V, T, p_pose, p_intr, H, W, near32,
+                                                          int(bool(cull)), small, workspace.data_ptr(), workspace.numel(),
+                                                          _lib.dev(counts, "counts", torch.int32), _lib.dev(clip_counts, "clip_counts", torch.int32),
+                                                          _lib.stream()), "sn_rm_mesh_raster_draw_clip")
+        return
     _lib.check(_lib.lib().sn_rm_mesh_raster_draw(_lib.dev(tri, "triangles", torch.int32), V, T, H, W, int(bool(cull)), small, workspace.data_ptr(),
                                                  workspace.numel(), _lib.dev(counts, "counts", torch.int32), _lib.stream()), "sn_rm_mesh_raster_draw")
 
 
 def mesh_raster_resolve(triangles: torch.Tensor, n_vertices: int, H: int, W: int, workspace: torch.Tensor, triangle_id: torch.Tensor,
                         depth: torch.Tensor, mask: torch.Tensor, colors=None, image=None, normals=None, normal=None, labels=None, label=None,
-                        bg_color: float = 1.0):
+                        bg_color: float = 1.0, clip: bool = False, vertices=None, pose=None, intrinsics=None, near=None):
     """The third phase: one lane per pixel turns the depth buffer into triangle_id [H,W] int32 (-1 where empty), depth [H,W] f32 (0) and
     mask [H,W] uint8, and interpolates the attributes that are given, perspective-correct in fp64: colors [V,3] f32 -> image [H,W,3] f32
     (bg_color where empty), normals [V,3] f32 -> normal [H,W,3] (not renormalised; 0), labels [V] uint8 -> label [H,W] uint8 (the corner
-    with the largest weight; 255).  An attribute and its image come together."""
+    with the largest weight; 255).  An attribute and its image come together.
+
+    clip=True after a draw with clip=True (sn_rm_mesh_raster_resolve_clip): a winner that the near plane cut is rebuilt from the
+    projection's vertices, pose, intrinsics and near, which it needs, and its attributes go through the triangle's own corners."""
     tri, V, T = _triangles_i32(triangles, n_vertices)
     V, T, H, W = _raster_sizes(V, T, H, W, "mesh_raster_resolve")
     if any(tuple(x.shape) != (H, W) for x in (triangle_id, depth, mask)):
@@ -626,11 +655,17 @@ def mesh_raster_resolve(triangles: torch.Tensor, n_vertices: int, H: int, W: int
             raise ValueError(f"mesh_raster_resolve: {name} come together")
         if a is not None and (tuple(a.shape) != a_shape or tuple(o.shape) != o_shape):
             raise ValueError(f"mesh_raster_resolve: {name} must be {list(a_shape)} and {list(o_shape)}")
-    _lib.check(_lib.lib().sn_rm_mesh_raster_resolve(_lib.dev(tri, "triangles", torch.int32), V, T, H, W, _lib.dev(colors, "colors"),
-                                                    _lib.dev(normals, "normals"), _lib.dev(labels, "labels", torch.uint8), float(bg_color),
-                                                    workspace.data_ptr(), workspace.numel(), _lib.dev(triangle_id, "triangle_id", torch.int32),
-                                                    _lib.dev(depth, "depth"), _lib.dev(mask, "mask", torch.uint8), _lib.dev(image, "image"),
-                                                    _lib.dev(normal, "normal"), _lib.dev(label, "label", torch.uint8), _lib.stream()),
+    camera = _raster_clip_args("mesh_raster_resolve", V, vertices, pose, intrinsics, near) if clip else None
+    outputs = (workspace.data_ptr(), workspace.numel(), _lib.dev(triangle_id, "triangle_id", torch.int32), _lib.dev(depth, "depth"),
+               _lib.dev(mask, "mask", torch.uint8), _lib.dev(image, "image"), _lib.dev(normal, "normal"), _lib.dev(label, "label", torch.uint8),
+               _lib.stream())
+    attributes = (_lib.dev(colors, "colors"), _lib.dev(normals, "normals"), _lib.dev(labels, "labels", torch.uint8), float(bg_color))
+    if clip:
+        p_v, p_pose, p_intr, near32 = camera
+        _lib.check(_lib.lib().sn_rm_mesh_raster_resolve_clip(p_v, _lib.dev(tri, "triangles", torch.int32), V, T, p_pose, p_intr, H, W, near32,
+                                                             *attributes, *outputs), "sn_rm_mesh_raster_resolve_clip")
+        return
+    _lib.check(_lib.lib().sn_rm_mesh_raster_resolve(_lib.dev(tri, "triangles", torch.int32), V, T, H, W, *attributes, *outputs),
                "sn_rm_mesh_raster_resolve")
 
 
@@ -651,15 +686,36 @@ def mesh_rasterize(mesh: dict, pose, intrinsics, H: int, W: int, near: float = 0
     a triangle with such a corner is dropped whole: there is no clipping.  cull drops the faces whose outside (counter-clockwise, as
     isosurface() orients them) looks away.  One sample per pixel at its centre, the top-left rule on shared edges, nearest surface wins,
     the lower triangle index at equal depth bits: the result depends on neither the order of the triangles nor the run, and equals
-    tests/mesh_raster_ref.py bit for bit; include/sanerf_hip.h has the definition.  Four launches, nothing is read back."""
+    tests/mesh_raster_ref.py bit for bit; include/sanerf_hip.h has the definition.  Four launches, nothing is read back.
+
+    mesh_rasterize_clip() is the same call with the near plane cutting the triangles that cross it."""
+    return _rasterize("mesh_rasterize", False, mesh, pose, intrinsics, H, W, near, cull, colors, labels, normals, bg_color, small_max_pixels)
+
+
+def mesh_rasterize_clip(mesh: dict, pose, intrinsics, H: int, W: int, near: float = 0.05, cull: bool = False, colors=None, labels=None, normals=None,
+                        bg_color: float = 1.0, small_max_pixels: int | None = None) -> dict:
+    """mesh_rasterize() with near-plane clipping, for a camera inside the mesh: a triangle with one or two corners behind the plane z = near
+    (nearer than it, or behind the camera) is cut there instead of being dropped, so a floor or a wall that passes the camera ends in a
+    clean edge, as the field's render of that camera does.  Same arguments, same outputs, and "clip_counts" int32 [2] = the clipped
+    triangles and the pieces of them that were drawn ("counts" counts a clipped triangle once).  A triangle without a corner behind the
+    plane gives the bits mesh_rasterize() gives.
+
+    Only the near plane clips: a corner outside the guard band or not finite still drops its triangle, and so does a crossing point that
+    leaves the guard band.  The crossing points are fp64 functions of the two vertices alone, so two triangles that share a cut edge share
+    its end; the result equals tests/mesh_raster_clip_ref.py bit for bit, whatever the order of the triangles or the run.  Four launches
+    and a 8-byte clear, nothing is read back; capturable as mesh_rasterize() is."""
+    return _rasterize("mesh_rasterize_clip", True, mesh, pose, intrinsics, H, W, near, cull, colors, labels, normals, bg_color, small_max_pixels)
+
+
+def _rasterize(what, clip, mesh, pose, intrinsics, H, W, near, cull, colors, labels, normals, bg_color, small_max_pixels):
     vertices, triangles = _f32(mesh["vertices"]), mesh["triangles"]
-    _vertices_v3(vertices, "mesh_rasterize")
+    _vertices_v3(vertices, what)
     tri, V, T = _triangles_i32(triangles, vertices.shape[0])
-    V, T, H, W = _raster_sizes(V, T, H, W, "mesh_rasterize")
-    near = _raster_near(near, "mesh_rasterize")
+    V, T, H, W = _raster_sizes(V, T, H, W, what)
+    near = _raster_near(near, what)
     bg = float(bg_color)
     if small_max_pixels is not None and not 0 <= int(small_max_pixels) <= RASTER_SMALL_MAX_LIMIT:
-        raise ValueError(f"mesh_rasterize: small_max_pixels = {small_max_pixels} must be in [0, 2^31)")
+        raise ValueError(f"{what}: small_max_pixels = {small_max_pixels} must be in [0, 2^31)")
     _lib.dev(vertices, "vertices")
     dev = vertices.device
     colors = mesh.get("colors") if colors is None else colors
@@ -668,10 +724,10 @@ def mesh_rasterize(mesh: dict, pose, intrinsics, H: int, W: int, near: float = 0
     normals = None if normals is None else _f32(normals)
     for a, name, shape in ((colors, "colors", (V, 3)), (normals, "normals", (V, 3)), (labels, "labels", (V,))):
         if a is not None and tuple(a.shape) != shape:
-            raise ValueError(f"mesh_rasterize: {name} must be {list(shape)}, got {tuple(a.shape)}")
+            raise ValueError(f"{what}: {name} must be {list(shape)}, got {tuple(a.shape)}")
     if labels is not None and labels.dtype != torch.uint8:
-        raise ValueError(f"mesh_rasterize: labels must be uint8, got {labels.dtype}")
-    pose, intrinsics = _raster_camera(pose, intrinsics, dev, "mesh_rasterize")
+        raise ValueError(f"{what}: labels must be uint8, got {labels.dtype}")
+    pose, intrinsics = _raster_camera(pose, intrinsics, dev, what)
     out = {"triangle_id": torch.empty(H, W, device=dev, dtype=torch.int32), "depth": torch.empty(H, W, device=dev, dtype=torch.float32),
            "mask": torch.empty(H, W, device=dev, dtype=torch.uint8), "counts": torch.empty(4, device=dev, dtype=torch.int32)}
     if colors is not None:
@@ -680,10 +736,13 @@ def mesh_rasterize(mesh: dict, pose, intrinsics, H: int, W: int, near: float = 0
         out["normal"] = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
     if labels is not None:
         out["label"] = torch.empty(H, W, device=dev, dtype=torch.uint8)
+    camera = dict(clip=True, vertices=vertices, pose=pose, intrinsics=intrinsics, near=near) if clip else {}
+    if clip:
+        out["clip_counts"] = torch.empty(2, device=dev, dtype=torch.int32)
     ws = mesh_raster_project(vertices, T, pose, intrinsics, H, W, near, out["counts"])
-    mesh_raster_draw(tri, V, H, W, ws, out["counts"], cull, small_max_pixels)
+    mesh_raster_draw(tri, V, H, W, ws, out["counts"], cull, small_max_pixels, clip_counts=out.get("clip_counts"), **camera)
     mesh_raster_resolve(tri, V, H, W, ws, out["triangle_id"], out["depth"], out["mask"], colors, out.get("image"), normals, out.get("normal"),
-                        labels.contiguous() if labels is not None else None, out.get("label"), bg)
+                        labels.contiguous() if labels is not None else None, out.get("label"), bg, **camera)
     return out
 
 

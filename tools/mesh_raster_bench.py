@@ -14,9 +14,16 @@ Beside them, from the same process:
                            12T + 16HW (depth buffer cleared and read) + the outputs;
   (b) field                NeRFRenderer.render() and render_object([1]) of the same camera and size (fused routes, unstaged);
   (c) sweep                project + draw at small_max_pixels = 0, 1, 4, 8, 16, 32, 64, 256, 1024, 2^31 - 1: what the Python default is chosen from.
+  (d) clipping             the raw scene mesh at 800 x 800 with near-plane clipping (mesh_raster_draw / _resolve with clip=True) beside the
+                           unclipped entries of the same build: from the bench camera, where no triangle crosses the near plane, and from
+                           cameras INSIDE the mesh (orbit_pose(0.3, 20, 30) and (0.6, 20, 30)), with the counts and clip_counts.
 Kernel rows: `--warmup` calls first, medians over `--rounds` rounds of `--repeats` calls.
 
     python tools/mesh_raster_bench.py [--size 256] [--out profiles/mesh_raster_bench.txt]
+    python tools/mesh_raster_bench.py --clip             only (d), appended to --out
+    python tools/mesh_raster_bench.py --ab PARENT_TREE   the UNCLIPPED entries of the checkout at PARENT_TREE (built) and of this one, three
+                                                         fresh processes each, alternating, in one visit to the device; appended to --out
+    python tools/mesh_raster_bench.py --unclipped [--tree T]   what --ab starts: one JSON line of the unclipped medians, the package from T
 
 Nothing is asserted about speed; the numbers of one run are reported.  That the thresholds give equal images IS asserted.
 """
@@ -29,7 +36,8 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+TREE = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1]) if "--tree" in sys.argv[:-1] else ROOT     # the checkout whose package is timed
+sys.path.insert(0, TREE)
 
 from sanerf_hq_amd import raymarching as rm, synth  # noqa: E402
 from sanerf_hq_amd.graph import GraphedStep  # noqa: E402
@@ -123,8 +131,100 @@ def bench_mesh(say, name, mesh, pose, intr, H, W, near, w):
     return eager
 
 
+def raster_phases(mesh, pose, intr, H, W, near, clip):
+    """(pair, resolve, out, counts): project + draw and the resolve as callables on preallocated outputs, clipped or not."""
+    vert, tri = mesh["vertices"], mesh["triangles"]
+    V, T = vert.shape[0], tri.shape[0]
+    out = (rm.mesh_rasterize_clip if clip else rm.mesh_rasterize)(mesh, pose, intr, H, W, near=near)
+    counts = out["counts"]
+    camera = dict(clip=True, vertices=vert, pose=pose, intrinsics=intr, near=near) if clip else {}
+    draw_extra = dict(camera, clip_counts=out["clip_counts"]) if clip else {}
+    ws = rm.mesh_raster_project(vert, T, pose, intr, H, W, near, counts)
+
+    def pair():
+        rm.mesh_raster_project(vert, T, pose, intr, H, W, near, counts)
+        rm.mesh_raster_draw(tri, V, H, W, ws, counts, **draw_extra)
+
+    def resolve():
+        rm.mesh_raster_resolve(tri, V, H, W, ws, out["triangle_id"], out["depth"], out["mask"], mesh["colors"], out["image"], None, None, mesh["labels"],
+                               out["label"], 1.0, **camera)
+    return pair, resolve, out, counts
+
+
+def bench_clip(say, mesh, cameras, intr, H, W, near, w):
+    """(d): clip off and on, per camera."""
+    say(f"\n==== (d) near-plane clipping: scene, raw at {W} x {H}, V = {mesh['vertices'].shape[0]}, T = {mesh['triangles'].shape[0]}, near = {near} ====")
+    for name, pose in cameras:
+        rows = {}
+        for clip in (False, True):
+            pair, resolve, out, counts = raster_phases(mesh, pose, intr, H, W, near, clip)
+            pair()
+            resolve()
+            queue = int(_buffers_head(mesh))
+            rows[clip] = (timed(pair, *w), timed(resolve, *w), counts.tolist(), out["clip_counts"].tolist() if clip else None,
+                          float(out["mask"].float().mean()), queue)
+        say(f"\n camera {name}: counts unclipped {rows[False][2]}, covered {rows[False][4]:.3f}, queue {rows[False][5]}; clipped {rows[True][2]}, "
+            f"clip_counts (triangles cut, pieces drawn) {rows[True][3]}, covered {rows[True][4]:.3f}, queue {rows[True][5]}")
+        for k, what in ((0, "project + draw"), (1, "resolve (colours, labels)")):
+            off, on = rows[False][k], rows[True][k]
+            say(line(f"{what}, clip off", off))
+            say(line(f"{what}, clip on", on, f"   on / off = {on['median_ms'] / off['median_ms']:.3f}"))
+
+
+def _buffers_head(mesh):
+    """The queue's length after the last draw on this device: the first word of the module's "mesh_raster" workspace."""
+    from sanerf_hq_amd import _buffers
+    return _buffers.scratch("mesh_raster", mesh["vertices"].device, 16)[:4].view(torch.int32)[0]
+
+
+def unclipped_medians(mesh, pose, intr, H, W, near, w):
+    """The entries that exist with and without the clipped ones, through calls both checkouts have."""
+    vert, tri = mesh["vertices"], mesh["triangles"]
+    V, T = vert.shape[0], tri.shape[0]
+    out = rm.mesh_rasterize(mesh, pose, intr, H, W, near=near)
+    counts = out["counts"]
+    ws = rm.mesh_raster_project(vert, T, pose, intr, H, W, near, counts)
+
+    def pair():
+        rm.mesh_raster_project(vert, T, pose, intr, H, W, near, counts)
+        rm.mesh_raster_draw(tri, V, H, W, ws, counts)
+
+    def resolve():
+        rm.mesh_raster_resolve(tri, V, H, W, ws, out["triangle_id"], out["depth"], out["mask"], mesh["colors"], out["image"], None, None, mesh["labels"],
+                               out["label"], 1.0)
+    pair()
+    return {"project_draw_ms": timed(pair, *w)["median_ms"], "resolve_ms": timed(resolve, *w)["median_ms"],
+            "mesh_rasterize_ms": timed(lambda: rm.mesh_rasterize(mesh, pose, intr, H, W, near=near), *w)["median_ms"]}
+
+
+def run_ab(say, parent, args):
+    """--ab: three fresh processes per checkout, alternating, each printing one JSON line."""
+    import json
+    import subprocess
+    runs = {"parent": [], "this": []}
+    for _ in range(3):
+        for name, tree in (("parent", parent), ("this", ROOT)):
+            cmd = [sys.executable, os.path.abspath(__file__), "--unclipped", "--size", str(args.size), "--quantile", str(args.quantile),
+                   "--warmup", str(args.warmup), "--repeats", str(args.repeats), "--rounds", str(args.rounds), "--tree", tree]
+            text = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=600).stdout
+            runs[name].append(json.loads([ln for ln in text.splitlines() if ln.startswith("{")][-1]))
+            print(f"  [{name}] {runs[name][-1]}", flush=True)
+    say(f"\n==== the unclipped entries before and after the clipped ones were added: scene, raw at 800 x 800, one visit to the device, three fresh "
+        f"processes per checkout, alternating (parent, this, parent, ...); medians of {args.rounds} rounds x {args.repeats} calls, ms ====")
+    for key in ("project_draw_ms", "resolve_ms", "mesh_rasterize_ms"):
+        a, b = [r[key] for r in runs["parent"]], [r[key] for r in runs["this"]]
+        med = statistics.median(b)
+        verdict = "inside" if min(a) <= med <= max(a) else ("below" if med < min(a) else "ABOVE")
+        say(f"  {key:<20} parent {', '.join(f'{x:.4f}' for x in a)}   this {', '.join(f'{x:.4f}' for x in b)}   this median {med:.4f}: {verdict} the "
+            f"parent's spread [{min(a):.4f}, {max(a):.4f}]")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--clip", action="store_true", help="only (d), appended to --out")
+    ap.add_argument("--ab", metavar="PARENT_TREE", help="time the unclipped entries of that built checkout and of this one; appended to --out")
+    ap.add_argument("--unclipped", action="store_true", help="one JSON line of the unclipped entries' medians (what --ab starts)")
+    ap.add_argument("--tree", default=ROOT, help="the checkout whose package is imported (default: this one)")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--quantile", type=float, default=0.99)
     ap.add_argument("--images", default="800,1600")
@@ -133,6 +233,20 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_raster_bench.txt"))
     args = ap.parse_args()
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    def write(mode):
+        if args.out:
+            with open(args.out, mode) as f:
+                f.write("\n".join(lines) + "\n")
+
+    if args.ab:                                            # this process starts the timed ones and never opens the device itself
+        run_ab(say, os.path.abspath(args.ab), args)
+        return write("a")
     if not torch.cuda.is_available():
         raise SystemExit("mesh_raster_bench: no GPU visible; times are measured on the device or not at all")
     dev = torch.device("cuda:0")
@@ -144,12 +258,23 @@ def main():
     model = model.to(dev).eval()
     n = args.size
     w = (args.warmup, args.repeats, args.rounds)
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
+    inside = [(f"inside, orbit_pose({r}, 20, 30)", torch.from_numpy(synth.orbit_pose(r, 20.0, 30.0)).to(dev)) for r in (0.3, 0.6)]
+    if args.clip or args.unclipped:
+        with torch.no_grad():
+            vol = model.density_volume(n)
+            iso = float(torch.quantile(vol.reshape(-1)[:: max(n ** 3 // (1 << 22), 1)], args.quantile))
+            del vol
+            scene = model.extract_mesh(n, threshold=iso, vertex_colors=True, vertex_labels=True)
+            pose = torch.from_numpy(synth.orbit_pose(2.2, 20.0, 30.0)).to(dev)
+            intr = torch.tensor(synth.pinhole_intrinsics(800, 800), device=dev, dtype=torch.float32)
+            if args.unclipped:
+                import json
+                print(json.dumps(unclipped_medians(scene, pose, intr, 800, 800, model.min_near, w)), flush=True)
+                return
+            say(f"\nNear-plane clipping: tools/mesh_raster_bench.py --clip, one run on {torch.cuda.get_device_name(0)} ({n}^3 lattice, threshold {iso:.4g}; "
+                f"{args.warmup} warm-up calls, {args.rounds} rounds x {args.repeats} calls; HIP events).")
+            bench_clip(say, scene, [("outside, orbit_pose(2.2, 20, 30)", pose)] + inside, intr, 800, 800, model.min_near, w)
+        return write("a")
     say(f"Mesh rasteriser: tools/mesh_raster_bench.py, one run on {torch.cuda.get_device_name(0)} (synthetic head model, n_inst 2; {args.warmup} "
         f"warm-up calls, {args.rounds} rounds x {args.repeats} calls; HIP events; kernel shares from torch.profiler).")
     pose_np = synth.orbit_pose(2.2, 20.0, 30.0)
@@ -177,9 +302,9 @@ def main():
             say(line("render()", timed(lambda: model.render(ro, rd, staged=False, perturb=False, H=H, W=W), 2, 3, 3)))
             say(line("render_object([1])", timed(lambda: model.render_object(ro, rd, [1], H=H, W=W), 2, 3, 3)))
             del ro, rd
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        intr = torch.tensor(synth.pinhole_intrinsics(800, 800), device=dev, dtype=torch.float32)
+        bench_clip(say, meshes[0][1], [("outside, orbit_pose(2.2, 20, 30)", pose)] + inside, intr, 800, 800, model.min_near, w)
+    write("w")
 
 
 if __name__ == "__main__":
