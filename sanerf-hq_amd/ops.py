@@ -627,6 +627,15 @@ def _wgrad_into(x2, gy2, gw, tag="small_mlp_wgrad"):
                                    ws.data_ptr(), ws.numel(), _lib.stream()), "sn_linear_wgrad")
 
 
+def _packed16(t):
+    """t as contiguous fp32 whose first element is 16-byte aligned, which sn_mlp_small_* require of x and grad_out whatever the width.
+    A contiguous row slice such as x[1:] of a 10- or 31-wide tensor starts 40 or 124 bytes into its allocation: such a view is repacked
+    (one copy), anything else is passed as it is.  Not needed for aux_in and grad_aux: the kernels read those with scalar loads and the
+    library does not check their alignment; grad_in, out and the hidden buffers are fresh allocations."""
+    t = t.contiguous().float()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _small_mlp_train(Function):
     """A bias-free ReLU `MLP` (network.py:9-29) of the reference network's sizes under autograd, with what follows it on the training path
     folded in: act = SMALL_ACT_TRUNC_EXP0 also returns trunc_exp(out[..., 0]) (network.py:155,179; activation.py:5-17), act =
@@ -639,7 +648,7 @@ class _small_mlp_train(Function):
         lib = _lib.lib()
         lead = x.shape[:-1]
         rows = x.numel() // x.shape[-1]
-        x2 = x.detach().reshape(rows, x.shape[-1]).contiguous().float()
+        x2 = _packed16(x.detach().reshape(rows, x.shape[-1]))
         ws = [w.detach().contiguous() for w in weights]
         desc = _small_desc(ws)
         nl = len(ws)
@@ -678,7 +687,7 @@ class _small_mlp_train(Function):
         lib = _lib.lib()
         rows, dev = x2.shape[0], x2.device
         dout = ws[-1].shape[0]
-        go = g_out.reshape(rows, dout).contiguous().float() if g_out is not None else None
+        go = _packed16(g_out.reshape(rows, dout)) if g_out is not None else None
         ga = g_aux.reshape(rows, 1 if act == SMALL_ACT_TRUNC_EXP0 else dout).contiguous().float() if g_aux is not None else None
         desc = _small_desc(ws)
         need_x = ctx.needs_input_grad[0]
