@@ -1034,6 +1034,52 @@ int sn_rm_mesh_filter_emit(const int32_t *triangles, uint32_t T, uint32_t V, con
                            const void *workspace, size_t workspace_bytes, float *out_vertices, float *out_normals, int32_t *out_triangles,
                            int32_t *source_vertex, uint32_t cap_v, uint32_t cap_t, sn_stream_t stream);
 
+/* Mesh split (raymarching.mesh_split, NeRFRenderer.extract_object_meshes): an indexed triangle mesh with an instance label on every vertex,
+ * taken apart into one mesh per label on the device (csrc/mesh_split.hip).  The definition is this project's; tests/mesh_split_ref.py
+ * restates it in numpy.
+ *
+ * Input: vertices [V,3] fp32, normals [V,3] fp32 or NULL, triangles [T,3] int32, vertex_labels [V] uint8.  Any indexed mesh.
+ *   Parts           P = SN_MESH_SPLIT_PARTS = 33.  part(label) = min(label, 32): part p < 32 is instance id p; part 32 collects every label
+ *                   >= 32, 255 = "none" among them, as sn_rm_vertex_probe_composite and the object gate read such labels.
+ *   Valid triangle  all three indices in [0, V).  An invalid triangle belongs to no part and is never emitted; every index is range-tested
+ *                   before it is used as an address.  Degenerate triangles and duplicates are valid.
+ *   Triangle part   the part that at least two of its corners have; with three different parts, the lowest.  The vote does not depend on
+ *                   the rotation of the corners.
+ *   Membership      vertex v belongs to part p iff some valid triangle of part p has v as a corner.  A vertex may belong to several
+ *                   parts -- a seam vertex is duplicated into each -- and a vertex in no valid triangle belongs to none and is dropped.
+ *   Output          packed, the parts contiguous and in part order.  part_triangle_offsets [P+1], part_vertex_offsets [P+1] (int32,
+ *                   DEVICE): the first row of each part, the totals T' and V' at [P].  out_triangles [T',3]: the triangles of part p in
+ *                   their input order (a stable partition) at rows part_triangle_offsets[p] ..; their indices are LOCAL to the part (row
+ *                   of the vertex - part_vertex_offsets[p]), so that a slice is a stand-alone mesh.  out_vertices [V',3], and out_normals
+ *                   iff normals != NULL: the members of part p in increasing input index, rows copied bit for bit.  source_vertex [V'],
+ *                   source_triangle [T'] (int32, either may be NULL): the input index of every output row.  counts [2] = {V', T'} (uint32,
+ *                   DEVICE); both are at most 3 T.
+ * Every number is an integer or a copied bit pattern; the result depends on neither the launch shape nor the run.
+ *
+ * sn_rm_mesh_split_workspace_bytes(V, T): 12 bytes per vertex (the 64-bit membership word, the row in the lowest part) + 4 per triangle +
+ * 2 P per 64 vertices + 4 P per 1024 vertices + 4 P per 1024 triangles, each of the six parts rounded up to 16.  0 (with a message) if V
+ * or T >= 2^31.
+ * sn_rm_mesh_split_count: the vote and an integer atomicOr of the part's bit into the membership words of the three corners (it places
+ * nothing and is order-independent); per triangle part << 16 | rank inside its segment of 1024; per 64 vertices and part the count inside
+ * the segment; the segment totals part-major, scanned by one workgroup; the two offset arrays and counts -- a memset and three launches.
+ * sn_rm_mesh_split_emit: out_vertices [cap_v,3], out_normals [cap_v,3] (iff normals != NULL), out_triangles [cap_t,3], source_vertex
+ * [cap_v] or NULL, source_triangle [cap_t] or NULL, from the workspace the count left and `triangles` (labels are not read; the workspace
+ * is written: one word per vertex).  Every store is guarded by the capacities: a capacity below the count truncates, and the stored prefix
+ * is the full result's.  Every index is range-tested again: triangles that changed between the two calls misplace rows (an index that cannot
+ * be resolved is emitted as -1) and never write out of bounds.  workspace: 16-byte aligned.
+ * V == 0 or T == 0 is the empty result: SN_OK; the count zeroes those of the offsets and counts that are not NULL and looks at no other
+ * pointer, the emit looks at none -- nor does it with both capacities 0.
+ * Errors before any HIP call: SN_ERR_INVALID (NULL pointer, normals without out_normals, cap_v > 2^31 - 1, misaligned workspace),
+ * SN_ERR_UNSUPPORTED (V or T >= 2^31), SN_ERR_WORKSPACE. */
+#define SN_MESH_SPLIT_PARTS 33
+size_t sn_rm_mesh_split_workspace_bytes(uint32_t V, uint32_t T);
+int sn_rm_mesh_split_count(const int32_t *triangles, uint32_t T, uint32_t V, const uint8_t *vertex_labels, void *workspace,
+                           size_t workspace_bytes, int32_t *part_triangle_offsets, int32_t *part_vertex_offsets, uint32_t *counts,
+                           sn_stream_t stream);
+int sn_rm_mesh_split_emit(const int32_t *triangles, uint32_t T, uint32_t V, const float *vertices, const float *normals, void *workspace,
+                          size_t workspace_bytes, float *out_vertices, float *out_normals, int32_t *out_triangles, int32_t *source_vertex,
+                          int32_t *source_triangle, uint32_t cap_v, uint32_t cap_t, sn_stream_t stream);
+
 /* Mesh simplification (raymarching.mesh_simplify, NeRFRenderer.extract_mesh(simplify)): uniform vertex clustering of an indexed triangle mesh
  * on the device (csrc/mesh_simplify.hip) -- one output vertex per occupied cell of a coarse lattice.  The definition is this project's;
  * tests/mesh_simplify_ref.py restates it in numpy.  Every quantity below is an integer or the correctly rounded result of the stated

@@ -201,6 +201,9 @@ _SIGNATURES = {
     "sn_rm_mesh_component_stats": (_int, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "sn_rm_mesh_filter_count": (_int, [_vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, C.c_size_t, _vp, _vp]),
     "sn_rm_mesh_filter_emit": (_int, [_vp, _u32, _u32, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
+    "sn_rm_mesh_split_workspace_bytes": (C.c_size_t, [_u32, _u32]),
+    "sn_rm_mesh_split_count": (_int, [_vp, _u32, _u32, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "sn_rm_mesh_split_emit": (_int, [_vp, _u32, _u32, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "sn_rm_mesh_simplify_workspace_bytes": (C.c_size_t, [_u32, _u32, _u32]),
     "sn_rm_mesh_simplify_count": (_int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "sn_rm_mesh_simplify_emit": (_int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),

@@ -649,6 +649,49 @@ class NeRFRenderer(nn.Module):
                 mesh["labels"] = attr["labels"]
         return mesh
 
+    def extract_object_meshes(self, instance_ids=None, part_min_triangles=0, part_keep_largest=0, **extract_mesh_kwargs):
+        """Every segmented object as a mesh of its own, {instance id: mesh}, from ONE pass of the density lattice: one
+        extract_mesh(vertex_labels=True, **extract_mesh_kwargs) of the scene, then raymarching.mesh_split by the vertex labels -- instead of
+        one extract_mesh(instance_ids=[k]) per object, each of which sends the whole lattice through the field and the mask head.  Each
+        mesh has the keys of extract_mesh, "labels" included and "colors" / "coverage" with vertex_colors=True, gathered from the scene
+        mesh; indices are local, so each goes to nerf.utils.save_mesh as it is (save_meshes writes them all).
+
+        instance_ids: which parts to return (default: every non-empty part below 32).  Part 32 -- the vertices whose label is no
+        instance, 255 = "none" among them -- is returned only when 32 is asked for; an id that has no triangle is absent from the result.
+        part_min_triangles, part_keep_largest (both 0: off): each part then goes through raymarching.mesh_clean with these, which drops
+        the specks that label noise leaves in a part; a part that is emptied is still returned, with 0 triangles.
+
+        The split sends a seam triangle whole to one part, so objects are open shells where they met a neighbour, unlike the closed
+        surface that extract_mesh(instance_ids=[k]) cuts from the gated density.  Needs opt.with_mask and normals=True.  No-grad only."""
+        self._inference_only("extract_object_meshes")
+        if "vertex_labels" in extract_mesh_kwargs:
+            raise ValueError("extract_object_meshes: vertex_labels is always on")
+        if not extract_mesh_kwargs.get("normals", True):
+            raise ValueError("extract_object_meshes: the vertex labels need normals=True (the probes enter along the normal)")
+        if not self.opt.with_mask:
+            raise RuntimeError("extract_object_meshes: the vertex labels need the mask field (opt.with_mask)")
+        part_min_triangles, part_keep_largest = int(part_min_triangles), int(part_keep_largest)
+        if part_min_triangles < 0 or part_keep_largest < 0:
+            raise ValueError("extract_object_meshes: part_min_triangles and part_keep_largest must not be negative")
+        if instance_ids is not None:
+            instance_ids = sorted({int(i) for i in instance_ids})
+            if any(i < 0 or i >= rm.MESH_SPLIT_PARTS for i in instance_ids):
+                raise ValueError(f"extract_object_meshes: instance ids are 0 .. {rm.MESH_SPLIT_PARTS - 1}, got {instance_ids}")
+        with torch.no_grad():
+            scene = self.extract_mesh(vertex_labels=True, **extract_mesh_kwargs)
+            parts = rm.mesh_split(scene)["parts"]
+            wanted = [p for p in parts if p < rm.MESH_SPLIT_PARTS - 1] if instance_ids is None else [p for p in instance_ids if p in parts]
+            out = {}
+            for p in wanted:
+                part = parts[p]
+                if part_min_triangles or part_keep_largest:
+                    kept = rm.mesh_clean(part, min_triangles=part_min_triangles, keep_largest=part_keep_largest, return_source=True)
+                    rows = kept.pop("source_vertex").long()
+                    kept.update({k: part[k][rows] for k in rm.mesh._CARRIED if k in part})
+                    part = kept
+                out[p] = part
+        return out
+
     def render_mesh(self, mesh, pose, intrinsics, H, W, cull=False, bg_color=1):
         """The image of an extracted mesh from one camera: raymarching.mesh_rasterize of `mesh` (what extract_mesh returns, with its "colors" and
         "labels" where it has them) for pose [4,4] and intrinsics [4] in get_rays' convention, with near = opt.min_near -- the plane at which

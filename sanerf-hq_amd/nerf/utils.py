@@ -369,3 +369,10 @@ def save_mesh(path, vertices, triangles, normals=None, colors=None, labels=None)
         fh.write(vert.tobytes())
         fh.write(face.tobytes())
     return path
+
+
+def save_meshes(prefix, parts):
+    """One save_mesh file per part of {id: mesh} -- what NeRFRenderer.extract_object_meshes and raymarching.mesh_split(...)["parts"] return --
+    at f"{prefix}_{id:02d}.ply", each with the normals, colours and labels its mesh has.  Returns the paths in id order."""
+    return [save_mesh(f"{prefix}_{int(i):02d}.ply", m["vertices"], m["triangles"], m.get("normals"), m.get("colors"), m.get("labels"))
+            for i, m in sorted(parts.items())]

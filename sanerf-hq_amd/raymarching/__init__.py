@@ -17,6 +17,7 @@ code in nerf/utils.py and nerf/renderer.py.  This package is that operator surfa
               isosurface           marching tetrahedra on a density lattice: vertices, normals, triangles (the size is data-dependent)
               mesh_components      connected components of an indexed mesh: labels, triangle and vertex counts per component
               mesh_clean           the mesh without its small components: by triangle count and / or the largest k
+              mesh_split           a labelled mesh taken apart: one stand-alone mesh per instance id, seam vertices duplicated
               mesh_simplify        uniform vertex clustering: one vertex per occupied cell of a coarse lattice, exact to the bit
               mesh_smooth          Taubin / Laplacian smoothing in fixed point, with the geometric normals of the result, exact to the bit
               mesh_vertex_normals  the area-weighted vertex normals of a mesh's own triangles
@@ -47,6 +48,7 @@ from .heads import (  # noqa: F401
 from .object import object_composite, keep_mask_of, LABEL_SKIPPED  # noqa: F401
 from .mesh import lattice_points, isosurface, isosurface_counts, isosurface_emit, ISOSURFACE_MAX_VERTICES  # noqa: F401
 from .mesh import mesh_components, mesh_clean, mesh_filter_counts, mesh_filter_emit  # noqa: F401
+from .mesh import mesh_split, mesh_split_counts, mesh_split_emit, MESH_SPLIT_PARTS  # noqa: F401
 from .mesh import mesh_simplify, mesh_simplify_counts, mesh_simplify_emit  # noqa: F401
 from .mesh import mesh_smooth, mesh_vertex_normals, mesh_smooth_build, mesh_smooth_steps, mesh_smooth_emit, smooth_quantisation  # noqa: F401
 from .mesh import mesh_rasterize, mesh_rasterize_clip, mesh_raster_project, mesh_raster_draw, mesh_raster_resolve, RASTER_SMALL_MAX_PIXELS, RASTER_MAX_SIDE  # noqa: F401

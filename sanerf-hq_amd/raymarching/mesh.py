@@ -1,11 +1,12 @@
-"""Geometry export (mesh.hip, mesh_clean.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_raster.hip, mesh_attr.hip): lattice positions, marching
-tetrahedra on a density lattice, the clean-up of the mesh, its simplification, its smoothing, its image from a camera, and the surface probes
-that give its vertices a colour and an instance label.
+"""Geometry export (mesh.hip, mesh_clean.hip, mesh_split.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_raster.hip, mesh_attr.hip): lattice
+positions, marching tetrahedra on a density lattice, the clean-up of the mesh, its split into one mesh per instance label, its simplification,
+its smoothing, its image from a camera, and the surface probes that give its vertices a colour and an instance label.
 
     lattice_points     positions of a window of the vertices of an nx x ny x nz lattice, optionally contracted -- no meshgrid per chunk
     isosurface         volume [nx,ny,nz], iso -> {"vertices" [V,3], "normals" [V,3] or None, "triangles" [T,3] int32}
     mesh_components    triangles [T,3], V -> labels, triangle and vertex counts per connected component
     mesh_clean         a mesh without its small components (floaters, label noise): by triangle count and / or the largest k
+    mesh_split         a mesh with a label per vertex -> one stand-alone mesh per instance id (tests/mesh_split_ref.py restates it)
     mesh_simplify      uniform vertex clustering: one vertex per occupied cell of a coarse lattice
     mesh_smooth        Taubin / Laplacian smoothing on integers, and the geometric normals of the result; mesh_vertex_normals alone
     mesh_rasterize     the mesh seen from one pinhole camera through a depth buffer: triangle id, depth, mask, interpolated attributes
@@ -264,6 +265,114 @@ def mesh_clean(mesh: dict, min_triangles: int = 0, keep_largest: int = 0, return
         mesh_filter_emit(triangles, vertices, normals, ws, out["vertices"], out["normals"], out["triangles"], source)
     if return_source:
         out["source_vertex"] = source
+    return out
+
+
+# ---- split by vertex label: one mesh per instance (mesh_split.hip) ------------------------------------------------------------------------
+MESH_SPLIT_PARTS = 33                  # include/sanerf_hip.h: SN_MESH_SPLIT_PARTS -- instance ids 0 .. 31, and part 32 for every label >= 32
+_CARRIED = ("colors", "coverage", "labels")    # per-vertex attributes of extract_mesh that a part takes along through source_vertex
+
+
+def _vertex_labels_u8(labels, V, what):
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or tuple(labels.shape) != (V,):
+        got = (tuple(labels.shape), labels.dtype) if torch.is_tensor(labels) else type(labels).__name__
+        raise RuntimeError(f"{what}: vertex_labels must be a uint8 tensor [{V}], one label per vertex, got {got}")
+    return labels.contiguous()
+
+
+def mesh_split_counts(triangles: torch.Tensor, n_vertices: int, vertex_labels: torch.Tensor):
+    """The first half of mesh_split(): (offsets, counts, workspace) with offsets = {"part_triangle_offsets", "part_vertex_offsets"}, int32
+    [34] each -- the first row of every part, the totals last -- and counts = {V', T'} as an int32 [2] tensor, all on the device (nothing
+    is read back), and the workspace that mesh_split_emit() takes -- the module's one "mesh_split" buffer per device: the next call on
+    that device reuses it.  vertex_labels: [n_vertices] uint8."""
+    tri, V, T = _triangles_i32(triangles, n_vertices)
+    dev = tri.device
+    lab = _vertex_labels_u8(vertex_labels, V, "mesh_split_counts")
+    p_tri, p_lab = _lib.dev(tri, "triangles", torch.int32), _lib.dev(lab, "vertex_labels", torch.uint8)
+    offsets = {k: torch.zeros(MESH_SPLIT_PARTS + 1, device=dev, dtype=torch.int32) for k in ("part_triangle_offsets", "part_vertex_offsets")}
+    counts = torch.zeros(2, device=dev, dtype=torch.int32)
+    L = _lib.lib()
+    ws = _workspace("mesh_split", int(L.sn_rm_mesh_split_workspace_bytes(V, T)), dev, empty_ok=not (V and T))
+    if V and T:
+        _lib.check(L.sn_rm_mesh_split_count(p_tri, T, V, p_lab, ws.data_ptr(), ws.numel(), offsets["part_triangle_offsets"].data_ptr(), offsets["part_vertex_offsets"].data_ptr(),
+                                            counts.data_ptr(), _lib.stream()), "sn_rm_mesh_split_count")
+    return offsets, counts, ws
+
+
+def mesh_split_emit(triangles: torch.Tensor, vertices: torch.Tensor, normals, workspace: torch.Tensor, out_vertices: torch.Tensor, out_normals,
+                    out_triangles: torch.Tensor, source_vertex=None, source_triangle=None, cap_v: int | None = None, cap_t: int | None = None):
+    """The second half: fills out_vertices [>= cap_v, 3] f32, out_normals (same shape; iff normals is given), out_triangles [>= cap_t, 3]
+    int32, source_vertex [>= cap_v] and source_triangle [>= cap_t] int32 (or None) from the workspace mesh_split_counts() left.  Capacities
+    below the counts truncate: the stored prefix is the full result's."""
+    tri, V, T = _triangles_i32(triangles, vertices.shape[0])
+    per_vertex = [out_vertices] + ([] if normals is None else [out_normals]) + ([] if source_vertex is None else [source_vertex])
+    cap_v, cap_t = _capacities("mesh_split_emit", cap_v, cap_t, per_vertex, out_triangles)
+    if source_triangle is not None and source_triangle.shape[0] < cap_t:
+        raise ValueError("mesh_split_emit: a capacity exceeds its buffer")
+    _rows3("mesh_split_emit", vertices, out_vertices, out_triangles, out_normals if normals is not None else None)
+    if normals is not None and tuple(normals.shape) != tuple(vertices.shape):
+        raise RuntimeError("mesh_split_emit: vertices, normals and triangles are [n,3]")
+    _lib.check(_lib.lib().sn_rm_mesh_split_emit(_lib.dev(tri, "triangles", torch.int32), T, V, _lib.dev(vertices, "vertices"),
+                                                _lib.dev(normals, "normals"), workspace.data_ptr(), workspace.numel(),
+                                                _lib.dev(out_vertices, "out_vertices"), _lib.dev(out_normals if normals is not None else None, "out_normals"),
+                                                _lib.dev(out_triangles, "out_triangles", torch.int32),
+                                                _lib.dev(source_vertex, "source_vertex", torch.int32),
+                                                _lib.dev(source_triangle, "source_triangle", torch.int32), cap_v, cap_t, _lib.stream()),
+               "sn_rm_mesh_split_emit")
+
+
+def mesh_split(mesh: dict, labels=None, return_source: bool = False) -> dict:
+    """A labelled mesh taken apart: one mesh per instance.  mesh: the keys of isosurface() ("vertices" [V,3] f32, "normals" [V,3] f32 or
+    None, "triangles" [T,3] int32; any indexed mesh on the device); labels [V] uint8, default mesh["labels"] -- what
+    extract_mesh(vertex_labels=True) and vertex_attributes(labels=True) give.  Part p < 32 is instance id p and part 32 collects every
+    label >= 32 (255 = "none" among them).  A triangle goes, whole, to the part that two of its corners have (three different ones: the
+    lowest); a vertex goes to every part that has a triangle of it, so a seam vertex is duplicated.  include/sanerf_hip.h has the
+    definition; tests/mesh_split_ref.py restates it.
+
+    Returns {"parts": {part id: mesh}, non-empty parts only, each a view of the packed arrays with "vertices", "normals", "triangles"
+    (indices local to the part: a stand-alone mesh) and, where the input mesh has them, "colors", "coverage" and "labels" gathered through
+    source_vertex; "vertices", "normals", "triangles": the packed arrays, parts contiguous and in part order; "part_triangle_offsets",
+    "part_vertex_offsets": int32 [34] on the device; return_source: "source_vertex" [V'], "source_triangle" [T'] int32, the input index of
+    every packed row}.  Triangles keep their input order inside a part and vertices their increasing index; rows are copied bit for bit.
+    Not done: seams are not re-cut along the label boundary, parts are not closed (a part is an open shell where it met its neighbour), and
+    attributes are gathered, not recomputed.
+
+    The two totals {V', T'} are read back once to allocate the result exactly (as mesh_clean does) and the 2 x 34 offsets once to slice
+    it: this call cannot be captured as a graph.  Deterministic: two calls give equal bits."""
+    vertices, normals, triangles = _f32(mesh["vertices"]), mesh["normals"], mesh["triangles"]
+    normals = None if normals is None else _f32(normals)
+    _vertices_v3(vertices, "mesh_split")
+    V, dev = vertices.shape[0], vertices.device
+    if labels is None:
+        labels = mesh.get("labels")
+        if labels is None:
+            raise ValueError("mesh_split: no labels given and the mesh has no 'labels' (extract_mesh(vertex_labels=True))")
+    labels = _vertex_labels_u8(labels, V, "mesh_split")
+    carried = {k: mesh[k] for k in _CARRIED if mesh.get(k) is not None}
+    offsets, counts, ws = mesh_split_counts(triangles, V, labels)
+    nv, nt = _read_counts(counts)
+    if nv > ISOSURFACE_MAX_VERTICES:
+        raise RuntimeError(f"mesh_split: {nv} vertices exceed the int32 indices of the result")
+    out = _empty_mesh(nv, nt, dev, normals is not None)
+    want_source_v = return_source or bool(carried)
+    source_v = torch.empty(nv, device=dev, dtype=torch.int32) if want_source_v else None
+    source_t = torch.empty(nt, device=dev, dtype=torch.int32) if return_source else None
+    if nv or nt:
+        mesh_split_emit(triangles, vertices, normals, ws, out["vertices"], out["normals"], out["triangles"], source_v, source_t)
+    packed = {k: v[source_v.long()] for k, v in carried.items()}
+    toff, voff = offsets["part_triangle_offsets"].tolist(), offsets["part_vertex_offsets"].tolist()
+    parts = {}
+    for p in range(MESH_SPLIT_PARTS):
+        (t0, t1), (v0, v1) = toff[p:p + 2], voff[p:p + 2]
+        if t1 > t0:
+            part = {"vertices": out["vertices"][v0:v1], "normals": None if normals is None else out["normals"][v0:v1],
+                    "triangles": out["triangles"][t0:t1]}
+            part.update({k: v[v0:v1] for k, v in packed.items()})
+            parts[p] = part
+    out.update(offsets)
+    out["parts"] = parts
+    if return_source:
+        out["source_vertex"], out["source_triangle"] = source_v, source_t
     return out
 
 
