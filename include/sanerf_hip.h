@@ -687,6 +687,12 @@ typedef struct sn_render_tuning {
                                   * (k_prop_stage<..., UN = 2>, 3 waves per SIMD instead of 5; bit-neutral): 0 automatic, 1 never, 2 always */
     int32_t experiment;          /* SN_EXP_*: variants that were built, verified bit-identical and measured SLOWER; honoured only by
                                   * a library built with -DSN_EXPERIMENTS (sn_build_flags), SN_ERR_UNSUPPORTED otherwise */
+    int32_t persistent_tiles;    /* last stage, plain linear-tail launch (no feature stage, no early stop or early-out, full product form): ONE resident
+                                  * workgroup of 8 waves per CU stages the weights once and every wave pulls 64-ray wave tiles from eight queues, one per
+                                  * XCD range of linear_tile_order (sn_rm_tile_queue_info states them), instead of one 4-wave workgroup per 256-ray tile
+                                  * (bit-neutral): 0 automatic (launches with more wave tiles than 8 x the device's CUs; with two row bands on two streams, than 32 x),
+                                  * 1 never, 2 always */
+    int32_t persistent_wgs;      /* workgroups of that launch: 0 = one per CU, n = exactly n (measurements and tests: any n >= 1 renders every tile) */
 } sn_render_tuning;
 
 typedef struct sn_render_cfg {
@@ -795,6 +801,9 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
 typedef struct sn_launch_info {
     char     final_kernel[64];
     uint32_t workgroups, lds_bytes, dense_levels, gathers_per_wave_sample, launches;
+    /* workgroups counts 256-ray TILE UNITS of the launch (what the grid of the ordinary launch is) whichever form ran; persistent_tiles: 1 when the
+     * persistent form ran (tuning.persistent_tiles), whose real grid -- 512-thread workgroups -- is grid_workgroups (= workgroups otherwise) */
+    uint32_t persistent_tiles, grid_workgroups;
 } sn_launch_info;
 int sn_rm_last_launch_info(sn_launch_info *info);
 /* Dry run: what sn_rm_last_launch_info would report after a successful sn_rm_render_rays(cfg, io) -- the last chunk's workgroups, launches =
@@ -802,6 +811,18 @@ int sn_rm_last_launch_info(sn_launch_info *info);
  * nothing is launched, no pointer is dereferenced, io->workspace is not needed.  Same statuses and messages as sn_rm_render_rays.
  * (lds_bytes is the dynamic LDS of the launch itself, the 84 KiB of SN_EXP_FINAL_ONE_WG included.) */
 int sn_rm_render_route_info(const sn_render_cfg *cfg, const sn_render_io *io, sn_launch_info *out);
+/* The same for a device of `compute_units` CUs: sn_rm_render_rays asks its device once and plans with that figure; the call above plans
+ * with 0 = not known, under which the automatic rule of tuning.persistent_tiles stays off (and a forced persistent launch is sized for 256). */
+int sn_rm_render_route_info_cus(const sn_render_cfg *cfg, const sn_render_io *io, uint32_t compute_units, sn_launch_info *out);
+
+/* The tile queues of the persistent last stage (tuning.persistent_tiles), on the host alone (no HIP call, the arithmetic the kernel runs): a
+ * launch of `units` 256-ray tile units (sn_launch_info.workgroups) has wave_tiles = 4 * units wave-tile ids, the ids sn_rm_tile_order_info walks
+ * as tile_id * 4 + wave; queue `queue` (0..7) holds [begin, end): 4 x the contiguous tile range linear_tile_order = `order` gives XCD `queue`,
+ * or, for the orders without that remap (1), everything in queue 0.  The eight ranges partition the ids. */
+typedef struct sn_tile_queue_info {
+    uint32_t queues, wave_tiles, begin, end;
+} sn_tile_queue_info;
+int sn_rm_tile_queue_info(uint32_t units, int32_t order, int32_t wave_tile, uint32_t queue, sn_tile_queue_info *out);
 
 /* Which part of a W x rows image (one launch: a whole image, a row band, a row chunk) workgroup `workgroup` (blockIdx.x) of the render stages
  * takes under tuning.wave_tile / tuning.linear_tile_order = `order`, on the host alone: no HIP call, the same arithmetic the kernels run.

@@ -91,12 +91,18 @@ class CollateDesc(C.Structure):
 
 class RenderTuning(C.Structure):
     _fields_ = [("mlp_mode", C.c_int32), ("per_sample_form", C.c_int32), ("densify", C.c_int32), ("linear_tile_order", C.c_int32),
-                ("prop_sp_max_rays", C.c_int32), ("final_sp_max_rays", C.c_int32), ("feat_levels", C.c_int32), ("band_streams", C.c_int32), ("exact_early_out", C.c_int32), ("wave_tile", C.c_int32), ("prop_sp_lanes", C.c_int32), ("feat_patch", C.c_int32), ("prop_pair", C.c_int32), ("experiment", C.c_int32)]
+                ("prop_sp_max_rays", C.c_int32), ("final_sp_max_rays", C.c_int32), ("feat_levels", C.c_int32), ("band_streams", C.c_int32), ("exact_early_out", C.c_int32), ("wave_tile", C.c_int32), ("prop_sp_lanes", C.c_int32), ("feat_patch", C.c_int32), ("prop_pair", C.c_int32), ("experiment", C.c_int32),
+                ("persistent_tiles", C.c_int32), ("persistent_wgs", C.c_int32)]
 
 
 class LaunchInfo(C.Structure):
     _fields_ = [("final_kernel", C.c_char * 64), ("workgroups", C.c_uint32), ("lds_bytes", C.c_uint32), ("dense_levels", C.c_uint32),
-                ("gathers_per_wave_sample", C.c_uint32), ("launches", C.c_uint32)]
+                ("gathers_per_wave_sample", C.c_uint32), ("launches", C.c_uint32), ("persistent_tiles", C.c_uint32), ("grid_workgroups", C.c_uint32)]
+
+
+class TileQueueInfo(C.Structure):
+    """sn_tile_queue_info: one of the eight wave-tile queues of the persistent last stage (raymarching.tile_queue_info)."""
+    _fields_ = [("queues", C.c_uint32), ("wave_tiles", C.c_uint32), ("begin", C.c_uint32), ("end", C.c_uint32)]
 
 
 class TileOrderInfo(C.Structure):
@@ -252,6 +258,8 @@ _SIGNATURES = {
     "sn_rm_last_launch_info": (_int, [_vp]),
     "sn_rm_render_route_info": (_int, [C.POINTER(RenderCfg), C.POINTER(RenderIO), _vp]),
     "sn_rm_tile_order_info": (_int, [_u32, _u32, _i32, _i32, _u32, C.POINTER(TileOrderInfo)]),
+    "sn_rm_render_route_info_cus": (_int, [C.POINTER(RenderCfg), C.POINTER(RenderIO), _u32, _vp]),
+    "sn_rm_tile_queue_info": (_int, [_u32, _i32, _i32, _u32, C.POINTER(TileQueueInfo)]),
     "sn_debug_eval": (_int, [_int, _vp, _vp, _u32, _vp, _vp]),
 }
 

@@ -19,6 +19,8 @@
 //                  two half-waves with v_permlane32_swap, weights pre-packed in LDS in
 //                  A-operand order) -> sigma/geo features -> ordered compositing in
 //                  registers -> per-ray view MLP -> sigmoid -> image/depth/weights_sum.
+//   k_final_stage_pt  the same code per ray (final_stage_rays) under a persistent launch: one 8-wave
+//                  workgroup per CU, every wave pulls 8x8 tiles from per-XCD queues.
 #include "sn_common.h"
 #include "sh_basis.inc"
 
@@ -58,6 +60,16 @@ __host__ __device__ __forceinline__ uint32_t xcd_tile_id(uint32_t b, uint32_t nw
     const uint32_t xcd = b & 7u, q = nwg >> 3, r = nwg & 7u;
     return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + (b >> 3);
 }
+// The eight tile queues of the persistent launch of the last stage (k_final_stage_pt).  Queue x holds the WAVE tiles of the workgroup-tile
+// range xcd_tile_id() gives XCD x in a launch of `units` workgroup tiles -- the same contiguous ranges x 4, in the same order: ids
+// [begin, end).  xcd = 0 (tile orders without the remap): one queue, number 0, over all ids.  The ranges partition [0, 4 * units).
+__host__ __device__ __forceinline__ void tile_queue_range(uint32_t x, uint32_t units, int xcd, uint32_t &begin, uint32_t &end) {
+    if (!xcd) { begin = 0u; end = x == 0u ? 4u * units : 0u; return; }
+    const uint32_t q = units >> 3, r = units & 7u;
+    const uint32_t first = x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q;      // = xcd_tile_id(x, units)
+    begin = 4u * first;
+    end = 4u * (first + q + (x < r ? 1u : 0u));
+}
 __device__ __forceinline__ uint32_t tile_id_x(const RayCommon &rc, uint32_t b, uint32_t nwg) { return rc.xcd_swizzle ? xcd_tile_id(b, nwg) : b; }
 __device__ __forceinline__ uint32_t tile_id(const RayCommon &rc) { return tile_id_x(rc, blockIdx.x, gridDim.x); }
 
@@ -93,14 +105,13 @@ __host__ __device__ __forceinline__ void wave_tile_of(uint32_t g, uint32_t tx8, 
 // ceil(wave tiles / 4) workgroups whatever the shape -- a 200-row band of a 1600-wide image (BASELINE configs[3] on 8 GPUs) is 1250
 // workgroups, not the 1300 of whole 16x16 tiles: tools/staircase.py shows the stages' time stepping at multiples of 256 workgroups
 // (one per CU), 1300 is just past the step at 1280 (profiles/r04/staircase_1600.txt).  Host twin: blocks_for().
-__device__ __forceinline__ bool ray_of_lane(const RayCommon &rc, uint32_t wg, uint32_t &n) {
-    const uint32_t tid = threadIdx.x;
+// (g: the wave tile id, wave-uniform -- four consecutive ones per workgroup of the ordinary launch, one per fetch of the persistent one;
+//  linear order: rays g * 64 .. g * 64 + 63)
+__device__ __forceinline__ bool ray_of_wave_tile(const RayCommon &rc, uint32_t g, uint32_t lane, uint32_t &n) {
     if (rc.W) {
         // wave tile = 2^tlw x 2^(6 - tlw) pixels (8x8 unless sn_render_tuning.wave_tile says otherwise; tx8 / ty8 keep their round-1 names)
         const uint32_t tlw = rc.tlw, tlh = 6u - tlw, tw = 1u << tlw, th = 1u << tlh;
         const uint32_t tx8 = (rc.W + tw - 1u) >> tlw, ty8 = (rc.rows + th - 1u) >> tlh;
-        const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63u;      // (the wave tile is the same for all lanes: scalar arithmetic)
-        const uint32_t g = wg * 4u + wave;                       // wave tile
         uint32_t wx, wy;
         wave_tile_of(g, tx8, ty8, rc.st_w, rc.st_h, wx, wy);   // (wx >= tx8: padding of the last workgroup)
         const uint32_t py = (wy << tlh) + (lane >> tlw);
@@ -109,10 +120,15 @@ __device__ __forceinline__ bool ray_of_lane(const RayCommon &rc, uint32_t wg, ui
         n = ok ? py * rc.W + px : 0u;
         return ok;
     }
-    n = wg * 256u + tid;
+    n = g * 64u + lane;
     const bool ok = n < rc.N;
     if (!ok) n = 0;
     return ok;
+}
+__device__ __forceinline__ bool ray_of_lane(const RayCommon &rc, uint32_t wg, uint32_t &n) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the wave tile is the same for all lanes: scalar arithmetic)
+    return ray_of_wave_tile(rc, wg * 4u + wave, tid & 63u, n);
 }
 
 struct RaySetup {
@@ -1948,73 +1964,39 @@ enum { MLP_VALU = 0, MLP_F32 = 1, MLP_F16X3 = 2 };
 // the A/B partner of the spread order, instantiated by experiments builds only (SN_EXP_MATRIX_CLUMPED)
 // CANON: the hashed levels of the FinalLv path in the canonical corner order instead of by cell parity (round 10): the A/B partner of the parity
 // order, instantiated by experiments builds only (SN_EXP_GATHER_CANONICAL)
-template <typename TT, int L, int C, int H1, int H2, int NOUT, int VH, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3, bool PORD = false,
-          bool CANON = false>
-__global__ __launch_bounds__(256, MODE == MLP_VALU ? 1 : SN_FINAL_WAVES) void k_final_stage(FinalArgs a) {
-    SN_POISON_ALL();
-    static_assert(NP == 3 || (LT && !L0L && !AUX), "reduced-product MLP forms: plain linear-tail instantiations only");
-    static_assert(!LT || (MODE == MLP_F16X3 && K >= 4 && K <= 8), "linear tail: split-fp16 MLP on the FinalLv path");
-    static_assert(!L0L || (LT && sizeof(TT) == 2), "LDS-resident level 0: fp16 tables, linear-tail instantiation (80 KiB: 32 packed weights + 4 x 8 swizzled slabs + 16 level 0)");
+// What one wave needs of the workgroup's LDS to march a wave tile: the carve-up the launch form made (k_final_stage: per workgroup tile;
+// k_final_stage_pt: once per resident workgroup)
+struct FinalLds {
+    float *lds;                 // base: packed grid-MLP weights (matrix-core forms), w3p inside
+    float *fe;                  // this lane's feature column base
+    uint32_t fstride;           // distance between consecutive features of one lane
+    float *actB;                // VALU form
+    float *lds_vw;              // view_mlp weights (padded rows), all three layers back to back
+    uint32_t *slab_hi, *slab_lo;      // MLP_F16X3: this wave's split feature images
+    const uint32_t *l0tab;      // L0L: level 0 of the main grid
+};
+
+// The last stage of ONE wave tile (g, wave-uniform): ray set-up, the march, the per-ray colour head, the output stores.  Both launch forms
+// run this code.  PT (persistent launch): the view weights are resident (no barrier, no staging behind the march) and the clock probe
+// belongs to the caller's loop.
+template <typename TT, int L, int C, int H1, int H2, int NOUT, int VH, int MODE, int K, bool AUX, bool LT, bool L0L, bool EO, int NP, bool PORD, bool CANON, bool PT>
+__device__ __forceinline__ void final_stage_rays(const FinalArgs &a, const FinalLds &fl, const uint32_t g) {
     constexpr int SLAB_DW = L0L ? 16 : SLAB_STRIDE;       // dwords per slab row
     constexpr bool MFMA = MODE != MLP_VALU;
     constexpr int IN = L * C;
     constexpr int GEO = NOUT - 1;
     constexpr int NSH = 16;                       // sh degree 4 (network.py:97)
     constexpr int NCOL = GEO + NSH;
-    static_assert(!MFMA || (IN == 32 && H1 == 64 && H2 == 64 && NOUT == 16), "MFMA path is the 32-64-64-16 MLP");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    // ---- LDS carve-up ----
-    //  MFMA : [ packed weights 32 KiB | per-wave feature slabs fe[IN][64] x 4 ]
-    //  VALU : [ activation columns actA[64][256] | actB[64][256] ]  (weights read through the scalar cache)
-    float *fe;            // this lane's feature column base
-    uint32_t fstride;     // distance between consecutive features of one lane
-    float *actB = nullptr;
     constexpr int VW0 = VH * PadIn<NCOL>::value, VW1 = VH * PadIn<VH>::value;   // third layer: 3 * PadIn<VH> floats follow
-    float *lds_vw;        // view_mlp weights (padded rows), all three layers back to back
-    uint32_t *slab_hi = nullptr, *slab_lo = nullptr;      // MLP_F16X3: this wave's split feature images
-    if constexpr (MODE == MLP_F16X3) {
-        static_assert(PACK16_U4 * 4 == PACK_FLOATS, "both packings fill the same 32 KiB");
-        for (uint32_t i = threadIdx.x; i < (uint32_t)PACK16_U4; i += 256u)
-            reinterpret_cast<uint4 *>(lds)[i] = reinterpret_cast<const uint4 *>(a.mlp_pack)[i];
-        if constexpr (LT) { __syncthreads(); stage_w3p(lds + W3P_OFFSET, a.w[2]); }     // over the (unused) packed layer-3 operands
-        constexpr int WAVE_SLAB = 2 * 64 * SLAB_DW;       // dwords: hi image + lo image
-        float *wave_base = lds + PACK_FLOATS + (threadIdx.x >> 6) * WAVE_SLAB;
-        slab_hi = reinterpret_cast<uint32_t *>(wave_base);
-        slab_lo = slab_hi + 64 * SLAB_DW;
-        if constexpr (L0L) {                              // level 0 of the main grid, rows as stored (half2 = one dword per vertex)
-            uint32_t *l0w = reinterpret_cast<uint32_t *>(lds + PACK_FLOATS + 4 * WAVE_SLAB);
-            const uint32_t rows0 = a.g.res[0] * a.g.res[0] * a.g.res[0];
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(a.table) + a.g.off[0];
-            for (uint32_t i = threadIdx.x; i < rows0; i += 256u) l0w[i] = src[i];
-        }
-        fe = wave_base + (threadIdx.x & 63u);             // after the march the slab is reused as fp32 columns
-        fstride = 64u;
-        lds_vw = lds;                                     // overlays the packed weights once the march is over
-    } else if constexpr (MODE == MLP_F32) {
-        for (uint32_t i = threadIdx.x; i < (uint32_t)PACK_FLOATS / 4u; i += 256u)
-            reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(a.mlp_pack)[i];
-        fe = lds + PACK_FLOATS + (threadIdx.x >> 6) * (IN * 64) + (threadIdx.x & 63u);
-        fstride = 64u;
-        lds_vw = lds;
-    } else {
-        fe = lds + threadIdx.x;
-        actB = lds + 64 * 256 + threadIdx.x;
-        fstride = 256u;
-        lds_vw = lds + 2 * 64 * 256;
-    }
-    if constexpr (!MFMA) {
-        stage_weights<NCOL, VH>(lds_vw, a.vw[0]);
-        stage_weights<VH, VH>(lds_vw + VW0, a.vw[1]);
-        stage_weights<VH, 3>(lds_vw + VW0 + VW1, a.vw[2]);
-    }
-    __syncthreads();
-    clock_probe(0);
-    const uint32_t *l0tab = reinterpret_cast<const uint32_t *>(lds + PACK_FLOATS + 4 * 2 * 64 * SLAB_DW);   // L0L: level 0 of the main grid
+    float *const lds = fl.lds, *const fe = fl.fe, *const actB = fl.actB, *const lds_vw = fl.lds_vw;
+    const uint32_t fstride = fl.fstride;
+    uint32_t *const slab_hi = fl.slab_hi, *const slab_lo = fl.slab_lo;
+    const uint32_t *const l0tab = fl.l0tab;
+    (void)SLAB_DW; (void)MFMA; (void)actB; (void)l0tab; (void)VW0; (void)VW1;
 
     uint32_t n;
-    const uint32_t wg = tile_id(a.rc);
-    const bool ok = ray_of_lane(a.rc, wg, n);
-    const uint32_t r = wg * 256u + threadIdx.x;
+    const bool ok = ray_of_wave_tile(a.rc, g, threadIdx.x & 63u, n);
+    const uint32_t r = g * 64u + (threadIdx.x & 63u);          // scratch column (= tile id * 256 + threadIdx.x of the ordinary launch)
     const uint32_t Npad = a.rc.Npad;
     RaySetup rs;
     setup_ray(a.rc, n, rs);
@@ -2287,7 +2269,7 @@ __global__ __launch_bounds__(256, MODE == MLP_VALU ? 1 : SN_FINAL_WAVES) void k_
         }
     }
 
-    clock_probe(1);
+    if constexpr (!PT) clock_probe(1);
     if constexpr (AUX) {            // the feature stage reads every weight: the samples behind the exact early-out carry weight 0 (and are skipped there too)
         if (a.w_out) for (uint32_t jj = j_stop; jj < T; ++jj) a.w_out[(size_t)jj * Npad + r] = 0.0f;
     }
@@ -2311,9 +2293,10 @@ __global__ __launch_bounds__(256, MODE == MLP_VALU ? 1 : SN_FINAL_WAVES) void k_
     }
     // ---- per-ray colour head: view_mlp(f_image) -> sigmoid -> + (1 - wsum) * bg (renderer.py:340-357) ----
     static_assert(VH <= IN && NCOL <= IN && IN * 64 <= 2 * 64 * SLAB_DW, "view MLP activations reuse the feature column / slab");
-    if constexpr (MFMA) {
+    if constexpr (MFMA && !PT) {
         // every wave marches the same T steps: once all are done the 32 KiB of packed MLP weights are dead and
-        // the view-MLP weights take their place (keeps the workgroup under 80 KiB of LDS = 2 workgroups per CU)
+        // the view-MLP weights take their place (keeps the workgroup under 80 KiB of LDS = 2 workgroups per CU).
+        // (The persistent launch keeps the view weights in a region of their own: no wave waits for another there.)
         __syncthreads();
         stage_weights<NCOL, VH>(lds_vw, a.vw[0]);
         stage_weights<VH, VH>(lds_vw + VW0, a.vw[1]);
@@ -2360,6 +2343,149 @@ __global__ __launch_bounds__(256, MODE == MLP_VALU ? 1 : SN_FINAL_WAVES) void k_
             q[3] = dep;
         }
     }
+}
+
+template <typename TT, int L, int C, int H1, int H2, int NOUT, int VH, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3, bool PORD = false,
+          bool CANON = false>
+__global__ __launch_bounds__(256, MODE == MLP_VALU ? 1 : SN_FINAL_WAVES) void k_final_stage(FinalArgs a) {
+    SN_POISON_ALL();
+    static_assert(NP == 3 || (LT && !L0L && !AUX), "reduced-product MLP forms: plain linear-tail instantiations only");
+    static_assert(!LT || (MODE == MLP_F16X3 && K >= 4 && K <= 8), "linear tail: split-fp16 MLP on the FinalLv path");
+    static_assert(!L0L || (LT && sizeof(TT) == 2), "LDS-resident level 0: fp16 tables, linear-tail instantiation (80 KiB: 32 packed weights + 4 x 8 swizzled slabs + 16 level 0)");
+    constexpr int SLAB_DW = L0L ? 16 : SLAB_STRIDE;       // dwords per slab row
+    constexpr bool MFMA = MODE != MLP_VALU;
+    constexpr int IN = L * C;
+    constexpr int GEO = NOUT - 1;
+    constexpr int NSH = 16;                       // sh degree 4 (network.py:97)
+    constexpr int NCOL = GEO + NSH;
+    static_assert(!MFMA || (IN == 32 && H1 == 64 && H2 == 64 && NOUT == 16), "MFMA path is the 32-64-64-16 MLP");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    // ---- LDS carve-up ----
+    //  MFMA : [ packed weights 32 KiB | per-wave feature slabs fe[IN][64] x 4 ]
+    //  VALU : [ activation columns actA[64][256] | actB[64][256] ]  (weights read through the scalar cache)
+    float *fe;            // this lane's feature column base
+    uint32_t fstride;     // distance between consecutive features of one lane
+    float *actB = nullptr;
+    constexpr int VW0 = VH * PadIn<NCOL>::value, VW1 = VH * PadIn<VH>::value;   // third layer: 3 * PadIn<VH> floats follow
+    float *lds_vw;        // view_mlp weights (padded rows), all three layers back to back
+    uint32_t *slab_hi = nullptr, *slab_lo = nullptr;      // MLP_F16X3: this wave's split feature images
+    if constexpr (MODE == MLP_F16X3) {
+        static_assert(PACK16_U4 * 4 == PACK_FLOATS, "both packings fill the same 32 KiB");
+        for (uint32_t i = threadIdx.x; i < (uint32_t)PACK16_U4; i += 256u)
+            reinterpret_cast<uint4 *>(lds)[i] = reinterpret_cast<const uint4 *>(a.mlp_pack)[i];
+        if constexpr (LT) { __syncthreads(); stage_w3p(lds + W3P_OFFSET, a.w[2]); }     // over the (unused) packed layer-3 operands
+        constexpr int WAVE_SLAB = 2 * 64 * SLAB_DW;       // dwords: hi image + lo image
+        float *wave_base = lds + PACK_FLOATS + (threadIdx.x >> 6) * WAVE_SLAB;
+        slab_hi = reinterpret_cast<uint32_t *>(wave_base);
+        slab_lo = slab_hi + 64 * SLAB_DW;
+        if constexpr (L0L) {                              // level 0 of the main grid, rows as stored (half2 = one dword per vertex)
+            uint32_t *l0w = reinterpret_cast<uint32_t *>(lds + PACK_FLOATS + 4 * WAVE_SLAB);
+            const uint32_t rows0 = a.g.res[0] * a.g.res[0] * a.g.res[0];
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(a.table) + a.g.off[0];
+            for (uint32_t i = threadIdx.x; i < rows0; i += 256u) l0w[i] = src[i];
+        }
+        fe = wave_base + (threadIdx.x & 63u);             // after the march the slab is reused as fp32 columns
+        fstride = 64u;
+        lds_vw = lds;                                     // overlays the packed weights once the march is over
+    } else if constexpr (MODE == MLP_F32) {
+        for (uint32_t i = threadIdx.x; i < (uint32_t)PACK_FLOATS / 4u; i += 256u)
+            reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(a.mlp_pack)[i];
+        fe = lds + PACK_FLOATS + (threadIdx.x >> 6) * (IN * 64) + (threadIdx.x & 63u);
+        fstride = 64u;
+        lds_vw = lds;
+    } else {
+        fe = lds + threadIdx.x;
+        actB = lds + 64 * 256 + threadIdx.x;
+        fstride = 256u;
+        lds_vw = lds + 2 * 64 * 256;
+    }
+    if constexpr (!MFMA) {
+        stage_weights<NCOL, VH>(lds_vw, a.vw[0]);
+        stage_weights<VH, VH>(lds_vw + VW0, a.vw[1]);
+        stage_weights<VH, 3>(lds_vw + VW0 + VW1, a.vw[2]);
+    }
+    __syncthreads();
+    clock_probe(0);
+    const uint32_t *l0tab = reinterpret_cast<const uint32_t *>(lds + PACK_FLOATS + 4 * 2 * 64 * SLAB_DW);   // L0L: level 0 of the main grid
+
+    FinalLds fl;
+    fl.lds = lds; fl.fe = fe; fl.fstride = fstride; fl.actB = actB; fl.lds_vw = lds_vw; fl.slab_hi = slab_hi; fl.slab_lo = slab_lo; fl.l0tab = l0tab;
+    // four consecutive wave tiles per workgroup tile (ray_of_lane)
+    final_stage_rays<TT, L, C, H1, H2, NOUT, VH, MODE, K, AUX, LT, L0L, EO, NP, PORD, CANON, false>(a, fl, tile_id(a.rc) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+}
+
+// ------------------------------------------------------------------------------------------
+// persistent launch of the plain linear-tail final stage (k_final_stage_pt)
+// ------------------------------------------------------------------------------------------
+// The ordinary launch hands the dispatcher one 4-wave workgroup per 16x16-pixel tile, with barriers inside: the stage's time steps at
+// multiples of 256 workgroups (tools/staircase.py), every workgroup stages 32 KiB of weights, and every wave waits at the end of its march
+// for the slowest of the four.  Here ONE 8-wave workgroup per CU stays resident, stages all weights once -- the packed image with w3p in its
+// place, the view weights in a region of their own, eight wave slabs: 32 + 80 + 8.4 KiB -- behind ONE barrier, and every wave then pulls
+// wave tiles (the ids wave_tile_of takes) from eight queues: tile_queue_range().  A wave starts at queue blockIdx.x & 7 (the XCD the
+// dispatcher is observed to place the workgroup on: speed only), and walks on to the next queue when one is exhausted; it ends after the
+// eighth.  A fetch is one lane's atomicAdd on the queue's counter (zeroed on the stream ahead of the launch).  After the barrier no wave
+// waits for another: no barrier, no flag, no spin; the loop is bounded by the fetches -- each one either takes a tile or retires a queue.
+// Every ray is computed by final_stage_rays, the code of the ordinary launch: bit-identical outputs.
+struct TileQueueArgs {
+    uint32_t *ctr;       // [8] fetch counters, zero at the start of the launch
+    uint32_t units;      // workgroup tiles (256 rays) of the ordinary launch of the same rays: blocks_for()
+};
+// the queues' counters back to zero, on the stream ahead of the launch that fetches from them (a kernel like every other node of the
+// call: captured and replayed with it)
+__global__ void k_tile_queue_reset(uint32_t *ctr) {
+    if (blockIdx.x == 0 && threadIdx.x < 8u) ctr[threadIdx.x] = 0u;
+}
+template <typename TT, int K>
+__global__ __launch_bounds__(512, 2) void k_final_stage_pt(FinalArgs a, TileQueueArgs q) {
+    SN_POISON_ALL();
+    constexpr int VIEW_FLOATS = 32 * PadIn<31>::value + 32 * PadIn<32>::value + 3 * PadIn<32>::value;
+    constexpr int WAVE_SLAB = 2 * 64 * SLAB_STRIDE;       // dwords: hi image + lo image
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *const lds_vw = lds + PACK_FLOATS + 8 * WAVE_SLAB;
+    static_assert(W3P_OFFSET % 4 == 0 && W3P_FLOATS % 4 == 0, "w3p is a whole number of 16-byte pieces of the weight image");
+    // the weight image but for the (unused) packed layer-3 operands w3p replaces: nothing below writes a word twice
+    for (uint32_t i = threadIdx.x; i < (uint32_t)PACK16_U4; i += 512u)
+        if (i < (uint32_t)(W3P_OFFSET / 4) || i >= (uint32_t)((W3P_OFFSET + W3P_FLOATS) / 4)) reinterpret_cast<uint4 *>(lds)[i] = reinterpret_cast<const uint4 *>(a.mlp_pack)[i];
+    stage_w3p(lds + W3P_OFFSET, a.w[2]);
+    stage_weights<31, 32>(lds_vw, a.vw[0]);
+    stage_weights<32, 32>(lds_vw + 32 * PadIn<31>::value, a.vw[1]);
+    stage_weights<32, 3>(lds_vw + 32 * PadIn<31>::value + 32 * PadIn<32>::value, a.vw[2]);
+    static_assert(VIEW_FLOATS == 32 * 32 + 32 * 32 + 3 * 32, "the view weights' region (LDS_F16X3_PT)");
+    __syncthreads();                                      // the only one
+    clock_probe(0);
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    float *wave_base = lds + PACK_FLOATS + wave * WAVE_SLAB;
+    FinalLds fl;
+    fl.lds = lds; fl.fe = wave_base + lane; fl.fstride = 64u; fl.actB = nullptr; fl.lds_vw = lds_vw;
+    fl.slab_hi = reinterpret_cast<uint32_t *>(wave_base); fl.slab_lo = fl.slab_hi + 64 * SLAB_STRIDE; fl.l0tab = nullptr;
+    // wave tiles that hold rays (ids beyond them are the padding of the last workgroup tile: nothing to compute, nothing to store)
+    uint32_t ntiles;
+    if (a.rc.W) {
+        const uint32_t tlw = a.rc.tlw, tlh = 6u - tlw;
+        ntiles = ((a.rc.W + (1u << tlw) - 1u) >> tlw) * ((a.rc.rows + (1u << tlh) - 1u) >> tlh);
+    } else ntiles = (a.rc.N + 63u) >> 6;
+    const uint32_t home = blockIdx.x & 7u;
+    for (uint32_t k = 0; k < 8u;) {                       // queues home, home + 1, ... (mod 8)
+        const uint32_t x = (home + k) & 7u;
+        uint32_t begin, end;
+        tile_queue_range(x, q.units, a.rc.xcd_swizzle, begin, end);
+        if (begin >= end) { ++k; continue; }
+        uint32_t t = 0;
+        if (lane == 0u) t = atomicAdd(&q.ctr[x], 1u);
+        t = __builtin_amdgcn_readfirstlane(t);
+        if (t >= end - begin) { ++k; continue; }          // exhausted: on to the next queue
+        const uint32_t g = begin + t;
+        if (g < ntiles) {
+            // The arguments are read again for every tile, through a pointer the optimiser cannot see through: hoisted out of this loop,
+            // the scalar loads of the whole march stay live across it and their spills cost the march vector registers it does not have.
+            // (FinalArgs is the kernel's first argument: offset 0 of the kernarg segment.)
+            typedef __attribute__((address_space(4))) const FinalArgs cst_final_args;
+            cst_final_args *ap = (cst_final_args *)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ap));
+            final_stage_rays<TT, 16, 2, 64, 64, 16, 32, MLP_F16X3, K, false, true, false, false, 3, false, false, true>(*(const FinalArgs *)ap, fl, g);
+        }
+    }
+    clock_probe(1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3639,6 +3765,7 @@ static bool final_lv_fits(const GridLevels &g, int K, uint32_t row_bytes) {
 constexpr int VIEW_W = 32 * 32 + 32 * 32 + 3 * 32;     // padded view_mlp rows
 static_assert(VIEW_W <= PACK_FLOATS, "view weights overlay the packed MLP weights");
 constexpr size_t LDS_F16X3 = (size_t)(PACK_FLOATS + 4 * 2 * 64 * SLAB_STRIDE) * sizeof(float);      // 72 KiB: packed weights + two sample slabs per wave
+constexpr size_t LDS_F16X3_PT = (size_t)(PACK_FLOATS + 8 * 2 * 64 * SLAB_STRIDE + VIEW_W) * sizeof(float);   // 120.4 KiB: k_final_stage_pt, one workgroup of 8 waves per CU
 constexpr size_t LDS_F16X3_L0 = (size_t)(PACK_FLOATS + 4 * 2 * 64 * 16 + L0_MAX_ROWS) * sizeof(float);
 constexpr size_t LDS_MFMA32 = (size_t)(PACK_FLOATS + 4 * 32 * 64) * sizeof(float);                  // 64 KiB
 constexpr size_t LDS_VALU = (size_t)(2 * 64 * 256 + VIEW_W) * sizeof(float);                        // 136 KiB + the view weights
@@ -3653,6 +3780,7 @@ static int experiment_of(const sn_render_cfg *cfg) {
 #endif
 }
 
+constexpr uint32_t SN_TILE_QUEUES = 8;
 struct FinalRoute {
     enum Family { NONE, ANY, SP, CMP, RS, LT, LT_L0, PER_SAMPLE, MFMA32, VALU };
     Family family = NONE;                  // NONE: skip_final
@@ -3668,6 +3796,8 @@ struct FinalRoute {
     int dense = 0;
     uint32_t gathers = 0;
     uint32_t lpr_log2 = 0, spl_log2 = 0;   // SP: lanes per ray, samples per lane
+    bool pt = false;                       // LT, plain: the persistent launch (k_final_stage_pt); grid stays the count of 256-ray tile units,
+    uint32_t pt_grid = 0;                  // the real grid is pt_grid workgroups of 512 threads
 };
 struct PropRoute {
     int K = -1;                            // dense prefix the instantiation is built for (3, 2, or -1: run time)
@@ -3688,7 +3818,11 @@ struct WorkspacePlan {
     size_t pair_main = 0, pair_prop[SN_MAX_STAGES] = {};   // floats of the packed pair rows: main grid (sized for its densified layout), proposal grids
     size_t pair_floats = 0, slot_floats = 0;         // all pair rows; stage scratch of one band slot
     size_t head_floats() const { return (size_t)PACK_FLOATS + pair_floats; }
-    size_t bytes() const { return ((size_t)bands.slots * slot_floats + head_floats()) * sizeof(float); }
+    // the tile-queue counters of the persistent last stage: 8 x uint32 per band slot, behind everything else (launches of one slot are
+    // ordered on its stream, and every launch zeroes its counters on that stream first)
+    size_t ctr_words() const { return (size_t)bands.slots * SN_TILE_QUEUES; }
+    size_t ctr_offset_floats() const { return (size_t)bands.slots * slot_floats + head_floats(); }
+    size_t bytes() const { return (ctr_offset_floats() + ctr_words()) * sizeof(float); }
 };
 struct RenderRoute {
     GridLevels gl_prop[SN_MAX_STAGES], gl_main, gl_feat;
@@ -3703,6 +3837,7 @@ struct RenderRoute {
     FinalRoute fin;                        // the last stage but for what depends on a chunk's ray count (plan_chunk completes it)
     FeatRoute feat;
     uint32_t chunks = 0;
+    uint32_t cus = 0;                      // compute units of the device the call runs on (0: not known -- the automatic rule of the persistent launch stays off)
     ChunkRoute full, last;                 // every chunk but the last one; the last one (the only one of a call that fits one chunk)
 };
 
@@ -3833,6 +3968,21 @@ static ChunkRoute plan_chunk(const sn_render_cfg *cfg, const sn_render_io *io, c
     FinalRoute &f = c.fin;
     f.grid = c.nblk;
     const uint32_t T = cfg->num_steps[S - 1];
+    // The persistent launch (k_final_stage_pt; tuning.persistent_tiles 2 = always, 1 = never, 0 = automatic): the plain linear-tail instantiation
+    // with the full product form, the parity gather order and no exact early-out.  Automatic: only when the launch has
+    // more wave tiles than the device has resident wave slots (8 per CU) -- below that every wave tile gets a wave at once and there is
+    // nothing to balance -- and only when the CU count is known.
+    if (f.family == FinalRoute::LT && !f.aux && !f.eo && f.np == 3 && !f.clumped && !f.canon && cfg->tuning.persistent_tiles != 1) {
+        const uint32_t cus = r.cus ? r.cus : 256u;           // (forced without a known device: the part this library is built for)
+        const uint32_t wgs = cfg->tuning.persistent_wgs > 0 ? (uint32_t)cfg->tuning.persistent_wgs : cus;
+        // Two row bands on two streams (tuning.band_streams): two persistent launches serialise -- each wants every CU -- where two ordinary ones
+        // overlap their tails.  Measured (profiles/r11/): 800x800 [128,64,32], 5000 wave tiles per band, +0.6 % per frame; 1600x1600, 20 000 per
+        // band, -2.0 %.  Such a call takes the form from four times the slot count.
+        const uint64_t slots = (uint64_t)SN_TILE_QUEUES * r.cus * (r.ws.bands.slots == 2u ? 4u : 1u);
+        if (cfg->tuning.persistent_tiles == 2 || (r.cus != 0u && (uint64_t)c.nblk * 4u > slots)) {
+            f.pt = true; f.pt_grid = wgs; f.lds = LDS_F16X3_PT;
+        }
+    }
 #ifdef SN_EXPERIMENTS
     if (f.family == FinalRoute::RS) {
         f.grid = W ? ((W + 31u) >> 5) * ((n / W + 15u) >> 4) : div_up(n, (uint32_t)(RS_PROD * 64));
@@ -3865,7 +4015,10 @@ static void plan_chunks(const sn_render_cfg *cfg, const sn_render_io *io, Render
 }
 
 // Validates cfg / io (all but the workspace) and fills *r.  Calls no HIP API, touches no global.  io->N >= 1 and check_io_pointers() passed.
-static int plan_render(const sn_render_cfg *cfg, const sn_render_io *io, RenderRoute *r) {
+static int plan_render(const sn_render_cfg *cfg, const sn_render_io *io, uint32_t cus, RenderRoute *r) {
+    r->cus = cus;
+    SN_REQUIRE(cfg->tuning.persistent_tiles >= 0 && cfg->tuning.persistent_tiles <= 2, "render_rays: tuning.persistent_tiles %d outside 0..2", cfg->tuning.persistent_tiles);
+    SN_REQUIRE(cfg->tuning.persistent_wgs >= 0 && cfg->tuning.persistent_wgs <= 65535, "render_rays: tuning.persistent_wgs %d outside 0..65535", cfg->tuning.persistent_wgs);
     SN_REQUIRE(io->out_stride == 0u || io->out_stride >= 5u, "render_rays: out_stride %u must be 0 (dense outputs) or at least 5 floats (rgb | depth | weights_sum per row)", io->out_stride);
     SN_REQUIRE(io->head_stride == 0u || (io->f_image && io->head_stride >= 31u + 4u && !io->skip_final),
                "render_rays: head_stride %u needs f_image and room for f_image | rgb | depth (>= 35 floats per row)", io->head_stride);
@@ -3987,6 +4140,7 @@ static void note_final(const FinalRoute &f, sn_launch_info *info) {
     snprintf(info->final_kernel, sizeof(info->final_kernel), "%s", f.name);
     info->workgroups = f.grid; info->lds_bytes = (uint32_t)f.lds; info->dense_levels = (uint32_t)(f.dense < 0 ? 0 : f.dense);
     info->gathers_per_wave_sample = f.gathers; info->launches += 1u;
+    info->persistent_tiles = f.pt ? 1u : 0u; info->grid_workgroups = f.pt ? f.pt_grid : f.grid;
 }
 
 // ---- launching what a route says ----------------------------------------------------------------------------------------------------
@@ -4064,8 +4218,19 @@ template <typename TT> static FinalKern final_kernel_of(const FinalRoute &f) {
     }
 }
 
-static int launch_final(const FinalRoute &f, hipStream_t st, const FinalArgs &fa, const AnyShape &any) {
+static int launch_final(const FinalRoute &f, hipStream_t st, const FinalArgs &fa, const AnyShape &any, uint32_t *queue_ctr) {
     const dim3 grid(f.grid), block(f.block);
+    if (f.pt) {
+        // the queues' counters start from zero on every launch, whatever the previous one left: ordered on the launch's stream, capturable
+        SN_REQUIRE(queue_ctr != nullptr, "render_rays: the persistent last stage has no counters");
+        static_assert(SN_TILE_QUEUES == 8, "k_tile_queue_reset clears eight counters");
+        const int rcz = launch(k_tile_queue_reset, dim3(1), dim3(64), 0, st, queue_ctr);
+        if (rcz) return rcz;
+        const TileQueueArgs q{queue_ctr, f.grid};
+        const dim3 pgrid(f.pt_grid), pblock(512);
+        if (f.K == 7) return f.f16 ? launch(k_final_stage_pt<__half, 7>, pgrid, pblock, f.lds, st, fa, q) : launch(k_final_stage_pt<float, 7>, pgrid, pblock, f.lds, st, fa, q);
+        return f.f16 ? launch(k_final_stage_pt<__half, 5>, pgrid, pblock, f.lds, st, fa, q) : launch(k_final_stage_pt<float, 5>, pgrid, pblock, f.lds, st, fa, q);
+    }
     switch (f.family) {
         case FinalRoute::ANY:
             return f.f16 ? launch(k_final_stage_any<__half>, grid, block, f.lds, st, fa, any) : launch(k_final_stage_any<float>, grid, block, f.lds, st, fa, any);
@@ -4098,6 +4263,21 @@ static FeatKern feat_kernel(const FeatRoute &ft, bool patch) {
         default: return ft.f16 ? feat_kernel_of<__half, 2>(ft.lg, patch) : feat_kernel_of<float, 2>(ft.lg, patch);
     }
 }
+// compute units of the current device, asked once per device and thread-safe; 0 where there is no device (the planner then leaves the
+// automatic rule of the persistent launch off, and everything that needs a device fails where it always did)
+static uint32_t device_compute_units() {
+    static std::mutex mu;
+    static std::map<int, uint32_t> known;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0u; }
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = known.find(dev);
+    if (it != known.end()) return it->second;
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 0) { (void)hipGetLastError(); n = 0; }
+    known[dev] = (uint32_t)n;
+    return (uint32_t)n;
+}
 }  // namespace sn
 
 extern "C" {
@@ -4107,18 +4287,31 @@ size_t sn_rm_render_workspace_bytes(const sn_render_cfg *cfg, uint32_t N, uint32
     return plan_workspace(cfg, N, tile_w).bytes();
 }
 
-int sn_rm_render_route_info(const sn_render_cfg *cfg, const sn_render_io *io, sn_launch_info *out) {
+int sn_rm_render_route_info_cus(const sn_render_cfg *cfg, const sn_render_io *io, uint32_t compute_units, sn_launch_info *out) {
     SN_REQUIRE(cfg && io && out, "render_route_info: cfg/io/out is NULL");
     *out = sn_launch_info{};
     if (io->N == 0) return SN_OK;
     int rc = check_io_pointers(cfg, io);
     if (rc) return rc;
     RenderRoute route;
-    rc = plan_render(cfg, io, &route);
+    rc = plan_render(cfg, io, compute_units, &route);
     if (rc) return rc;
     if (io->skip_final) return SN_OK;
     note_final(route.last.fin, out);
     out->launches = route.chunks;
+    return SN_OK;
+}
+int sn_rm_render_route_info(const sn_render_cfg *cfg, const sn_render_io *io, sn_launch_info *out) { return sn_rm_render_route_info_cus(cfg, io, 0u, out); }
+
+int sn_rm_tile_queue_info(uint32_t units, int32_t order, int32_t wave_tile, uint32_t queue, sn_tile_queue_info *out) {
+    SN_REQUIRE(out, "tile_queue_info: out is NULL");
+    SN_REQUIRE(queue < SN_TILE_QUEUES, "tile_queue_info: queue %u outside 0..7", queue);
+    SN_REQUIRE(units <= 0x3fffffffu, "tile_queue_info: %u workgroup tiles are more than a launch holds", units);
+    SN_REQUIRE(wave_tile >= 0 && wave_tile <= 5, "tile_queue_info: wave_tile %d outside 0..5", wave_tile);
+    const TileOrder to = tile_order_of(order, wave_tile ? (uint32_t)wave_tile : 3u);
+    *out = sn_tile_queue_info{};
+    tile_queue_range(queue, units, to.xcd, out->begin, out->end);
+    out->queues = SN_TILE_QUEUES; out->wave_tiles = 4u * units;
     return SN_OK;
 }
 
@@ -4156,7 +4349,7 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
     int rc = check_io_pointers(cfg, io);
     if (rc) return rc;
     RenderRoute route;
-    rc = plan_render(cfg, io, &route);
+    rc = plan_render(cfg, io, device_compute_units(), &route);
     if (rc) return rc;
     SN_REQUIRE(io->workspace != nullptr, "render_rays: workspace is NULL");
     SN_REQUIRE(table_aligned(io->workspace), "render_rays: workspace must be 16-byte aligned");
@@ -4315,7 +4508,7 @@ int sn_rm_render_rays(const sn_render_cfg *cfg, const sn_render_io *io, sn_strea
         {
             ProfScope ps_final(st, PK_FINAL);
             note_final(fr, &g_launch);
-            rc = launch_final(fr, st, fa, route.any);
+            rc = launch_final(fr, st, fa, route.any, reinterpret_cast<uint32_t *>(pack + route.ws.ctr_offset_floats()) + (size_t)slot * SN_TILE_QUEUES);
             if (rc) return rc;
             SN_LAUNCH_CHECK(fr.family == FinalRoute::ANY ? "k_final_stage_any" : "k_final_stage");
         }

@@ -53,4 +53,4 @@ from .mesh import mesh_simplify, mesh_simplify_counts, mesh_simplify_emit  # noq
 from .mesh import mesh_smooth, mesh_vertex_normals, mesh_smooth_build, mesh_smooth_steps, mesh_smooth_emit, smooth_quantisation  # noqa: F401
 from .mesh import mesh_rasterize, mesh_rasterize_clip, mesh_raster_project, mesh_raster_draw, mesh_raster_resolve, RASTER_SMALL_MAX_PIXELS, RASTER_MAX_SIDE  # noqa: F401
 from .mesh import vertex_probe_points, vertex_probe_composite, PROBE_SAMPLES  # noqa: F401
-from .render import RenderPlan, Tuning, tuning, last_launch_info, route_info, tile_order_info, render_rays, FP16_SPLIT_LIMIT  # noqa: F401
+from .render import RenderPlan, Tuning, tuning, last_launch_info, route_info, tile_order_info, tile_queue_info, render_rays, FP16_SPLIT_LIMIT  # noqa: F401

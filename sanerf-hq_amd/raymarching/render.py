@@ -33,8 +33,12 @@ class Tuning:
         prop_sp_lanes      small linear-order batches: lanes sharing a ray in the proposal stages (0 automatic; 8 / 16 / 32; bit-neutral)
         feat_patch         feature stage: 1 = per-wave LDS patch of the dense levels (bit-neutral; measured 3-9 % slower, so 0 = off is the default)
         prop_pair          proposal stages: a lane evaluates two consecutive samples at once (bit-neutral): 0 automatic, 1 never, 2 always
-        experiment         _lib.EXP_*: measured-and-rejected variants, experiments builds only (SN_LIB=.../libsanerf_hip_exp.so)"""
-    FIELDS = ("mlp_mode", "per_sample_form", "densify", "linear_tile_order", "prop_sp_max_rays", "final_sp_max_rays", "feat_levels", "band_streams", "exact_early_out", "wave_tile", "prop_sp_lanes", "feat_patch", "prop_pair", "experiment")
+        experiment         _lib.EXP_*: measured-and-rejected variants, experiments builds only (SN_LIB=.../libsanerf_hip_exp.so)
+        persistent_tiles   last stage, plain linear-tail launch: one resident 8-wave workgroup per CU whose waves pull 64-ray wave tiles from eight
+                           queues (bit-neutral): 0 automatic (more wave tiles than 8 x CUs), 1 never, 2 always; tile_queue_info() states the queues
+        persistent_wgs     workgroups of that launch: 0 one per CU, n exactly n"""
+    FIELDS = ("mlp_mode", "per_sample_form", "densify", "linear_tile_order", "prop_sp_max_rays", "final_sp_max_rays", "feat_levels", "band_streams", "exact_early_out", "wave_tile", "prop_sp_lanes", "feat_patch", "prop_pair", "experiment",
+              "persistent_tiles", "persistent_wgs")
 
     def __init__(self, **kw):
         for f in self.FIELDS:
@@ -61,8 +65,22 @@ def last_launch_info() -> dict:
     instructions per wave-sample): sn_rm_last_launch_info."""
     info = _lib.LaunchInfo()
     _lib.check(_lib.lib().sn_rm_last_launch_info(C.byref(info)), "last_launch_info")
+    return _launch_info_dict(info)
+
+
+def _launch_info_dict(info) -> dict:
+    """sn_launch_info as a dict.  workgroups counts 256-ray tile units whichever launch form ran; grid_workgroups is the real grid."""
     return dict(final_kernel=info.final_kernel.decode(), workgroups=int(info.workgroups), lds_bytes=int(info.lds_bytes),
-                dense_levels=int(info.dense_levels), gathers_per_wave_sample=int(info.gathers_per_wave_sample), launches=int(info.launches))
+                dense_levels=int(info.dense_levels), gathers_per_wave_sample=int(info.gathers_per_wave_sample), launches=int(info.launches),
+                persistent_tiles=int(info.persistent_tiles), grid_workgroups=int(info.grid_workgroups))
+
+
+def tile_queue_info(units: int, queue: int, order: int = 0, wave_tile: int = 0) -> dict:
+    """Queue `queue` (0..7) of the persistent last stage for a launch of `units` 256-ray tile units under Tuning.linear_tile_order = order
+    (sn_rm_tile_queue_info: host arithmetic only): queues, wave_tiles = 4 * units, and the wave-tile ids [begin, end) the queue holds."""
+    info = _lib.TileQueueInfo()
+    _lib.check(_lib.lib().sn_rm_tile_queue_info(int(units), int(order), int(wave_tile), int(queue), C.byref(info)), "tile_queue_info")
+    return dict(queues=int(info.queues), wave_tiles=int(info.wave_tiles), begin=int(info.begin), end=int(info.end))
 
 
 def tile_order_info(W: int, rows: int, workgroup: int, wave_tile: int = 0, order: int = 0) -> dict:
@@ -313,20 +331,23 @@ def _fill_io(plan: RenderPlan, io, N: int, tile_w: int, want, u_tables, bins0_ta
 
 def route_info(plan: RenderPlan, N: int, tile_w: int = 0, want: Sequence[str] = (), u_tables: Optional[Dict[int, torch.Tensor]] = None,
                bins0_table: Optional[torch.Tensor] = None, skip_final: bool = False, tuning: Optional["Tuning"] = None,
-               packed: Optional[torch.Tensor] = None, head_input: bool = False) -> dict:
+               packed: Optional[torch.Tensor] = None, head_input: bool = False, compute_units: Optional[int] = None) -> dict:
     """What last_launch_info() would report after render_rays(plan, <N rays>, ...) with the same arguments, without rendering
     (sn_rm_render_route_info: the same validation and route planning on the host; no render kernel is launched and no output is
     allocated).  Like render_rays it writes the effective tuning into plan.cfg.tuning and, unless skip_final, consults the plan's fp16
-    range guard (plan.check_range(): device reductions and one sync when a parameter version moved) -- the guard decides the route."""
+    range guard (plan.check_range(): device reductions and one sync when a parameter version moved) -- the guard decides the route.
+    compute_units: CUs of the device to plan for (None: the device of the plan's tables; 0: not known)."""
     io = _lib.RenderIO()
     stand_in = 64                                                  # an aligned non-NULL address: the dry run dereferences nothing
     io.rays_o = io.rays_d = stand_in
     _fill_io(plan, io, int(N), tile_w, want, u_tables, bins0_table, skip_final, packed, head_input, tuning,
              lambda name, shape, dtype=torch.float32: stand_in, lambda t: (t, stand_in))
     info = _lib.LaunchInfo()
-    _lib.check(_lib.lib().sn_rm_render_route_info(C.byref(plan.cfg), C.byref(io), C.byref(info)), "route_info")
-    return dict(final_kernel=info.final_kernel.decode(), workgroups=int(info.workgroups), lds_bytes=int(info.lds_bytes),
-                dense_levels=int(info.dense_levels), gathers_per_wave_sample=int(info.gathers_per_wave_sample), launches=int(info.launches))
+    if compute_units is None:      # the device the plan's tables live on: what sn_rm_render_rays asks its device (the automatic rule of persistent_tiles)
+        t0 = plan.keep[0] if plan.keep else None
+        compute_units = torch.cuda.get_device_properties(t0.device).multi_processor_count if t0 is not None and t0.is_cuda else 0
+    _lib.check(_lib.lib().sn_rm_render_route_info_cus(C.byref(plan.cfg), C.byref(io), int(compute_units), C.byref(info)), "route_info")
+    return _launch_info_dict(info)
 
 
 def render_rays(plan: RenderPlan, rays_o, rays_d, cam_near_far=None, bg_color: float = 1.0, tile_w: int = 0,
