@@ -21,8 +21,23 @@
 //                  registers -> per-ray view MLP -> sigmoid -> image/depth/weights_sum.
 //   k_final_stage_pt  the same code per ray (final_stage_rays) under a persistent launch: one 8-wave
 //                  workgroup per CU, every wave pulls 8x8 tiles from per-XCD queues.
-#include "sn_common.h"
-#include "sh_basis.inc"
+//
+// One translation unit.  The code up to and including the matrix phase lives in headers, included in this order (definitions and
+// instantiations keep it, so a pure move leaves the device code unchanged: tools/render_isa_sha.sh, profiles/render_split_isa.txt):
+//   render_knobs.h   every build-time SN_* constant of this file with its measured history
+//   render_rays.h    RayCommon, tile orders (xcd_tile_id, wave_tile_of, tile_queue_range), ray_of_lane, setup_ray, bins -> sample position
+//   render_gather.h  Corner, two-phase level groups, XSWAP and PARITY helpers, PairTab, encode_levels*, GroupRegs, FinalLv, FinalSpans
+//   render_dense.h   PadIn, stage_weights*, dense_ldsw*: the VALU layers of the proposal and colour heads
+//   render_prop.h    PropArgs, ray_misses, k_prop_stage, k_prop_stage_sp
+//   render_mfma.h    pack layouts, k_pack_grid_mlp*, the matrix phase up to grid_mlp_mfma16_l12_spread, the VALU fallback
+// This file: the last stage (FinalArgs, clock probe, final_stage_rays and its launch forms, _any / _cmp / _sp), the feature stage, the route
+// planner, the launch glue and the C entry points.
+#include "render_knobs.h"
+#include "render_rays.h"
+#include "render_gather.h"
+#include "render_dense.h"
+#include "render_prop.h"
+#include "render_mfma.h"
 
 #include <float.h>
 #include <stdlib.h>
@@ -34,1263 +49,6 @@
 #include <vector>
 
 namespace sn {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-struct RayCommon {
-    const float *rays_o, *rays_d, *cnf;
-    uint32_t N;        // rays in this launch
-    uint32_t W;        // image width (tile mode) or 0
-    uint32_t rows;     // image rows in this launch (tile mode)
-    uint32_t Npad;     // scratch row stride = gridDim.x * 256
-    float aabb[6];
-    float min_near, bound;
-    int contract, last_opaque;
-    float bg;
-    int xcd_swizzle;
-    uint32_t st_w, st_h;   // wave tiles walked in super-tiles of st_w units x st_h row pairs (wave_tile_of); st_w = 0: in whole row pairs
-    uint32_t tlw;      // log2 of the wave tile's width in pixels (3: 8x8; sn_render_tuning.wave_tile)
-    float inv_den;     // 1 / (2*bound) when that is a power of two (exact scaling), else 0
-};
-
-// Workgroup id -> tile id.  The dispatcher places workgroup b on XCD b % 8 (observed, not contractual: used
-// for speed only).  Remapping so that each XCD owns a contiguous range of tile ids keeps neighbouring image
-// tiles -- which share fine-level table lines -- behind the same private L2.  Bijective for any grid size.
-__host__ __device__ __forceinline__ uint32_t xcd_tile_id(uint32_t b, uint32_t nwg) {
-    const uint32_t xcd = b & 7u, q = nwg >> 3, r = nwg & 7u;
-    return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + (b >> 3);
-}
-// The eight tile queues of the persistent launch of the last stage (k_final_stage_pt).  Queue x holds the WAVE tiles of the workgroup-tile
-// range xcd_tile_id() gives XCD x in a launch of `units` workgroup tiles -- the same contiguous ranges x 4, in the same order: ids
-// [begin, end).  xcd = 0 (tile orders without the remap): one queue, number 0, over all ids.  The ranges partition [0, 4 * units).
-__host__ __device__ __forceinline__ void tile_queue_range(uint32_t x, uint32_t units, int xcd, uint32_t &begin, uint32_t &end) {
-    if (!xcd) { begin = 0u; end = x == 0u ? 4u * units : 0u; return; }
-    const uint32_t q = units >> 3, r = units & 7u;
-    const uint32_t first = x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q;      // = xcd_tile_id(x, units)
-    begin = 4u * first;
-    end = 4u * (first + q + (x < r ? 1u : 0u));
-}
-__device__ __forceinline__ uint32_t tile_id_x(const RayCommon &rc, uint32_t b, uint32_t nwg) { return rc.xcd_swizzle ? xcd_tile_id(b, nwg) : b; }
-__device__ __forceinline__ uint32_t tile_id(const RayCommon &rc) { return tile_id_x(rc, blockIdx.x, gridDim.x); }
-
-// Wave-tile id -> wave tile (wx, wy) of an image of tx8 x ty8 wave tiles.  Wave-tile rows go in pairs; a "unit" is one column of a pair
-// (two wave tiles, one above the other), so that the four consecutive ids of a workgroup are a 2x2 block wherever the image has one.  An
-// odd last wave-tile row comes after all pairs, left to right.
-//   sw = 0: the units of a row pair left to right, pair after pair: 64 consecutive workgroups are a strip the width of the image.
-//   sw > 0: the units in super-tiles sw units wide and up to sh row pairs high (the row pairs are dealt evenly to ceil(P / sh)
-//           super-tile rows).  Super-tile rows alternate direction (odd ones are walked mirrored), a super-tile is row-major inside, edge
-//           super-tiles are narrower: a contiguous range of ids -- what one XCD has in flight, xcd_tile_id -- is a connected region a few
-//           super-tiles long.  Closed form, evaluated once per lane before the march.  Bijective on the units for every shape.
-__host__ __device__ __forceinline__ void wave_tile_of(uint32_t g, uint32_t tx8, uint32_t ty8, uint32_t sw, uint32_t sh, uint32_t &wx, uint32_t &wy) {
-    const uint32_t P = ty8 >> 1, pair = 2u * tx8, paired = P * pair;
-    if (g >= paired) { wx = g - paired; wy = ty8 & ~1u; return; }          // the odd last row
-    if (sw == 0u) { const uint32_t p = g / pair, i = g - p * pair; wx = i >> 1; wy = 2u * p + (i & 1u); return; }
-    const uint32_t u = g >> 1;
-    const uint32_t nsy = (P + sh - 1u) / sh, base = P / nsy, extra = P - base * nsy;    // the first `extra` super-tile rows are base + 1 high
-    const uint32_t big = (base + 1u) * tx8;                                                         // units of such a row
-    uint32_t sy, r0, h, y0;
-    if (u < extra * big) { sy = u / big; r0 = u - sy * big; h = base + 1u; y0 = sy * h; }
-    else { const uint32_t v = u - extra * big, row = base * tx8, s = v / row; r0 = v - s * row; sy = extra + s; h = base; y0 = extra * (base + 1u) + s * base; }
-    const uint32_t full = sw * h, sx = r0 / full, r1 = r0 - sx * full;
-    const uint32_t left = tx8 - sx * sw, w = left < sw ? left : sw;
-    const uint32_t ry = r1 / w, rx = r1 - ry * w;
-    const uint32_t x = sx * sw + rx;
-    wx = (sy & 1u) ? tx8 - 1u - x : x;
-    wy = 2u * (y0 + ry) + (g & 1u);
-}
-
-// lane -> ray.  Tile mode: wave = 8x8 pixels; a workgroup takes four CONSECUTIVE wave tiles of this order: wave-tile rows go in
-// pairs, column-major inside a pair ((0,0) (0,1) (1,0) (1,1) (2,0) ...; wave_tile_of, which also states the super-tile order), so that a workgroup is a 16x16-pixel block wherever the
-// image has one, and an odd last wave-tile row is walked left to right (32x8 pixels per workgroup).  The launch has
-// ceil(wave tiles / 4) workgroups whatever the shape -- a 200-row band of a 1600-wide image (BASELINE configs[3] on 8 GPUs) is 1250
-// workgroups, not the 1300 of whole 16x16 tiles: tools/staircase.py shows the stages' time stepping at multiples of 256 workgroups
-// (one per CU), 1300 is just past the step at 1280 (profiles/r04/staircase_1600.txt).  Host twin: blocks_for().
-// (g: the wave tile id, wave-uniform -- four consecutive ones per workgroup of the ordinary launch, one per fetch of the persistent one;
-//  linear order: rays g * 64 .. g * 64 + 63)
-__device__ __forceinline__ bool ray_of_wave_tile(const RayCommon &rc, uint32_t g, uint32_t lane, uint32_t &n) {
-    if (rc.W) {
-        // wave tile = 2^tlw x 2^(6 - tlw) pixels (8x8 unless sn_render_tuning.wave_tile says otherwise; tx8 / ty8 keep their round-1 names)
-        const uint32_t tlw = rc.tlw, tlh = 6u - tlw, tw = 1u << tlw, th = 1u << tlh;
-        const uint32_t tx8 = (rc.W + tw - 1u) >> tlw, ty8 = (rc.rows + th - 1u) >> tlh;
-        uint32_t wx, wy;
-        wave_tile_of(g, tx8, ty8, rc.st_w, rc.st_h, wx, wy);   // (wx >= tx8: padding of the last workgroup)
-        const uint32_t py = (wy << tlh) + (lane >> tlw);
-        const uint32_t px = (wx << tlw) + (lane & (tw - 1u));
-        const bool ok = wx < tx8 && px < rc.W && py < rc.rows;
-        n = ok ? py * rc.W + px : 0u;
-        return ok;
-    }
-    n = g * 64u + lane;
-    const bool ok = n < rc.N;
-    if (!ok) n = 0;
-    return ok;
-}
-__device__ __forceinline__ bool ray_of_lane(const RayCommon &rc, uint32_t wg, uint32_t &n) {
-    const uint32_t tid = threadIdx.x;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the wave tile is the same for all lanes: scalar arithmetic)
-    return ray_of_wave_tile(rc, wg * 4u + wave, tid & 63u, n);
-}
-
-struct RaySetup {
-    float o[3], d[3];
-    float s_near, s_far;
-};
-
-__device__ __forceinline__ void setup_ray(const RayCommon &rc, uint32_t n, RaySetup &rs) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { rs.o[k] = rc.rays_o[(size_t)n * 3 + k]; rs.d[k] = rc.rays_d[(size_t)n * 3 + k]; }
-    float near, far;
-    near_far_one(rs.o, rs.d, rc.aabb, rc.min_near, near, far);
-    if (rc.cnf) {  // renderer.py:233-235
-        const float cn = rc.cnf[(size_t)n * 2], cf = rc.cnf[(size_t)n * 2 + 1];
-        near = cn > near ? cn : near;
-        far = cf < far ? cf : far;
-    }
-    rs.s_near = spacing_fn(near);
-    rs.s_far = spacing_fn(far);
-}
-
-// renderer.py:277 — normalised bin -> distance along the ray
-__device__ __forceinline__ float real_bin(const RaySetup &rs, float b) {
-    const float a = rs.s_near * (1.0f - b);
-    const float c = rs.s_far * b;
-    return spacing_inv(a + c);
-}
-
-// renderer.py:279-285 + grid.py:156: sample position -> table coordinate in [0,1]
-__device__ __forceinline__ void sample_x01(const RayCommon &rc, const RaySetup &rs, float tmid, float (&p)[3], float (&x01)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { const float m = rs.d[k] * tmid; p[k] = rs.o[k] + m; }
-    if (rc.contract) contract3(p[0], p[1], p[2]);
-    const float den = 2.0f * rc.bound;
-    if (rc.inv_den != 0.0f) {   // 2*bound is a power of two (bound = 2 when contracted): x / den == x * (1/den) exactly
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x01[k] = (p[k] + rc.bound) * rc.inv_den;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x01[k] = (p[k] + rc.bound) / den;
-    }
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// ---- two-phase level groups -----------------------------------------------------------------
-// hipcc schedules "8 loads, wait, 16 fmas" level by level if the source is written level by level,
-// which leaves 8 gathers in flight per lane and exposes one full memory latency per level.  The
-// march therefore handles GROUP levels at a time in two explicit phases separated by scheduling
-// barriers: (1) locate + row indices + ISSUE all GROUP*8 gathers (32-bit byte offsets from a
-// wave-uniform base -> saddr-form global loads, one address VGPR each), (2) blend.
-template <typename T, int C>
-struct Corner { float v[C]; };
-
-// fp16 tables, C = 2: a fetched row stays PACKED (its half2 bit pattern in v[0]) and the blend multiplies it with
-// v_fma_mix_f32, which widens an f16 operand on the fly -- the same fp32 fma on the same exactly-converted value as
-// v_cvt_f32_f16 + v_fma_f32, so results are bit-identical, but the 16 conversions per level (256 of ~1500 vector
-// instructions per sample of the final stage, 80 of ~700 in a proposal stage) disappear.
-template <typename T, int C>
-__device__ __forceinline__ void corner_set_half2(Corner<T, C> &c, uint32_t bits) {
-    static_assert(C == 2 && sizeof(T) == 2, "packed rows: fp16 tables with two features per level");
-    c.v[0] = __uint_as_float(bits); c.v[1] = 0.0f;
-}
-__device__ __forceinline__ float fma_mix_lo(float w, uint32_t packed, float acc) {      // fmaf(w, (float)packed.lo, acc)
-    float d;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[0,1,0]" : "=v"(d) : "v"(w), "v"(packed), "v"(acc));
-    return d;
-}
-__device__ __forceinline__ float fma_mix_hi(float w, uint32_t packed, float acc) {      // fmaf(w, (float)packed.hi, acc)
-    float d;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(d) : "v"(w), "v"(packed), "v"(acc));
-    return d;
-}
-
-// XSWAP (hashed fine levels of the final stage): the two x-corners of a cell sit in the same 128-byte line 15 times
-// out of 16 (index = x ^ y*P1 ^ z*P2: x and x+1 differ in the low bits only), but as two instructions each line is
-// looked up twice and a fine-level instruction already touches ~40 distinct lines (its cost).
-// The half-waves therefore trade addresses with one v_permlane32_swap per corner pair: the first load serves BOTH
-// x-corners of lanes 0-31, the second those of lanes 32-63 -- about half the distinct lines per instruction, same
-// instruction count -- and blend_level_x swaps the fetched values back.
-#ifndef SN_PROP_GROUP
-#define SN_PROP_GROUP 2      // proposal stage: levels gathered in groups of 2 + 2 + 1.  History: all 5 at once spilled at 128 VGPRs; 3 + 2 fitted
-                             // (4.70 -> 4.55 ms); 2 + 2 + 1 fits 96 VGPRs = 5 waves per SIMD instead of 4 (SN_PROP_WAVES): [128,64,32] 4.53 -> 4.44 ms fp32
-#endif
-#ifndef SN_PROP_GROUP_H
-#define SN_PROP_GROUP_H 2    // the same for fp16 tables (78 VGPRs): 4.10 -> 3.98 ms
-#endif
-template <typename T, int KIND, int l>
-constexpr bool xswap_level() {
-    return KIND == 1 && l >= 0;
-}
-#ifndef SN_XSWAP_MODE
-#define SN_XSWAP_MODE 0      // which lanes trade the two x-corners of a cell (A/B, tools/xswap_ab.sh, profiles/r06/xswap_ab.txt; all bit-identical): 0 = the wave's
-                             // halves (v_permlane32_swap; 6.21-6.27 ms); 1 = neighbours (lanes 2i, 2i+1: both corners of a ray in ONE quad of the address unit, 13 %
-                             // fewer quad-line pairs but 40 % more distinct lines per instruction and a select per swap: 6.43-6.45 ms); 2 = 16-lane rows
-                             // (v_permlane16_swap: 6.19-6.20 ms, inside the noise of the default)
-#endif
-// PARITY (round 10, hashed levels of the FinalLv path): instruction (dy, dz) of a level used to fetch the corner (cell.y + dy, cell.z + dz),
-// so two rays in y-adjacent cells asked for the hash row they share in two different instructions.  Instead every lane puts into
-// instruction (a, b) the corner whose ABSOLUTE y has parity a and whose absolute z has parity b: lanes with an odd cell coordinate
-// exchange their two slots along that axis.  Requests for one row then meet in one instruction, where the address unit merges them
-// (n consecutive cells along an axis: n + 1 distinct rows instead of 2n).  The exchange is a lane-wise permutation of a lane's eight
-// requests, undone on the landed values before the blend (blend_level_par): every corner value reaches the same slot of the same
-// corner-ascending fma chain, so results are bit-identical.  The parity bits travel from issue to blend in the sign bits of the level's
-// pos[1] / pos[2] (fract never sets a sign), which costs no register.
-#ifndef SN_PARITY_FIRST
-#define SN_PARITY_FIRST 12   // first hashed level issued by parity: 9 / 11 / 12 / 13 / 14 measured (profiles/r10/README.md); levels 7-11 sit at the 8-line floor of
-                             // the address unit already (tools/gather_parity_table.py) and the exchange costs ~18 vector instructions per level
-#endif
-#ifndef SN_PARITY_AXES
-#define SN_PARITY_AXES 2     // 2 = y and z, 1 = z only
-#endif
-template <typename T, int AXIS, int l>
-constexpr bool parity_level() {
-    return l >= SN_PARITY_FIRST && (AXIS == 2 || (AXIS == 1 && SN_PARITY_AXES == 2));
-}
-__device__ __forceinline__ float parity_tag(float frac, uint32_t cell) {     // frac >= 0 with the cell's parity as its sign
-    return __uint_as_float(__float_as_uint(frac) | (cell << 31));
-}
-__device__ __forceinline__ bool parity_of(float tagged) { return (__float_as_uint(tagged) >> 31) != 0u; }
-#ifndef SN_PARITY_UNDO
-#define SN_PARITY_UNDO 1     // how odd lanes trade two registers (address terms at issue, landed values at the blend): 0 = two selects per pair (26 vector instructions per
-                             // level: slower than the canonical order, profiles/r10/undo_by_selects_ab.json), 1 = one v_swap_b32 per pair with the odd lanes as the exec mask (18)
-#endif
-// lanes with `odd` set trade a and b
-__device__ __forceinline__ void swap_if(bool odd, uint32_t &a, uint32_t &b) {
-#if SN_PARITY_UNDO == 1
-    const uint64_t m = __builtin_amdgcn_ballot_w64(odd);
-    uint64_t sv;
-    asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_swap_b32 %[a], %[b]\n\ts_mov_b64 exec, %[sv]" : [a] "+v"(a), [b] "+v"(b), [sv] "=&s"(sv) : [m] "s"(m) : "scc");
-#else
-    const uint32_t t = a;
-    a = odd ? b : a; b = odd ? t : b;
-#endif
-}
-__device__ __forceinline__ void swap_if4(bool odd, uint32_t &a0, uint32_t &b0, uint32_t &a1, uint32_t &b1, uint32_t &a2, uint32_t &b2, uint32_t &a3, uint32_t &b3) {
-#if SN_PARITY_UNDO == 1
-    const uint64_t m = __builtin_amdgcn_ballot_w64(odd);
-    uint64_t sv;
-    asm("s_and_saveexec_b64 %[sv], %[m]\n\t"
-        "v_swap_b32 %[a0], %[b0]\n\tv_swap_b32 %[a1], %[b1]\n\tv_swap_b32 %[a2], %[b2]\n\tv_swap_b32 %[a3], %[b3]\n\t"
-        "s_mov_b64 exec, %[sv]"
-        : [a0] "+v"(a0), [b0] "+v"(b0), [a1] "+v"(a1), [b1] "+v"(b1), [a2] "+v"(a2), [b2] "+v"(b2), [a3] "+v"(a3), [b3] "+v"(b3), [sv] "=&s"(sv)
-        : [m] "s"(m)
-        : "scc");
-#else
-    uint32_t t;
-    t = a0; a0 = odd ? b0 : a0; b0 = odd ? t : b0;
-    t = a1; a1 = odd ? b1 : a1; b1 = odd ? t : b1;
-    t = a2; a2 = odd ? b2 : a2; b2 = odd ? t : b2;
-    t = a3; a3 = odd ? b3 : a3; b3 = odd ? t : b3;
-#endif
-}
-
-__device__ __forceinline__ void half_wave_swap(uint32_t &a, uint32_t &b) {
-#if SN_XSWAP_MODE == 0
-    // a' = [a.lanes0-31 | b.lanes0-31], b' = [a.lanes32-63 | b.lanes32-63]
-    auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-#elif SN_XSWAP_MODE == 1
-    // lane 2i: a' = a, b' = a of lane 2i+1;  lane 2i+1: a' = b of lane 2i, b' = b  (its own inverse, like the half-wave swap)
-    const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
-    const uint32_t na = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a, 0xB1, 0xF, 0xF, true);
-    const bool odd = (threadIdx.x & 1u) != 0u;
-    a = odd ? nb : a; b = odd ? b : na;
-#else
-    auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-#endif
-}
-
-// Dense levels re-laid out for the final stage (k_pack_pairs, once per render call, a few MB): pair row i of a level
-// = (row i, row of the +1 neighbour in x, clamped at the border) -> the two x-corners of a cell come from ONE
-// naturally aligned 16-byte load and the border case needs no select (fp16: quad rows, the y-neighbours too).  The gather address
-// rate (one wave instruction per 17.5 cycles per CU) is what bounds the final stage: 4 loads
-// instead of 8 on the 5 dense levels = 108 instead of 128 gather instructions per sample.
-struct PairTab {
-    const void *base;            // device; NULL = not available
-    uint32_t off[8];             // first pair row of each dense level
-};
-
-template <typename T, int C, int KIND, bool PAIRA, bool XSWAP = false>
-__device__ __forceinline__ void issue_level(const T *__restrict__ table, const GridLevels &g, int l, const float (&x01)[3],
-                                            float (&pos)[3], Corner<T, C> (&cv)[8], const PairTab *pt = nullptr) {
-    const uint32_t res = g.res[l], size = g.size[l], mode = g.mode[l];
-    const T *tab = table + (size_t)g.off[l] * C;
-    uint32_t cell[3], offs[8];
-    locate_linear(x01, res, pos, cell);
-    if constexpr (PAIRA && KIND == 0 && C == 2 && sizeof(T) == 2) {
-        // fp16 rows are 4 bytes: a 16-byte load (which costs what an 8-byte one costs) carries the x- AND the
-        // y-neighbour: quad row i = rows (x,y), (x+1,y), (x,y+1), (x+1,y+1), clamped -> 2 loads per level
-        constexpr uint32_t QB = 16u;
-        const uint32_t sy = res * QB, sz = res * res * QB, top = res - 1u;
-        const uint32_t base_off = cell[0] * QB + __umul24(cell[1], sy);
-        const uint32_t Z0 = __umul24(cell[2], sz), Z1 = umin(Z0 + sz, top * sz);
-        const char *pbase = reinterpret_cast<const char *>(pt->base) + (size_t)pt->off[l] * QB;
-#pragma unroll
-        for (int zi = 0; zi < 2; ++zi) {
-            const uint4 t = *reinterpret_cast<const uint4 *>(pbase + base_off + (zi ? Z1 : Z0));
-            const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) corner_set_half2(cv[4 * zi + q], w[q]);   // q = x + 2 y -> corner index x + 2 y + 4 z
-        }
-        return;
-    }
-    if constexpr (PAIRA && KIND == 0 && C == 2) {
-        constexpr uint32_t PB = (uint32_t)(2 * C * sizeof(T));
-        const uint32_t sy = res * PB, sz = res * res * PB, top = res - 1u;
-        const uint32_t X0 = cell[0] * PB, Y0 = __umul24(cell[1], sy), Z0 = __umul24(cell[2], sz);
-        const uint32_t Y1 = umin(Y0 + sy, top * sy), Z1 = umin(Z0 + sz, top * sz);
-        const char *pbase = reinterpret_cast<const char *>(pt->base) + (size_t)pt->off[l] * PB;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t off = X0 + ((i & 1) ? Y1 : Y0) + ((i & 2) ? Z1 : Z0);
-            if constexpr (sizeof(T) == 4) {
-                const float4 t = *reinterpret_cast<const float4 *>(pbase + off);
-                cv[2 * i].v[0] = t.x; cv[2 * i].v[1] = t.y; cv[2 * i + 1].v[0] = t.z; cv[2 * i + 1].v[1] = t.w;
-            } else {
-                const uint2 t = *reinterpret_cast<const uint2 *>(pbase + off);
-                corner_set_half2(cv[2 * i], t.x); corner_set_half2(cv[2 * i + 1], t.y);
-            }
-        }
-        return;
-    }
-    corner_offsets<KIND, (uint32_t)(C * sizeof(T))>(cell, res, size, mode, offs);
-    if constexpr (XSWAP) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) half_wave_swap(offs[2 * p], offs[2 * p + 1]);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const T *row = reinterpret_cast<const T *>(reinterpret_cast<const char *>(tab) + offs[i]);
-        if constexpr (C == 2 && sizeof(T) == 4) {
-            const float2 t = *reinterpret_cast<const float2 *>(row);
-            cv[i].v[0] = t.x; cv[i].v[1] = t.y;
-        } else if constexpr (C == 2 && sizeof(T) == 2) {
-            if constexpr (XSWAP) {   // keep the packed row: blend_level_x swaps one register per corner, then unpacks
-                cv[i].v[0] = __uint_as_float(*reinterpret_cast<const uint32_t *>(row));
-                cv[i].v[1] = 0.0f;
-            } else {
-                corner_set_half2(cv[i], *reinterpret_cast<const uint32_t *>(row));
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; ++c) cv[i].v[c] = table_ld<T>(row + c);
-        }
-    }
-}
-
-// PKW: the 8 corner weights as 6 packed multiplies (x-pairs: (wx0, wx1) * wy, then * wz) instead of 12 scalar ones;
-// every weight is still (wx * wy) * wz, every channel still one corner-ascending fma chain.  Final stage only (the
-// proposal kernels have no registers to spare for the even-aligned pairs).
-template <typename T, int C, bool PKW = false>
-__device__ __forceinline__ void blend_level(const float (&pos)[3], const Corner<T, C> (&cv)[8], float (&acc)[C]) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) acc[c] = 0.0f;
-    if constexpr (C == 2 && sizeof(T) == 2) {   // packed fp16 rows (corner_set_half2): widening fma, same order
-        float w[8];
-        if constexpr (PKW) {                // the 8 corner weights as 6 packed multiplies: every weight still (wx * wy) * wz
-            typedef float f2 __attribute__((ext_vector_type(2)));
-            const f2 wx = {1.0f - pos[0], pos[0]};
-            const float wy0 = 1.0f - pos[1], wz0 = 1.0f - pos[2];
-            const f2 xy0 = wx * f2{wy0, wy0}, xy1 = wx * f2{pos[1], pos[1]};
-            const f2 w01 = xy0 * f2{wz0, wz0}, w23 = xy1 * f2{wz0, wz0}, w45 = xy0 * f2{pos[2], pos[2]}, w67 = xy1 * f2{pos[2], pos[2]};
-            w[0] = w01.x; w[1] = w01.y; w[2] = w23.x; w[3] = w23.y; w[4] = w45.x; w[5] = w45.y; w[6] = w67.x; w[7] = w67.y;
-        } else {
-#pragma unroll
-            for (uint32_t idx = 0; idx < 8; ++idx) {
-                float t = 1.0f;
-#pragma unroll
-                for (uint32_t d = 0; d < 3; ++d) t *= (idx & (1u << d)) ? pos[d] : 1.0f - pos[d];
-                w[idx] = t;
-            }
-        }
-#pragma unroll
-        for (uint32_t idx = 0; idx < 8; ++idx) {
-            const uint32_t bits = __float_as_uint(cv[idx].v[0]);
-            acc[0] = fma_mix_lo(w[idx], bits, acc[0]);
-            acc[1] = fma_mix_hi(w[idx], bits, acc[1]);
-        }
-        return;
-    }
-    if constexpr (PKW && C == 2) {
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        const f2 wx = {1.0f - pos[0], pos[0]};
-        const float wy0 = 1.0f - pos[1], wz0 = 1.0f - pos[2];
-        const f2 xy0 = wx * f2{wy0, wy0}, xy1 = wx * f2{pos[1], pos[1]};
-        const f2 w01 = xy0 * f2{wz0, wz0}, w23 = xy1 * f2{wz0, wz0}, w45 = xy0 * f2{pos[2], pos[2]}, w67 = xy1 * f2{pos[2], pos[2]};
-        const float w[8] = {w01.x, w01.y, w23.x, w23.y, w45.x, w45.y, w67.x, w67.y};
-        f2 a = {0.0f, 0.0f};
-#pragma unroll
-        for (int idx = 0; idx < 8; ++idx) a = __builtin_elementwise_fma(f2{w[idx], w[idx]}, f2{cv[idx].v[0], cv[idx].v[1]}, a);
-        acc[0] = a.x; acc[1] = a.y;
-        return;
-    }
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; ++idx) {   // corner order and weight products exactly as gridencoder.cu:171-192
-        float w = 1.0f;
-#pragma unroll
-        for (uint32_t d = 0; d < 3; ++d) w *= (idx & (1u << d)) ? pos[d] : 1.0f - pos[d];
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = __builtin_fmaf(w, cv[idx].v[c], acc[c]);
-    }
-}
-
-// blend of a level whose gathers were issued with XSWAP: first give every lane its own corner values back
-template <typename T, int C, bool PKW = false>
-__device__ __forceinline__ void blend_level_x(const float (&pos)[3], const Corner<T, C> (&cv)[8], float (&acc)[C]) {
-    Corner<T, C> own[8];
-    if constexpr (C == 2 && sizeof(T) == 2) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            uint32_t a = __float_as_uint(cv[2 * p].v[0]), b = __float_as_uint(cv[2 * p + 1].v[0]);
-            half_wave_swap(a, b);
-            corner_set_half2(own[2 * p], a); corner_set_half2(own[2 * p + 1], b);
-        }
-        blend_level<T, C, PKW>(pos, own, acc);
-        return;
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            uint32_t a = __float_as_uint(cv[2 * p].v[c]), b = __float_as_uint(cv[2 * p + 1].v[c]);
-            half_wave_swap(a, b);
-            own[2 * p].v[c] = __uint_as_float(a); own[2 * p + 1].v[c] = __uint_as_float(b);
-        }
-    }
-    blend_level<T, C, PKW>(pos, own, acc);
-}
-
-// blend of a hashed FinalLv level issued with XSWAP and by parity (issue_level_lv<..., PY, PZ>): the half-wave exchange back, then lanes
-// whose cell was odd along z trade the landed values of slots i and i + 4, then those odd along y the slots i and i + 2 -- the issue
-// order undone in reverse -- and the unchanged blend on |pos| (the signs of pos[1] / pos[2] carried the parities)
-template <typename T, bool PY, bool PZ>
-__device__ __forceinline__ void blend_level_par(const float (&pos)[3], const Corner<T, 2> (&cv)[8], float (&acc)[2]) {
-    constexpr int NW = sizeof(T) == 2 ? 1 : 2;          // dwords per landed row: fp16 rows stay packed in v[0]
-    uint32_t w[8][NW];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-#pragma unroll
-        for (int c = 0; c < NW; ++c) {
-            uint32_t a = __float_as_uint(cv[2 * p].v[c]), b = __float_as_uint(cv[2 * p + 1].v[c]);
-            half_wave_swap(a, b);
-            w[2 * p][c] = a; w[2 * p + 1][c] = b;
-        }
-    }
-    float ap[3] = {pos[0], pos[1], pos[2]};
-    if constexpr (PZ) {
-        const bool odd = parity_of(pos[2]);
-        ap[2] = __builtin_fabsf(pos[2]);
-#pragma unroll
-        for (int c = 0; c < NW; ++c) swap_if4(odd, w[0][c], w[4][c], w[1][c], w[5][c], w[2][c], w[6][c], w[3][c], w[7][c]);
-    }
-    if constexpr (PY) {
-        const bool odd = parity_of(pos[1]);
-        ap[1] = __builtin_fabsf(pos[1]);
-#pragma unroll
-        for (int c = 0; c < NW; ++c) swap_if4(odd, w[0][c], w[2][c], w[1][c], w[3][c], w[4][c], w[6][c], w[5][c], w[7][c]);
-    }
-    Corner<T, 2> own[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        if constexpr (sizeof(T) == 2) corner_set_half2(own[i], w[i][0]);
-        else { own[i].v[0] = __uint_as_float(w[i][0]); own[i].v[1] = __uint_as_float(w[i][1]); }
-    }
-    blend_level<T, 2, true>(ap, own, acc);
-}
-
-// Encodes all L levels; `emit(l, acc)` receives each level's C features (zeros when out of range).
-// K = number of leading dense levels (levels >= K are hashed); K < 0: level kind decided at run time.
-// Returns true for lanes whose coordinate is outside [0,1] (gridencoder.cu:105-130 writes zeros for them): the
-// caller zeroes those lanes' features on a wave-uniform, practically never taken branch instead of paying a
-// select per level (positions are contracted into [0,1] on this path).
-template <typename T, int L, int C, int GROUP, int K, bool PAIR, typename Emit>
-__device__ __forceinline__ bool encode_grouped(const T *__restrict__ table, const GridLevels &g, const float (&x01)[3], Emit emit,
-                                               const PairTab *pt = nullptr) {
-    // (a last, shorter group is allowed: L = 5 levels in groups of 3 + 2)
-    bool oob = false;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) oob |= (x01[d] < 0.0f || x01[d] > 1.0f);
-    constexpr int G = GROUP >= L ? L : GROUP;
-    static_for<0, (L + G - 1) / G>([&](auto grp) {
-        constexpr int l0 = decltype(grp)::value * G;
-        constexpr int GN = (L - l0) < G ? (L - l0) : G;        // levels in this group
-        float pos[GN][3];
-        Corner<T, C> cv[GN][8];
-        static_for<0, GN>([&](auto kk) {
-            constexpr int k = decltype(kk)::value;
-            constexpr int KIND = K < 0 ? -1 : ((l0 + k) < K ? 0 : 1);
-            issue_level<T, C, KIND, (PAIR && K > 0 && K <= 8)>(table, g, l0 + k, x01, pos[k], cv[k], pt);
-        });
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < GN; ++k) {
-            float acc[C];
-            blend_level<T, C>(pos[k], cv[k], acc);
-            emit(l0 + k, acc);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    });
-    return oob;
-}
-
-// ---- software-pipelined form of encode_grouped ------------------------------------------------
-// issue_group<GRP> starts the GROUP*8 gathers of level group GRP; blend_group<GRP> consumes them.
-// The final stage uses the pair to keep the FIRST group of sample j+1 in flight across the
-// matrix-core phase of sample j (the compiler never hoists loads over the loop back-edge).
-template <typename T, int C, int G>
-struct GroupRegs {
-    float pos[G][3];
-    Corner<T, C> cv[G][8];
-    bool oob;
-};
-
-template <typename T, int C, int G, int K, int GRP>
-__device__ __forceinline__ void issue_group(const T *__restrict__ table, const GridLevels &g, const float (&x01)[3],
-                                            GroupRegs<T, C, G> &r, const PairTab &pt) {
-    r.oob = false;   // out-of-range lanes are fixed up by the caller on a wave-uniform rare path
-    static_for<0, G>([&](auto kk) {
-        constexpr int k = decltype(kk)::value;
-        constexpr int l = GRP * G + k;
-        constexpr int KIND = K < 0 ? -1 : (l < K ? 0 : 1);
-        issue_level<T, C, KIND, (K > 0 && K <= 8), xswap_level<T, KIND, l>()>(table, g, l, x01, r.pos[k], r.cv[k], &pt);
-    });
-}
-
-template <typename T, int C, int G, int K, int GRP, typename Emit>
-__device__ __forceinline__ void blend_group(const GroupRegs<T, C, G> &r, Emit emit) {
-    static_for<0, G>([&](auto kk) {
-        constexpr int k = decltype(kk)::value;
-        constexpr int l = GRP * G + k;
-        constexpr int KIND = K < 0 ? -1 : (l < K ? 0 : 1);
-        float acc[C];
-        if constexpr (xswap_level<T, KIND, l>()) blend_level_x<T, C, true>(r.pos[k], r.cv[k], acc);
-        else blend_level<T, C, true>(r.pos[k], r.cv[k], acc);
-        emit(l, acc);
-    });
-}
-
-// ---- final stage, specialised instantiations (K > 0: dense prefix + hashed tail): per-level constants from the host ----
-// The generic code above derives every per-level quantity from GridLevels inside the march: u32 -> f32 conversions of the
-// resolutions, 64-bit base pointers per level (more than the scalar file holds: ~150 v_readlane / v_writelane spill
-// instructions per sample), border selects and clamps on every level.  The final stage issues one instruction per
-// 4 cycles per SIMD whatever its type and is bound by exactly that, so this variant removes
-// instructions, bit-identically:
-//   * resolutions / limits arrive as floats and byte quantities in the kernel argument (FinalLv);
-//   * hashed levels of a GridEncoder table are equal-sized and contiguous (grid.py:121-136: a level is hashed iff it hit
-//     the 2^log2_hashmap_size cap), so ONE base pointer + a per-level byte offset OR-ed into the masked x term serves all
-//     of them; the two prime multiplies become full-rate 24-bit multiplies (only the bits under the mask matter);
-//   * FAST (wave-uniform, decided per sample): every lane's coordinate is at least one coarsest-hashed-level cell away
-//     from the border of [0,1]^3 -> on hashed levels neither the position clamp nor the clamp of the +1 neighbour
-//     (gridencoder.cu:148,182) can trigger, and out-of-range zeroing cannot apply.  Otherwise the general form runs.
-struct FinalLv {
-    float res_f[16];                 // level resolution (gridencoder.cu:133) as float
-    float top_f[16];                 // res - 1
-    uint32_t d_sy[8], d_sz[8];       // dense levels inside the pair / quad-row table (PairTab): y and z strides in bytes,
-    uint32_t d_ylim[8], d_zlim[8];   //   (res - 1) * stride, the clamp of the +1 neighbour,
-    uint32_t d_off[8];               //   byte offset of the level
-    uint32_t h_off[16];              // hashed levels: byte offset from the first hashed level (a multiple of size * row bytes)
-    uint32_t h_mask;                 // (size - 1) * row bytes, the same for every hashed level
-    float in_lo, in_hi;              // FAST <=> in_lo <= x01[d] <= in_hi for all lanes and dimensions
-    const char *pair_base, *hash_base;
-};
-
-template <typename T, bool DENSE, bool FAST, bool XSWAP, int l, bool PY = false, bool PZ = false>
-__device__ __forceinline__ void issue_level_lv(const FinalLv &lv, const float (&x01)[3], float (&pos)[3], Corner<T, 2> (&cv)[8]) {
-    static_assert(!(PY || PZ) || (!DENSE && XSWAP), "parity grouping: hashed levels, in front of the half-wave exchange");
-    constexpr uint32_t RB = 2u * (uint32_t)sizeof(T);              // bytes per table row (C = 2)
-    const float rf = lv.res_f[l];
-    uint32_t cell[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        float p = __builtin_fmaf(x01[d], rf, -0.5f);
-        if constexpr (DENSE || !FAST) p = __builtin_amdgcn_fmed3f(p, 0.0f, lv.top_f[l]);   // = min(max(p, 0), res-1), gridencoder.cu:148
-        cell[d] = (uint32_t)p;
-        pos[d] = __builtin_amdgcn_fractf(p);
-    }
-    if constexpr (DENSE) {
-        const uint32_t sy = lv.d_sy[l], sz = lv.d_sz[l];
-        const uint32_t X0 = __umul24(cell[0], 16u) + lv.d_off[l];
-        const uint32_t Y0 = __umul24(cell[1], sy), Z0 = __umul24(cell[2], sz);
-        const uint32_t Y1 = umin(Y0 + sy, lv.d_ylim[l]), Z1 = umin(Z0 + sz, lv.d_zlim[l]);
-        if constexpr (sizeof(T) == 2) {          // quad rows: (x,y), (x+1,y), (x,y+1), (x+1,y+1)
-#pragma unroll
-            for (int zi = 0; zi < 2; ++zi) {
-                const uint4 t = *reinterpret_cast<const uint4 *>(lv.pair_base + (X0 + Y0 + (zi ? Z1 : Z0)));
-                const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) corner_set_half2(cv[4 * zi + q], w[q]);
-            }
-        } else {                                 // pair rows: (x, x+1)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint32_t off = X0 + ((i & 1) ? Y1 : Y0) + ((i & 2) ? Z1 : Z0);
-                const float4 t = *reinterpret_cast<const float4 *>(lv.pair_base + off);
-                cv[2 * i].v[0] = t.x; cv[2 * i].v[1] = t.y; cv[2 * i + 1].v[0] = t.z; cv[2 * i + 1].v[1] = t.w;
-            }
-        }
-    } else {
-        constexpr uint32_t MY = (2654435761u * RB) & 0xFFFFFFu, MZ = (805459861u * RB) & 0xFFFFFFu;   // gridencoder.cu:49, low 24 bits
-        const uint32_t mask = lv.h_mask, ho = lv.h_off[l];
-        const uint32_t X0 = cell[0] * RB, Y0 = __umul24(cell[1], MY), Z0 = __umul24(cell[2], MZ);
-        uint32_t X1 = X0 + RB, Y1 = Y0 + MY, Z1 = Z0 + MZ;
-        if constexpr (!FAST) {                   // the +1 neighbour is clamped to res-1 (gridencoder.cu:182)
-            const uint32_t top = (uint32_t)lv.top_f[l];
-            X1 = cell[0] < top ? X1 : X0; Y1 = cell[1] < top ? Y1 : Y0; Z1 = cell[2] < top ? Z1 : Z0;
-        }
-        const uint32_t X0m = (X0 & mask) | ho, X1m = (X1 & mask) | ho;
-        uint32_t Y0m = Y0 & mask, Y1m = Y1 & mask, Z0m = Z0 & mask, Z1m = Z1 & mask;
-        // PARITY: slot a of an axis takes the corner whose absolute coordinate has parity a -- odd cells trade their two terms (with the
-        // clamped neighbour both terms are equal: the rule is only a grouping); the parity rides in the sign of pos[d] to the blend
-        if constexpr (PY) {
-            pos[1] = parity_tag(pos[1], cell[1]);
-            swap_if(parity_of(pos[1]), Y0m, Y1m);
-        }
-        if constexpr (PZ) {
-            pos[2] = parity_tag(pos[2], cell[2]);
-            swap_if(parity_of(pos[2]), Z0m, Z1m);
-        }
-        uint32_t offs[8];
-#pragma unroll
-        for (uint32_t i = 0; i < 8; ++i) offs[i] = ((i & 1u) ? X1m : X0m) ^ ((i & 2u) ? Y1m : Y0m) ^ ((i & 4u) ? Z1m : Z0m);
-        if constexpr (XSWAP) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) half_wave_swap(offs[2 * q], offs[2 * q + 1]);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const char *row = lv.hash_base + offs[i];
-            if constexpr (sizeof(T) == 4) {
-                const float2 t = *reinterpret_cast<const float2 *>(row);
-                cv[i].v[0] = t.x; cv[i].v[1] = t.y;
-            } else if constexpr (XSWAP) {
-                cv[i].v[0] = __uint_as_float(*reinterpret_cast<const uint32_t *>(row)); cv[i].v[1] = 0.0f;
-            } else {
-                corner_set_half2(cv[i], *reinterpret_cast<const uint32_t *>(row));
-            }
-        }
-    }
-}
-
-// levels L0 .. L0+G-1 (a "span": the gather groups of the final stage need not be equally long)
-// PAR = false: the canonical corner order on every level (the A/B partner of the parity order, experiments builds: SN_EXP_GATHER_CANONICAL)
-template <typename T, int L0, int G, int K, bool FAST, bool PAR = true>
-__device__ __forceinline__ void issue_span_lv(const FinalLv &lv, const float (&x01)[3], GroupRegs<T, 2, G> &r) {
-    r.oob = false;
-    static_for<0, G>([&](auto kk) {
-        constexpr int k = decltype(kk)::value;
-        constexpr int l = L0 + k;
-        constexpr bool DENSE = l < K;
-        issue_level_lv<T, DENSE, FAST, xswap_level<T, DENSE ? 0 : 1, l>(), l, PAR && !DENSE && parity_level<T, 1, l>(), PAR && !DENSE && parity_level<T, 2, l>()>(
-            lv, x01, r.pos[k], r.cv[k]);
-    });
-}
-template <typename T, int G, int K, int GRP, bool FAST, bool PAR = true>
-__device__ __forceinline__ void issue_group_lv(const FinalLv &lv, const float (&x01)[3], GroupRegs<T, 2, G> &r) {
-    issue_span_lv<T, GRP * G, G, K, FAST, PAR>(lv, x01, r);
-}
-template <typename T, int L0, int G, int K, bool PAR = true, typename Emit>
-__device__ __forceinline__ void blend_span(const GroupRegs<T, 2, G> &r, Emit emit) {
-    static_for<0, G>([&](auto kk) {
-        constexpr int k = decltype(kk)::value;
-        constexpr int l = L0 + k;
-        constexpr int KIND = K < 0 ? -1 : (l < K ? 0 : 1);
-        constexpr bool PY = PAR && KIND == 1 && parity_level<T, 1, l>(), PZ = PAR && KIND == 1 && parity_level<T, 2, l>();
-        float acc[2];
-        if constexpr (PY || PZ) blend_level_par<T, PY, PZ>(r.pos[k], r.cv[k], acc);
-        else if constexpr (xswap_level<T, KIND, l>()) blend_level_x<T, 2, true>(r.pos[k], r.cv[k], acc);
-        else blend_level<T, 2, true>(r.pos[k], r.cv[k], acc);
-        emit(l, acc);
-    });
-}
-// gather spans of the final stage (FinalLv path).  Span 0 is issued for sample j+1 before the matrix-core phase of sample j
-// (its registers are live across that phase), so it has to be short when the MLP needs many registers; it must be all dense.
-#ifndef SN_FINAL_SPANS_LT_H
-#define SN_FINAL_SPANS_LT_H 4  // the same for fp16 tables
-#endif
-#ifndef SN_FINAL_SPANS_LT
-#define SN_FINAL_SPANS_LT 4    // linear-tail instantiation: 64 weight-accumulated hidden values per lane live through the march -> short span 0
-#endif
-template <int CFG> struct FinalSpans;
-template <> struct FinalSpans<0> { static constexpr int N = 4; static constexpr int B[5] = {0, 4, 8, 12, 16}; };
-template <> struct FinalSpans<1> { static constexpr int N = 4; static constexpr int B[5] = {0, 2, 6, 11, 16}; };
-template <> struct FinalSpans<2> { static constexpr int N = 4; static constexpr int B[5] = {0, 3, 7, 12, 16}; };
-template <> struct FinalSpans<3> { static constexpr int N = 4; static constexpr int B[5] = {0, 1, 6, 11, 16}; };
-template <> struct FinalSpans<4> { static constexpr int N = 5; static constexpr int B[6] = {0, 2, 5, 9, 13, 16}; };
-template <> struct FinalSpans<5> { static constexpr int N = 5; static constexpr int B[6] = {0, 1, 4, 8, 12, 16}; };
-template <> struct FinalSpans<6> { static constexpr int N = 5; static constexpr int B[6] = {0, 2, 4, 8, 12, 16}; };
-template <> struct FinalSpans<7> { static constexpr int N = 5; static constexpr int B[6] = {0, 3, 6, 9, 13, 16}; };
-template <> struct FinalSpans<8> { static constexpr int N = 5; static constexpr int B[6] = {0, 4, 7, 10, 13, 16}; };
-template <> struct FinalSpans<9> { static constexpr int N = 6; static constexpr int B[7] = {0, 2, 5, 8, 11, 14, 16}; };
-template <> struct FinalSpans<10> { static constexpr int N = 3; static constexpr int B[4] = {0, 2, 9, 16}; };
-template <> struct FinalSpans<11> { static constexpr int N = 4; static constexpr int B[5] = {0, 2, 7, 12, 16}; };
-template <> struct FinalSpans<12> { static constexpr int N = 3; static constexpr int B[4] = {0, 4, 10, 16}; };
-template <> struct FinalSpans<13> { static constexpr int N = 3; static constexpr int B[4] = {0, 1, 8, 16}; };
-template <> struct FinalSpans<14> { static constexpr int N = 2; static constexpr int B[3] = {0, 5, 16}; };
-template <> struct FinalSpans<15> { static constexpr int N = 3; static constexpr int B[4] = {0, 3, 9, 16}; };
-
-// FAST test of one sample (see FinalLv): wave-uniform
-__device__ __forceinline__ bool all_interior(const FinalLv &lv, const float (&x01)[3]) {
-    const bool in = (x01[0] >= lv.in_lo && x01[0] <= lv.in_hi) && (x01[1] >= lv.in_lo && x01[1] <= lv.in_hi) &&
-                    (x01[2] >= lv.in_lo && x01[2] <= lv.in_hi);
-    return __all(in) != 0;
-}
-
-// all levels of one grid at one position into registers; D = 3.  gridencoder.cu:94-201 per level.
-template <typename T, int L, int C, int K, bool PAIRX, int GROUP = L>
-__device__ __forceinline__ void encode_levels(const T *__restrict__ table, const GridLevels &g, const float (&x01)[3],
-                                              float (&feat)[L * C], const PairTab *pt = nullptr) {
-    const bool oob = encode_grouped<T, L, C, GROUP, K, PAIRX>(table, g, x01, [&](int l, const float (&acc)[C]) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) feat[l * C + c] = acc[c];
-    }, pt);
-    // register variant (proposal stages): L*C unconditional selects; a branch here costs more in scheduling than it saves
-#pragma unroll
-    for (int i = 0; i < L * C; ++i) feat[i] = oob ? 0.0f : feat[i];
-}
-
-// U positions of one lane through the same grid at once: every level group issues the gathers of all U positions before the
-// first blend, so a wave carries U independent gather -> blend chains (the proposal stage is bound by the length of that chain,
-// not by an execution unit).  Values identical to U calls of encode_levels.
-template <typename T, int L, int C, int K, bool PAIRX, int GROUP, int U>
-__device__ __forceinline__ void encode_levels_multi(const T *__restrict__ table, const GridLevels &g, const float (&x01)[U][3],
-                                                    float (&feat)[U][L * C], const PairTab *pt = nullptr) {
-    constexpr int G = GROUP >= L ? L : GROUP;
-    static_for<0, (L + G - 1) / G>([&](auto grp) {
-        constexpr int l0 = decltype(grp)::value * G;
-        constexpr int GN = (L - l0) < G ? (L - l0) : G;
-        float pos[U][GN][3];
-        Corner<T, C> cv[U][GN][8];
-        static_for<0, U>([&](auto uu) {
-            constexpr int u = decltype(uu)::value;
-            static_for<0, GN>([&](auto kk) {
-                constexpr int k = decltype(kk)::value;
-                constexpr int KIND = K < 0 ? -1 : ((l0 + k) < K ? 0 : 1);
-                issue_level<T, C, KIND, (PAIRX && K > 0 && K <= 8)>(table, g, l0 + k, x01[u], pos[u][k], cv[u][k], pt);
-            });
-        });
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int k = 0; k < GN; ++k) {
-                float acc[C];
-                blend_level<T, C>(pos[u][k], cv[u][k], acc);
-#pragma unroll
-                for (int c = 0; c < C; ++c) feat[u][(l0 + k) * C + c] = acc[c];
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    });
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        bool oob = false;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) oob |= (x01[u][d] < 0.0f || x01[u][d] > 1.0f);
-#pragma unroll
-        for (int i = 0; i < L * C; ++i) feat[u][i] = oob ? 0.0f : feat[u][i];
-    }
-}
-
-// y = act(W x), W [OUT][IN] row-major at a wave-uniform address (SGPR / scalar-cache loads);
-// each output is one k-ascending fmaf chain (the oracle's order).
-template <int IN, int OUT, int ACT>
-__device__ __forceinline__ void dense_uniform(const float *__restrict__ W, const float (&x)[IN], float (&y)[OUT]) {
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < IN; ++k) acc = __builtin_fmaf(W[o * IN + k], x[k], acc);
-        if (ACT == 1) acc = relu_ieee(acc);                  // ReLU as one v_maximum_f32 (a NaN stays NaN, as torch.relu)
-        y[o] = acc;
-    }
-}
-
-// An always-zero offset the optimiser cannot see through.  Adding it to an LDS index inside the
-// sample loop stops loop-invariant code motion from hoisting every (loop-invariant) weight
-// read out of the loop and pinning hundreds of VGPRs for the whole march.
-__device__ __forceinline__ uint32_t opaque_zero() {
-    uint32_t z = 0;
-    asm volatile("" : "+v"(z));
-    return z;
-}
-
-// Tiny-MLP weights are staged once per workgroup in LDS with rows padded to a multiple of 4
-// floats, and read back at wave-uniform addresses (LDS broadcast, one ds_read_b128 per 4
-// weights).  Reading them through global pointers makes hipcc hoist hundreds of vector loads
-// (it cannot prove the buffers read-only next to the kernel's stores) and wrecks occupancy.
-template <int IN> struct PadIn { static constexpr int value = (IN + 3) & ~3; };
-
-// dst[k * OUTP + o] = W[o][k]  (k-major; rows padded to a multiple of 4 outputs)
-template <int IN, int OUT>
-__device__ __forceinline__ void stage_weights_t(float *__restrict__ dst, const float *__restrict__ src) {
-    constexpr int OUTP = PadIn<OUT>::value;
-    for (uint32_t i = threadIdx.x; i < (uint32_t)(IN * OUTP); i += blockDim.x) {
-        const uint32_t k = i / OUTP, o = i - k * OUTP;
-        dst[i] = o < (uint32_t)OUT ? src[o * IN + k] : 0.0f;
-    }
-}
-
-// y = act(W x), W k-major in LDS at a wave-uniform address (broadcast ds_read_b128 of 4 adjacent outputs);
-// every output is still ONE k-ascending fmaf chain starting from 0 (the oracle's order), the chains of
-// adjacent outputs just advance together, which lets the compiler use packed fp32 FMAs without shuffles.
-// PIN: the weights of input k+1 are fetched under the FMAs of input k and never earlier -- their address carries a fake dependence on the
-// accumulators of step k-1 (an empty asm).  In a register-hungry caller the scheduler otherwise fetches all IN * OUT weights ahead (160 registers).
-template <int IN, int OUT, int ACT, bool PIN = false>
-__device__ __forceinline__ void dense_ldsw_t(const float *__restrict__ Wl, const float (&x)[IN], float (&y)[OUT]) {
-    constexpr int OUTP = PadIn<OUT>::value;
-    float acc[OUTP];
-#pragma unroll
-    for (int o = 0; o < OUTP; ++o) acc[o] = 0.0f;
-    uint32_t z = 0;
-    float4 w[2][OUTP / 4];
-    if (PIN) {
-#pragma unroll
-        for (int o4 = 0; o4 < OUTP / 4; ++o4) w[0][o4] = *reinterpret_cast<const float4 *>(Wl + 4 * o4);
-    }
-#pragma unroll
-    for (int k = 0; k < IN; ++k) {
-#pragma unroll
-        for (int o4 = 0; o4 < OUTP / 4; ++o4) {
-            const float4 wk = PIN ? w[k & 1][o4] : *reinterpret_cast<const float4 *>(Wl + k * OUTP + 4 * o4);
-            if (PIN && o4 == 0 && k + 1 < IN) {
-                static_assert(!PIN || OUTP == 16, "the fake dependence lists 16 accumulators");
-                // (all accumulators as they stand after step k-1: the fetch of step k+1 cannot start before step k-1 is complete)
-                asm volatile("" : "+v"(z) : "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]),
-                                            "v"(acc[8 % OUTP]), "v"(acc[9 % OUTP]), "v"(acc[10 % OUTP]), "v"(acc[11 % OUTP]), "v"(acc[12 % OUTP]), "v"(acc[13 % OUTP]),
-                                            "v"(acc[14 % OUTP]), "v"(acc[15 % OUTP]));
-#pragma unroll
-                for (int q = 0; q < OUTP / 4; ++q) w[(k + 1) & 1][q] = *reinterpret_cast<const float4 *>(Wl + z + (k + 1) * OUTP + 4 * q);
-            }
-            acc[4 * o4 + 0] = __builtin_fmaf(wk.x, x[k], acc[4 * o4 + 0]);
-            acc[4 * o4 + 1] = __builtin_fmaf(wk.y, x[k], acc[4 * o4 + 1]);
-            acc[4 * o4 + 2] = __builtin_fmaf(wk.z, x[k], acc[4 * o4 + 2]);
-            acc[4 * o4 + 3] = __builtin_fmaf(wk.w, x[k], acc[4 * o4 + 3]);
-        }
-    }
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) y[o] = (ACT == 1) ? relu_ieee(acc[o]) : acc[o];
-}
-
-// Tiny-MLP weights in the [out][in_padded] layout (view MLP, evaluated once per ray)
-template <int IN, int OUT>
-__device__ __forceinline__ void stage_weights(float *__restrict__ dst, const float *__restrict__ src) {
-    constexpr int INP = PadIn<IN>::value;
-    for (uint32_t i = threadIdx.x; i < (uint32_t)(OUT * INP); i += blockDim.x) {
-        const uint32_t o = i / INP, k = i - o * INP;
-        dst[i] = k < (uint32_t)IN ? src[o * IN + k] : 0.0f;
-    }
-}
-
-// y = act(W x) with W in LDS (padded rows), fully unrolled; k-ascending fmaf chain per output.
-template <int IN, int OUT, int ACT>
-__device__ __forceinline__ void dense_ldsw(const float *__restrict__ Wl, const float (&x)[IN], float (&y)[OUT]) {
-    constexpr int INP = PadIn<IN>::value;
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k4 = 0; k4 < INP / 4; ++k4) {
-            const float4 w = *reinterpret_cast<const float4 *>(Wl + o * INP + 4 * k4);
-            if (4 * k4 + 0 < IN) acc = __builtin_fmaf(w.x, x[4 * k4 + 0], acc);
-            if (4 * k4 + 1 < IN) acc = __builtin_fmaf(w.y, x[4 * k4 + 1], acc);
-            if (4 * k4 + 2 < IN) acc = __builtin_fmaf(w.z, x[4 * k4 + 2], acc);
-            if (4 * k4 + 3 < IN) acc = __builtin_fmaf(w.w, x[4 * k4 + 3], acc);
-        }
-        if (ACT == 1) acc = relu_ieee(acc);                  // ReLU as one v_maximum_f32 (a NaN stays NaN, as torch.relu)
-        y[o] = acc;
-    }
-}
-
-// same, but the output loop stays rolled and activations travel through an LDS column
-// (xin[k*stride] -> yout[o*stride]); x is read completely before the first write, so
-// xin == yout is allowed.
-template <int IN, int OUT, int ACT>
-__device__ __forceinline__ void dense_ldsw_col(const float *__restrict__ Wl, const float *xin, float *yout, uint32_t stride) {
-    constexpr int INP = PadIn<IN>::value;
-    float x[IN];
-#pragma unroll
-    for (int k = 0; k < IN; ++k) x[k] = xin[k * stride];
-#pragma unroll 1
-    for (int o = 0; o < OUT; ++o) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k4 = 0; k4 < INP / 4; ++k4) {
-            const float4 w = *reinterpret_cast<const float4 *>(Wl + o * INP + 4 * k4);
-            if (4 * k4 + 0 < IN) acc = __builtin_fmaf(w.x, x[4 * k4 + 0], acc);
-            if (4 * k4 + 1 < IN) acc = __builtin_fmaf(w.y, x[4 * k4 + 1], acc);
-            if (4 * k4 + 2 < IN) acc = __builtin_fmaf(w.z, x[4 * k4 + 2], acc);
-            if (4 * k4 + 3 < IN) acc = __builtin_fmaf(w.w, x[4 * k4 + 3], acc);
-        }
-        if (ACT == 1) acc = relu_ieee(acc);                  // ReLU as one v_maximum_f32 (a NaN stays NaN, as torch.relu)
-        yout[o * stride] = acc;
-    }
-}
-
-// degree-4 real SH (16 values) of a unit vector; basis generated by tools/gen_sh.py
-__device__ __forceinline__ void sh_degree4(float x, float y, float z, float (&o)[16]) {
-    const uint32_t C = 4u;
-    SN_SH_POWERS
-    (void)x4; (void)x5; (void)x6; (void)x7; (void)y4; (void)y5; (void)y6; (void)y7; (void)z4; (void)z5; (void)z6; (void)z7;
-    SN_SH_VALUES(o);
-}
-
-__device__ __forceinline__ float nan_to_num(float v) {
-    if (v != v) return 0.0f;
-    if (v == __builtin_inff()) return FLT_MAX;
-    if (v == -__builtin_inff()) return -FLT_MAX;
-    return v;
-}
-
-// ------------------------------------------------------------------------------------------
-// proposal stage
-// ------------------------------------------------------------------------------------------
-struct PropArgs {
-    RayCommon rc;
-    GridLevels g;
-    const void *table;
-    const float *w0, *w1;        // MLP weights (device), [HID][IN], [1][HID]
-    uint32_t T, Tn;              // steps of this stage; bins of the next stage = Tn + 1
-    const float *bins_in;        // scratch [T+1][Npad] or NULL (stage 0)
-    const float *bins0_tab;      // device [T+1] (bins0_stride 0) or per ray [N][bins0_stride], or NULL (stage 0 only)
-    const float *u_tab;          // device [Tn+1] (u_stride 0) or per ray [N][u_stride], or NULL
-    uint32_t bins0_stride, u_stride;
-    float *dbg_bins_next;        // [N,Tn+1] or NULL: the resampled bins in the reference's layout (io->skip_final)
-    float *w_scr;                // scratch [T][Npad]
-    float *bins_out;             // scratch [Tn+1][Npad]
-    float *dbg_bins, *dbg_w, *dbg_sigma;  // [N,T+1], [N,T], [N,T] or NULL
-    int32_t *dbg_inds;                    // [N,Tn+1] or NULL
-    PairTab pairs;                        // dense levels as aligned x-pairs
-    int skip_miss;                        // the last stage runs k_final_stage_cmp: waves whose rays all miss the aabb leave at once
-};
-
-// renderer.py:133-135: near = far = 1e9 marks a ray that misses the aabb
-__device__ __forceinline__ bool ray_misses(const RayCommon &rc, const RaySetup &rs) {
-    float nr, fr;
-    near_far_one(rs.o, rs.d, rc.aabb, rc.min_near, nr, fr);
-    return nr == 1e9f && fr == 1e9f;
-}
-
-#ifndef SN_PROP_PB
-#define SN_PROP_PB 4         // cdf entries per block of the sample_pdf merge (pass 2 of the proposal stage); 8: same, 16: slower (select chains)
-#endif
-#ifndef SN_PROP_WAVES
-#define SN_PROP_WAVES 5      // waves per SIMD the proposal stage is compiled for (register budget 512 / N in steps of 8: 96 VGPRs); the
-                             // stage is bound by each wave's dependent chain, so a fifth wave buys 3-4 % (profiles/r02/ab_round2_experiments.txt)
-#endif
-#ifndef SN_PROP_GROUP_U2
-#define SN_PROP_GROUP_U2 1   // levels per gather group of the two-samples-at-once instantiation (x 2 positions)
-#endif
-#ifndef SN_PROP_WAVES_U2
-#define SN_PROP_WAVES_U2 3   // the two-samples-at-once instantiation (UN = 2): 168 VGPRs
-#endif
-// UN: samples of a ray evaluated together in pass 1 (their gathers and their MLP chains interleave: two dependent chains per wave instead of
-// one).  Every sample goes through the same arithmetic and the weights / the normaliser are formed in the same order: bit-identical to UN = 1.
-template <typename TT, int L, int C, int HID, int K, int UN = 1>
-__global__ __launch_bounds__(256, (UN == 1 ? SN_PROP_WAVES : SN_PROP_WAVES_U2)) void k_prop_stage(PropArgs a) {
-    SN_POISON_ALL();
-    constexpr int IN = L * C;
-    __shared__ __attribute__((aligned(16))) float lds_w0[IN * PadIn<HID>::value];   // k-major [IN][HID]
-    __shared__ __attribute__((aligned(16))) float lds_w1[PadIn<HID>::value];        // [1][HID]
-    stage_weights_t<IN, HID>(lds_w0, a.w0);
-    stage_weights<HID, 1>(lds_w1, a.w1);
-    __syncthreads();
-    uint32_t n;
-    const uint32_t wg = tile_id(a.rc);
-    const bool ok = ray_of_lane(a.rc, wg, n);
-    const uint32_t r = wg * 256u + threadIdx.x;           // scratch column
-    const uint32_t Npad = a.rc.Npad;
-    RaySetup rs;
-    setup_ray(a.rc, n, rs);
-    // opt-in compaction (cfg->compact_live): k_final_stage_cmp gives rays that miss the aabb (and lanes beyond the image
-    // edge) no samples and never reads their bins, so a wave made of such rays only has nothing to produce (no barrier follows)
-    if (a.skip_miss && __all(!ok || ray_misses(a.rc, rs))) return;
-    const uint32_t T = a.T;
-    const float b0step = 1.0f / (float)T;                 // (1-0)/(steps-1), steps = T+1
-
-    auto bin_at = [&](uint32_t j) -> float {
-        if (a.bins_in) return a.bins_in[(size_t)j * Npad + r];
-        if (a.bins0_tab) return a.bins0_tab[(size_t)n * a.bins0_stride + j];
-        return linspace_at(0.0f, 1.0f, b0step, T + 1u, j);
-    };
-
-    // ---- pass 1: sigma -> weights (renderer.py:277-325) ----
-    float bprev = bin_at(0);
-    float rb_prev = real_bin(rs, bprev);
-    if (ok && a.dbg_bins) a.dbg_bins[(size_t)n * (T + 1)] = bprev;
-    double cum = 0.0, wacc = 0.0;
-    const TT *table = reinterpret_cast<const TT *>(a.table);
-    const bool early_out = !a.dbg_bins && !a.dbg_sigma && !a.dbg_w;
-    // samples j .. j+U-1; returns true once the transmittance of all 64 rays of the wave has underflowed to exactly 0
-    auto march = [&](auto un_tag, uint32_t j) -> bool {
-        constexpr int U = decltype(un_tag)::value;
-        float bnext[U], rb_next[U], x01[U][3];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            bnext[u] = bin_at(j + (uint32_t)u + 1u);
-            rb_next[u] = real_bin(rs, bnext[u]);
-            const float tmid = (rb_next[u] + (u ? rb_next[u ? u - 1 : 0] : rb_prev)) / 2.0f;
-            float p[3];
-            sample_x01(a.rc, rs, tmid, p, x01[u]);
-        }
-        float feat[U][L * C], raw[U];
-        if constexpr (U == 1) encode_levels<TT, L, C, K, true, (sizeof(TT) == 4 ? SN_PROP_GROUP : SN_PROP_GROUP_H)>(table, a.g, x01[0], feat[0], &a.pairs);
-        else encode_levels_multi<TT, L, C, K, true, SN_PROP_GROUP_U2, U>(table, a.g, x01, feat, &a.pairs);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float h[HID], r1[1];
-            const uint32_t oz = opaque_zero();
-            dense_ldsw_t<IN, HID, 1, (U > 1)>(lds_w0 + oz, feat[u], h);
-            dense_ldsw<HID, 1, 0>(lds_w1 + oz, h, r1);
-            raw[u] = r1[0];
-        }
-        bool dark = false;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t ju = j + (uint32_t)u;
-            const float rbp = u ? rb_next[u ? u - 1 : 0] : rb_prev;
-            const float sigma = expf_det(raw[u]);                // trunc_exp forward (activation.py:9)
-            const float delta = rb_next[u] - rbp;
-            float ds = delta * sigma;
-            if (a.rc.last_opaque && ju == T - 1u) ds = __builtin_inff();
-            const float alpha = 1.0f - expf_det(-ds);
-            const float tr = expf_det(-(float)cum);
-            float w = alpha * tr;
-            if (w != w) w = 0.0f;
-            a.w_scr[(size_t)ju * Npad + r] = w;
-            cum += (double)ds;
-            wacc += (double)(w + 0.01f);
-            if (ok) {
-                if (a.dbg_bins) a.dbg_bins[(size_t)n * (T + 1) + ju + 1] = bnext[u];
-                if (a.dbg_sigma) a.dbg_sigma[(size_t)n * T + ju] = sigma;
-                if (a.dbg_w) a.dbg_w[(size_t)n * T + ju] = w;
-            }
-            // EXACT early-out (round 4): once the transmittance of all 64 rays of the wave has underflowed to exactly 0 it stays 0 (the optical
-            // depth never decreases), so every later weight is alpha * 0 = 0 whatever the density: the remaining samples are not evaluated, their
-            // weights are written as 0 and the pdf normaliser keeps taking its (0 + 0.01) terms in the same order.  Opaque scenes only; bit-identical.
-            // (with U > 1 the samples of the group that follow the underflow are still evaluated: their weights come out as the same zeros)
-            if (u == U - 1) dark = early_out && __all(tr == 0.0f);
-        }
-        rb_prev = rb_next[U - 1];
-        return dark;
-    };
-    {
-        uint32_t j = 0;
-        bool dark = false;
-        if constexpr (UN > 1) {
-            for (; j + (uint32_t)UN <= T && !dark; j += (uint32_t)UN) dark = march(std::integral_constant<int, UN>{}, j);
-        }
-        for (; j < T && !dark; ++j) dark = march(std::integral_constant<int, 1>{}, j);
-        for (; j < T; ++j) {                                   // (only after an early-out)
-            a.w_scr[(size_t)j * Npad + r] = 0.0f;
-            wacc += (double)(0.0f + 0.01f);
-        }
-    }
-
-    // ---- pass 2: sample_pdf (renderer.py:84-119) as one merge of cdf against u ----
-    // The cdf is walked in blocks of PB entries: the block's weights and bins are fetched with independent, coalesced loads
-    // (the former one-entry-at-a-time merge chained T dependent global loads per ray and cost 19 % of the stage), its PB
-    // prefix values are formed in the oracle's order (fp64 running sum of the pdf, rounded per prefix, clamped at 1), and
-    // every lane then emits the outputs whose searchsorted(right=True) count falls inside the block.
-    const float wsum = (float)wacc;
-    const uint32_t Tq = a.Tn + 1u;
-    const float ustart = (float)(0.5 / Tq), uend = (float)(1 - 0.5 / Tq);
-    const float ustep = (uend - ustart) / (float)(Tq - 1u);
-    auto u_at = [&](uint32_t j) -> float { return a.u_tab ? a.u_tab[(size_t)n * a.u_stride + (j < Tq ? j : Tq - 1u)] : linspace_at(ustart, uend, ustep, Tq, j); };
-    constexpr uint32_t PB = SN_PROP_PB;
-    uint32_t jq = 0;
-    float uj = u_at(0);
-    double acc = 0.0;
-    float c_start = 0.0f, b_start = bin_at(0);              // cdf[ib], bins[ib]
-    for (uint32_t ib = 0; ib < T; ib += PB) {
-        const bool last_block = ib + PB >= T;
-        float e_c[PB + 1], e_b[PB + 1];                     // entries ib .. ib+PB of the cdf and the bins (past T: repeats of entry T)
-        e_c[0] = c_start; e_b[0] = b_start;
-        float wv[PB];
-#pragma unroll
-        for (uint32_t k = 0; k < PB; ++k) {
-            const uint32_t idx = ib + k < T ? ib + k : T - 1u;
-            wv[k] = a.w_scr[(size_t)idx * Npad + r];
-            e_b[k + 1] = bin_at(idx + 1u);
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < PB; ++k) {
-            if (ib + k < T) {                               // uniform
-                const float pdf = (wv[k] + 0.01f) / wsum;
-                acc += (double)pdf;
-                const float c = (float)acc;
-                e_c[k + 1] = c > 1.0f ? 1.0f : c;
-            } else {
-                e_c[k + 1] = e_c[k];
-            }
-        }
-        const uint32_t nb = last_block ? T - ib : PB;       // real entries after e[0] in this block
-        // outputs of this block: all whose u is below the block's last cdf value; in the last block all that remain
-        while (jq < Tq && (last_block || e_c[PB] > uj)) {
-            uint32_t cnt = 0;                                // entries e[0..nb] that are <= uj (e is non-decreasing)
-#pragma unroll
-            for (uint32_t m = 0; m <= PB; ++m) cnt += (m <= nb && e_c[m] <= uj) ? 1u : 0u;
-            const uint32_t i = ib + cnt;                     // = searchsorted(cdf, u, right=True): every entry before ib is <= e[0]
-            // below = entry i-1, above = entry i; i == 0 -> both entry 0; i > T -> both entry T (renderer.py:104-107 clamps)
-            const uint32_t lo_m = cnt == 0u ? 0u : cnt - 1u, hi_m = cnt > nb ? nb : cnt;
-            float c0 = e_c[0], c1 = e_c[0], bb0 = e_b[0], bb1 = e_b[0];
-#pragma unroll
-            for (uint32_t m = 1; m <= PB; ++m) {
-                c0 = lo_m == m ? e_c[m] : c0; bb0 = lo_m == m ? e_b[m] : bb0;
-                c1 = hi_m == m ? e_c[m] : c1; bb1 = hi_m == m ? e_b[m] : bb1;
-            }
-            if (cnt > nb) { c0 = c1; bb0 = bb1; }            // i > T: below = above = the last entry
-            float t = nan_to_num((uj - c0) / (c1 - c0));
-            t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-            const float m = t * (bb1 - bb0);
-            a.bins_out[(size_t)jq * Npad + r] = bb0 + m;
-            if (ok && a.dbg_bins_next) a.dbg_bins_next[(size_t)n * Tq + jq] = bb0 + m;
-            if (ok && a.dbg_inds) a.dbg_inds[(size_t)n * Tq + jq] = (int32_t)i;
-            ++jq;
-            uj = u_at(jq);
-        }
-        c_start = e_c[PB]; b_start = e_b[PB];
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// proposal stage, sample-parallel variant for small ray batches (training steps: a few thousand rays)
-// ------------------------------------------------------------------------------------------
-// k_prop_stage walks one ray per lane: 4096 rays are 64 waves on a 1024-SIMD chip, each alone with its memory
-// latency, and a 128-sample stage takes 128 serial steps (0.55 ms for 4096 rays).  Here 8 lanes share a ray: each
-// evaluates a contiguous chunk of T/8 samples (the expensive part: position, grid, MLP), everything that must keep
-// the oracle's sequential order -- the fp64 optical-depth prefix, the cdf -- is done by the ray's first lane over
-// values parked in LDS (a few adds per sample), and the T_next + 1 resampled bins are found by a binary search
-// per output, 8 outputs at a time.  Same arithmetic, same order where order matters: bit-identical results.
-// Linear ray order only (scratch column = ray index), T <= SP_MAX_T.
-// Round 6: the lanes per ray are a template parameter (8, 16 or 32: 32, 16 or 8 rays per workgroup).  With 8 lanes a 4096-ray training batch is
-// 128 workgroups on 256 CUs and every lane walks T/8 = 16 samples one after the other; the launcher now picks the smallest count that gives
-// >= 512 workgroups (4096 rays: 32 lanes, 4 samples per lane).  The serial parts (prefix, cdf) and every sample's arithmetic are unchanged and
-// the fp64 sum of the weights is exact in any order: bit-identical for every choice (sn_render_tuning.prop_sp_lanes forces one).
-constexpr uint32_t SP_MAX_T = 128;        // 3 arrays x (256 / LPR) rays x (T+4) floats: 50 KiB of static LDS at 8 lanes per ray
-constexpr uint32_t SP_STRIDE = SP_MAX_T + 4;   // floats per ray per LDS array
-
-template <typename TT, int L, int C, int HID, int K, uint32_t SP_LPR = 8>
-__global__ __launch_bounds__(256, 3) void k_prop_stage_sp(PropArgs a) {
-    SN_POISON_ALL();
-    static_assert(SP_LPR == 8 || SP_LPR == 16 || SP_LPR == 32, "a ray's lanes live in one wave");
-    constexpr uint32_t RPB = 256u / SP_LPR;      // rays per workgroup
-    constexpr int IN = L * C;
-    __shared__ __attribute__((aligned(16))) float lds_w0[IN * PadIn<HID>::value];
-    __shared__ __attribute__((aligned(16))) float lds_w1[PadIn<HID>::value];
-    __shared__ float l_bins[RPB][SP_STRIDE];    // stage bins b_0..b_T of the rays of this workgroup
-    __shared__ float l_ds[RPB][SP_STRIDE];      // delta*sigma, then reused for the weights
-    __shared__ float l_cum[RPB][SP_STRIDE];     // (float) of the fp64 exclusive prefix of delta*sigma, then the cdf
-    stage_weights_t<IN, HID>(lds_w0, a.w0);
-    stage_weights<HID, 1>(lds_w1, a.w1);
-    const uint32_t tid = threadIdx.x, c = tid & (SP_LPR - 1u), rl = tid / SP_LPR;      // chunk index, local ray
-    const uint32_t n_raw = blockIdx.x * RPB + rl;
-    const bool ok = n_raw < a.rc.N;
-    const uint32_t n = ok ? n_raw : 0u, r = n_raw;                                     // scratch column = ray index (linear order)
-    const uint32_t Npad = a.rc.Npad, T = a.T;
-    RaySetup rs;
-    setup_ray(a.rc, n, rs);
-    const float b0step = 1.0f / (float)T;
-    auto bin_src = [&](uint32_t j) -> float {
-        if (a.bins_in) return a.bins_in[(size_t)j * Npad + r];
-        if (a.bins0_tab) return a.bins0_tab[(size_t)n * a.bins0_stride + j];
-        return linspace_at(0.0f, 1.0f, b0step, T + 1u, j);
-    };
-    for (uint32_t j = c; j <= T; j += SP_LPR) l_bins[rl][j] = bin_src(j);
-    __syncthreads();                                                                   // weights + bins in LDS
-    if (ok && a.dbg_bins) for (uint32_t j = c; j <= T; j += SP_LPR) a.dbg_bins[(size_t)n * (T + 1) + j] = l_bins[rl][j];
-
-    // ---- per-sample work, T / SP_LPR consecutive samples per lane ----
-    const uint32_t spl = (T + SP_LPR - 1u) / SP_LPR;
-    const TT *table = reinterpret_cast<const TT *>(a.table);
-    for (uint32_t i = 0; i < spl; ++i) {
-        const uint32_t jr = c * spl + i;
-        const uint32_t j = jr < T ? jr : T - 1u;                                       // lanes past the end redo the last sample
-        const float rb_prev = real_bin(rs, l_bins[rl][j]), rb_next = real_bin(rs, l_bins[rl][j + 1u]);
-        const float tmid = (rb_next + rb_prev) / 2.0f;
-        float p[3], x01[3];
-        sample_x01(a.rc, rs, tmid, p, x01);
-        float feat[L * C];
-        encode_levels<TT, L, C, K, true>(table, a.g, x01, feat, &a.pairs);
-        float h[HID], raw[1];
-        const uint32_t oz = opaque_zero();
-        dense_ldsw_t<IN, HID, 1>(lds_w0 + oz, feat, h);
-        dense_ldsw<HID, 1, 0>(lds_w1 + oz, h, raw);
-        const float sigma = expf_det(raw[0]);
-        float ds = (rb_next - rb_prev) * sigma;
-        if (a.rc.last_opaque && j == T - 1u) ds = __builtin_inff();
-        if (jr < T) {
-            l_ds[rl][j] = ds;
-            if (ok && a.dbg_sigma) a.dbg_sigma[(size_t)n * T + j] = sigma;
-        }
-    }
-    __syncthreads();
-    // ---- exclusive prefix of delta*sigma in the oracle's order: fp64 running sum, rounded per prefix ----
-    if (c == 0u) {
-        double cum = 0.0;
-        for (uint32_t j = 0; j < T; ++j) { l_cum[rl][j] = (float)cum; cum += (double)l_ds[rl][j]; }
-    }
-    __syncthreads();
-    // ---- weights (renderer.py:308-325); their fp64 sum is exact in any order (addends within 2^7 of each other) ----
-    double wacc = 0.0;
-    for (uint32_t i = 0; i < spl; ++i) {
-        const uint32_t j = c * spl + i;
-        if (j < T) {
-            const float alpha = 1.0f - expf_det(-l_ds[rl][j]);
-            const float tr = expf_det(-l_cum[rl][j]);
-            float w = alpha * tr;
-            if (w != w) w = 0.0f;
-            wacc += (double)(w + 0.01f);
-            l_ds[rl][j] = w;                                                             // own slot: no hazard
-            a.w_scr[(size_t)j * Npad + r] = w;                                           // padding columns too, like k_prop_stage
-            if (ok && a.dbg_w) a.dbg_w[(size_t)n * T + j] = w;
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < (int)SP_LPR; d <<= 1) wacc += __shfl_xor(wacc, d, SP_LPR);
-    const float wsum = (float)wacc;
-    __syncthreads();
-    // ---- cdf (renderer.py:92-96): fp64 running sum of the pdf, rounded per prefix, clamped at 1 ----
-    if (c == 0u) {
-        double acc = 0.0;
-        l_cum[rl][0] = 0.0f;
-        for (uint32_t j = 0; j < T; ++j) {
-            const float pdf = (l_ds[rl][j] + 0.01f) / wsum;
-            acc += (double)pdf;
-            const float cv = (float)acc;
-            l_cum[rl][j + 1u] = cv > 1.0f ? 1.0f : cv;
-        }
-    }
-    __syncthreads();
-    // ---- resample: searchsorted(cdf, u, right=True) per output, then the interpolation of renderer.py:104-119 ----
-    const uint32_t Tq = a.Tn + 1u;
-    const float ustart = (float)(0.5 / Tq), uend = (float)(1 - 0.5 / Tq);
-    const float ustep = (uend - ustart) / (float)(Tq - 1u);
-    for (uint32_t jq = c; jq < Tq; jq += SP_LPR) {
-        const float uj = a.u_tab ? a.u_tab[(size_t)n * a.u_stride + jq] : linspace_at(ustart, uend, ustep, Tq, jq);
-        uint32_t lo = 0u, hi = T + 1u;                                                   // number of cdf[0..T] entries <= uj
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (l_cum[rl][mid] <= uj) lo = mid + 1u; else hi = mid;
-        }
-        const uint32_t i = lo;
-        float c0, c1, bb0, bb1;
-        if (i == 0u) { c0 = c1 = l_cum[rl][0]; bb0 = bb1 = l_bins[rl][0]; }
-        else if (i > T) { c0 = c1 = l_cum[rl][T]; bb0 = bb1 = l_bins[rl][T]; }
-        else { c0 = l_cum[rl][i - 1u]; c1 = l_cum[rl][i]; bb0 = l_bins[rl][i - 1u]; bb1 = l_bins[rl][i]; }
-        float t = nan_to_num((uj - c0) / (c1 - c0));
-        t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-        const float m = t * (bb1 - bb0);
-        a.bins_out[(size_t)jq * Npad + r] = bb0 + m;
-        if (ok && a.dbg_bins_next) a.dbg_bins_next[(size_t)n * Tq + jq] = bb0 + m;
-        if (ok && a.dbg_inds) a.dbg_inds[(size_t)n * Tq + jq] = (int32_t)i;
-    }
-}
 
 // ------------------------------------------------------------------------------------------
 // final stage
@@ -1331,632 +89,6 @@ __device__ __forceinline__ void clock_probe(int slot) {
     }
 }
 
-// A-operand packing for the 32->64->64->16 MLP on v_mfma_f32_32x32x2_f32.
-//   D[m][j] += sum_k A[m][k] * B[k][j],  A = weights (m = output neuron), B = activations
-//   (j = sample).  Lane l supplies A[m = l&31][k = l>>5] and B[k = l>>5][j = l&31]; the
-//   accumulator register r of lane l holds D[(r&3) + 8*(r>>2) + 4*(l>>5)][l&31].
-//   Because that accumulator layout IS a valid B-operand layout (low half-wave: row h0(r),
-//   high half-wave: row h0(r)+4), layer n+1 consumes layer n's accumulators in place; only
-//   the weights are permuted, once, here.
-constexpr int PACK_L1 = 0;                       // [mt 2][step 16][64]
-constexpr int PACK_L2 = PACK_L1 + 2 * 16 * 64;   // [mt 2][step 32][64]
-constexpr int PACK_L3 = PACK_L2 + 2 * 32 * 64;   // [step 32][64]
-constexpr int PACK_FLOATS = PACK_L3 + 32 * 64;   // 8192 floats = 32 KiB
-
-__global__ void k_pack_grid_mlp(const float *__restrict__ w1, const float *__restrict__ w2, const float *__restrict__ w3,
-                                float *__restrict__ pack) {
-    SN_POISON_ALL();
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (uint32_t)PACK_FLOATS) return;
-    const uint32_t lane = t & 63u, vec = t >> 6;
-    const uint32_t m = lane & 31u, hi = lane >> 5;
-    float v;
-    if (vec < 32u) {                       // layer 1: in 32 -> out 64
-        const uint32_t mt = vec >> 4, s = vec & 15u;
-        v = w1[(mt * 32u + m) * 32u + 2u * s + hi];
-    } else if (vec < 96u) {                // layer 2: in 64 -> out 64
-        const uint32_t q = vec - 32u, mt = q >> 5, s = q & 31u, src_mt = s >> 4, r = s & 15u;
-        const uint32_t h = src_mt * 32u + (r & 3u) + 8u * (r >> 2) + 4u * hi;
-        v = w2[(mt * 32u + m) * 64u + h];
-    } else {                               // layer 3: in 64 -> out 16 (rows 16..31 are zero padding)
-        const uint32_t s = vec - 96u, src_mt = s >> 4, r = s & 15u;
-        const uint32_t h = src_mt * 32u + (r & 3u) + 8u * (r >> 2) + 4u * hi;
-        v = m < 16u ? w3[m * 64u + h] : 0.0f;
-    }
-    pack[t] = v;
-}
-
-
-// max(t, 0) of matrix-core results, one IEEE maximum each (relu_ieee: -0 -> +0, a NaN of either sign stays NaN like torch.relu).
-// fmaxf would cost two instructions there: the compiler cannot prove an MFMA output canonical and puts a v_max_f32 t, t, t in front of
-// every v_max_f32 0, t; the maximum needs no canonical input.
-__device__ __forceinline__ floatx16 relu16(floatx16 v) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = relu_ieee(v[i]);
-    return v;
-}
-
-// 32 -> 64 -> 64 -> 16 for the wave's 64 samples (lane = sample).
-// Features arrive through the wave's LDS slab fe[k][lane] (written by encode_levels_lds), which
-// is already a B-operand image: step s of sample tile t reads fe[2s + (lane>>5)][32t + (lane&31)].
-__device__ __forceinline__ void grid_mlp_mfma(const float *__restrict__ lds_pack, const float *__restrict__ fe, float (&out)[16]) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t lo = lane & 31u, hi = lane >> 5;
-    float res[2][8];
-#pragma unroll
-    for (int tile = 0; tile < 2; ++tile) {
-        floatx16 h1[2], h2[2], o3;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            floatx16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < 16; ++s)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_pack[PACK_L1 + (mt * 16 + s) * 64 + lane],
-                                                           fe[(2 * s + hi) * 64 + tile * 32 + lo], acc, 0, 0, 0);
-            h1[mt] = relu16(acc);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            floatx16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < 32; ++s)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_pack[PACK_L2 + (mt * 32 + s) * 64 + lane], h1[s >> 4][s & 15], acc, 0, 0, 0);
-            h2[mt] = relu16(acc);
-        }
-        {
-            floatx16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < 32; ++s)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_pack[PACK_L3 + s * 64 + lane], h2[s >> 4][s & 15], acc, 0, 0, 0);
-            o3 = acc;
-        }
-#pragma unroll
-        for (int r = 0; r < 8; ++r) res[tile][r] = o3[r];
-    }
-    // bring every sample's 16 outputs to its own lane: accumulator reg r of tile t holds rows
-    // base(r) [low half-wave] / base(r)+4 [high half-wave] of sample 32t + (lane&31)
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(res[0][r]), __float_as_uint(res[1][r]), false, false);
-        const int base = (r & 3) + 8 * (r >> 2);
-        out[base] = __uint_as_float(rr[0]);
-        out[base + 4] = __uint_as_float(rr[1]);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// fp16 hi/lo split path of the same MLP (MLP_F16X3, the default).
-// fp32 MFMA issues at the vector-ALU rate (64 cycles per 32x32x2), which made the matrix pipe the
-// co-bound of the final stage.  Writing every operand as x = hi + lo with hi = f16(x),
-// lo = f16(x - hi) (22 significant bits) and accumulating the three products hi*hi + hi*lo + lo*hi
-// in fp32 on v_mfma_f32_32x32x16_f16 costs 3 x 32 cycles per 32x32x16 block instead of 8 x 64:
-// 5.3x fewer matrix-pipe cycles at ~2^-22 relative error per product (f16 x f16 is exact in fp32;
-// the dropped lo*lo term is 2^-22).  Range: |activation| must stay below 65504.
-//   A operand (weights):     lane l holds W[m = l&31][k = 8*(l>>5) + 0..7] of the k-step
-//   B operand (activations): lane l holds X[k = 8*(l>>5) + 0..7][j = l&31]
-//   C/D layout as for every 32x32 MFMA: reg r of lane l = D[(r&3) + 8*(r>>2) + 4*(l>>5)][l&31]
-// so 8 consecutive accumulator registers of a lane are a valid B operand of the next layer
-// (low half-wave rows {0-3, 8-11} / high half-wave rows {4-7, 12-15} of that 16-row block); only
-// the weights' k order is permuted, once, by k_pack_grid_mlp_f16.
-// ------------------------------------------------------------------------------------------
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-constexpr int PACK16_VECS = 4 + 8 + 4;                 // layer1 [mt 2][s 2], layer2 [mt 2][q 4], layer3 [q 4]
-constexpr int PACK16_U4 = PACK16_VECS * 2 * 64;        // x (hi, lo) x 64 lanes, 16 B each = 32 KiB
-constexpr int SLAB_STRIDE = 20;                        // dwords per sample row (16 levels + 4 pad: conflict-free b128 reads)
-
-__device__ __forceinline__ void split2(float a, float b, uint32_t &hi, uint32_t &lo) {
-    const half2_t h = {(_Float16)a, (_Float16)b};
-    hi = __builtin_bit_cast(uint32_t, h);
-    // x - hi (exact in fp32: hi is x rounded to 11 bits) straight from the packed halves with the mixed-precision fma:
-    // v_fma_mix_f32 widens its f16 operand for free, where the compiler's form was two v_cvt_f32_f16 + one v_pk_add_f32
-    // (5 -> 4 instructions per pair, 80 pairs per sample in the final stage)
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hi), "v"(a));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hi), "v"(b));
-    const half2_t l = {(_Float16)l0, (_Float16)l1};
-    lo = __builtin_bit_cast(uint32_t, l);
-}
-
-__global__ void k_pack_grid_mlp_f16(const float *__restrict__ w1, const float *__restrict__ w2, const float *__restrict__ w3,
-                                    uint4 *__restrict__ pack) {
-    SN_POISON_ALL();
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;        // one thread per (vec, lane)
-    if (t >= (uint32_t)PACK16_VECS * 64u) return;
-    const uint32_t lane = t & 63u, vec = t >> 6;
-    const uint32_t m = lane & 31u, hi = lane >> 5;
-    float v[8];
-    if (vec < 4u) {                       // layer 1: k = 16 s + 8 hi + i  (feature 2*level + c)
-        const uint32_t mt = vec >> 1, sst = vec & 1u;
-        for (uint32_t i = 0; i < 8; ++i) v[i] = w1[(mt * 32u + m) * 32u + 16u * sst + 8u * hi + i];
-    } else {
-        const bool l3 = vec >= 12u;
-        const uint32_t q = l3 ? vec - 12u : (vec - 4u) & 3u, mt = l3 ? 0u : (vec - 4u) >> 2;
-        const uint32_t src_mt = q >> 1, half = q & 1u;
-        for (uint32_t i = 0; i < 8; ++i) {
-            const uint32_t r = 8u * half + i;
-            const uint32_t h = src_mt * 32u + (r & 3u) + 8u * (r >> 2) + 4u * hi;
-            v[i] = l3 ? (m < 16u ? w3[m * 64u + h] : 0.0f) : w2[(mt * 32u + m) * 64u + h];
-        }
-    }
-    uint4 ph, pl;
-    split2(v[0], v[1], ph.x, pl.x); split2(v[2], v[3], ph.y, pl.y);
-    split2(v[4], v[5], ph.z, pl.z); split2(v[6], v[7], ph.w, pl.w);
-    pack[(vec * 2u + 0u) * 64u + lane] = ph;
-    pack[(vec * 2u + 1u) * 64u + lane] = pl;
-}
-
-__device__ __forceinline__ floatx16 mfma3(const uint4 &ah, const uint4 &al, const uint4 &bh, const uint4 &bl, floatx16 acc) {
-    const half8_t Ah = __builtin_bit_cast(half8_t, ah), Al = __builtin_bit_cast(half8_t, al);
-    const half8_t Bh = __builtin_bit_cast(half8_t, bh), Bl = __builtin_bit_cast(half8_t, bl);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh, acc, 0, 0, 0);   // small terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh, acc, 0, 0, 0);
-    return acc;
-}
-
-// Reduced-product form of the split arithmetic (sn_render_tuning.mlp_mode = SN_MLP_F16X1; opt-in, NOT fp32-class, NOT within the 1e-4 bar):
-//   NP = 3  Al*Bh + Ah*Bl + Ah*Bh   (the default: every product to 2^-22)
-//   NP = 1  Ah*Bh                   plain fp16 operands with fp32 accumulation -- what an autocast fp16 run of the reference multiplies
-// Measured in round 6 (profiles/r06/mlp_modes_ab.json): 800x800 [128] 6.19 -> 5.44 ms, and max |dRGB| against the reference's own output on
-// the stress-init fixtures 3.2e-4 / 3.5e-4 (x3: 6e-7 / 7e-6) -- over the north star's 1e-4, so it can never be the default.  A two-product
-// form (weights exact, activations rounded to fp16) was measured too: 1.9e-4 / 2.6e-4, i.e. over the bar as well, and dropped.
-template <int NP>
-__device__ __forceinline__ floatx16 mfma_np(const uint4 &ah, const uint4 &al, const uint4 &bh, const uint4 &bl, floatx16 acc) {
-    if constexpr (NP == 3) return mfma3(ah, al, bh, bl, acc);
-    const half8_t Ah = __builtin_bit_cast(half8_t, ah), Bh = __builtin_bit_cast(half8_t, bh);
-    if constexpr (NP == 2) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, al), Bh, acc, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh, acc, 0, 0, 0);
-}
-__device__ __forceinline__ uint32_t pack_h2(float a, float b) {
-    const half2_t h = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(uint32_t, h);
-}
-// relu + fp16 rounding only (NP < 3: the lo image of an activation is never multiplied)
-__device__ __forceinline__ void acc_to_b_hi(const floatx16 &v, int half, uint4 &bh) {
-    float x[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = relu_ieee(v[8 * half + i]);
-    bh.x = pack_h2(x[0], x[1]); bh.y = pack_h2(x[2], x[3]); bh.z = pack_h2(x[4], x[5]); bh.w = pack_h2(x[6], x[7]);
-}
-
-// relu + split of 8 consecutive accumulator registers -> (hi, lo) B operand of the next layer
-__device__ __forceinline__ void acc_to_b(const floatx16 &v, int half, uint4 &bh, uint4 &bl) {
-    float x[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = relu_ieee(v[8 * half + i]);
-    split2(x[0], x[1], bh.x, bl.x); split2(x[2], x[3], bh.y, bl.y);
-    split2(x[4], x[5], bh.z, bl.z); split2(x[6], x[7], bh.w, bl.w);
-}
-
-// slab_hi / slab_lo: this wave's [64 samples][SLAB_STRIDE dwords] images written by encode_levels_split
-__device__ __forceinline__ void grid_mlp_mfma16(const uint4 *__restrict__ pk, const uint32_t *__restrict__ slab_hi,
-                                                const uint32_t *__restrict__ slab_lo, float (&out)[16]) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t lo = lane & 31u, hi = lane >> 5;
-    float res[2][8];
-#pragma unroll
-    for (int tile = 0; tile < 2; ++tile) {
-        const uint32_t row = (tile * 32u + lo) * SLAB_STRIDE + 4u * hi;
-        floatx16 h1[2], h2[2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            floatx16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                const uint4 bh = *reinterpret_cast<const uint4 *>(slab_hi + row + 8 * st);
-                const uint4 bl = *reinterpret_cast<const uint4 *>(slab_lo + row + 8 * st);
-                const int vec = mt * 2 + st;
-                acc = mfma3(pk[(vec * 2 + 0) * 64 + lane], pk[(vec * 2 + 1) * 64 + lane], bh, bl, acc);
-            }
-            h1[mt] = acc;
-            __builtin_amdgcn_sched_barrier(0);   // keep the next block's operand reads from being hoisted (VGPR pressure)
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            floatx16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint4 bh, bl;
-                acc_to_b(h1[q >> 1], q & 1, bh, bl);
-                const int vec = 4 + mt * 4 + q;
-                acc = mfma3(pk[(vec * 2 + 0) * 64 + lane], pk[(vec * 2 + 1) * 64 + lane], bh, bl, acc);
-            }
-            h2[mt] = acc;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        floatx16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            uint4 bh, bl;
-            acc_to_b(h2[q >> 1], q & 1, bh, bl);
-            const int vec = 12 + q;
-            acc = mfma3(pk[(vec * 2 + 0) * 64 + lane], pk[(vec * 2 + 1) * 64 + lane], bh, bl, acc);
-        }
-#pragma unroll
-        for (int r = 0; r < 8; ++r) res[tile][r] = acc[r];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(res[0][r]), __float_as_uint(res[1][r]), false, false);
-        const int base = (r & 3) + 8 * (r >> 2);
-        out[base] = __uint_as_float(rr[0]);
-        out[base + 4] = __uint_as_float(rr[1]);
-    }
-}
-
-// The same MLP with BOTH 32-sample tiles of the wave advancing together: every weight operand is read from LDS once per
-// wave-sample instead of once per tile (64 -> 32 ds_read_b128 of 1 KiB; the weight stream was 12 % of the final stage:
-// timing with the reads removed, profiles/r03/ab_round3_experiments.txt) and the matrix pipe always has two to four
-// independent accumulators in flight.  Every accumulator still receives exactly the same sequence of products (k-steps
-// ascending, small terms first), so the results are bit-identical to grid_mlp_mfma16.  Costs 64 more live registers at
-// the layer-2 peak (both tiles' h1 and all four layer-2 accumulators), paid for with a shorter prefetched gather span.
-__device__ __forceinline__ void grid_mlp_mfma16_2t(const uint4 *__restrict__ pk, const uint32_t *__restrict__ slab_hi,
-                                                   const uint32_t *__restrict__ slab_lo, float (&out)[16]) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t lo = lane & 31u, hi = lane >> 5;
-    const floatx16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    floatx16 h1[2][2];                                    // [tile][mt]
-#pragma unroll
-    for (int t = 0; t < 2; ++t) { h1[t][0] = zero16; h1[t][1] = zero16; }
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-        uint4 bh[2], bl[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const uint32_t row = (t * 32u + lo) * SLAB_STRIDE + 4u * hi + 8u * st;
-            bh[t] = *reinterpret_cast<const uint4 *>(slab_hi + row);
-            bl[t] = *reinterpret_cast<const uint4 *>(slab_lo + row);
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            const int vec = mt * 2 + st;
-            const uint4 ah = pk[(vec * 2 + 0) * 64 + lane], al = pk[(vec * 2 + 1) * 64 + lane];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) h1[t][mt] = mfma3(ah, al, bh[t], bl[t], h1[t][mt]);
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    floatx16 h2[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) { h2[t][0] = zero16; h2[t][1] = zero16; }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint4 bh[2], bl[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc_to_b(h1[t][q >> 1], q & 1, bh[t], bl[t]);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            const int vec = 4 + mt * 4 + q;
-            const uint4 ah = pk[(vec * 2 + 0) * 64 + lane], al = pk[(vec * 2 + 1) * 64 + lane];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) h2[t][mt] = mfma3(ah, al, bh[t], bl[t], h2[t][mt]);
-        }
-        __builtin_amdgcn_sched_barrier(0);                // one k-step at a time: h1 dies in halves behind this loop
-    }
-    floatx16 o3[2] = {zero16, zero16};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint4 bh[2], bl[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc_to_b(h2[t][q >> 1], q & 1, bh[t], bl[t]);
-        const int vec = 12 + q;
-        const uint4 ah = pk[(vec * 2 + 0) * 64 + lane], al = pk[(vec * 2 + 1) * 64 + lane];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) o3[t] = mfma3(ah, al, bh[t], bl[t], o3[t]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(o3[0][r]), __float_as_uint(o3[1][r]), false, false);
-        const int base = (r & 3) + 8 * (r >> 2);
-        out[base] = __uint_as_float(rr[0]);
-        out[base + 4] = __uint_as_float(rr[1]);
-    }
-}
-
-// Slab row addressing.  Padded form: 20 dwords per sample row.  Swizzled form (SW): 16 dwords per row, the four 16-byte blocks
-// of a row XOR-ed with (row >> 2) & 3 -- conflict-free for the ds_read_b128 of the B operands without the 4 padding dwords,
-// which frees 8 KiB per workgroup for the LDS-resident coarse level below.
-template <bool SW>
-__device__ __forceinline__ uint32_t slab_dword(uint32_t row, uint32_t d) {
-    if constexpr (SW) return row * 16u + ((((d >> 2) ^ (row >> 2)) & 3u) << 2) + (d & 3u);
-    else return row * (uint32_t)SLAB_STRIDE + d;
-}
-
-// LDS-resident level 0 (north_star: "LDS staging of per-tile grid voxels"; the reference's only gesture at table locality is its
-// level-major launch, gridencoder.cu:383-399).  The coarsest level of the main grid is 16^3 vertices = 16 KiB of fp16 rows: every
-// workgroup stages it once and its 2 x 128 samples per lane read their 8 corners with ds_read_b32 instead of two 16-byte gathers
-// through the texture path (98 -> 96 gather instructions per wave-sample).  Arithmetic as issue_level_lv's dense branch.
-[[maybe_unused]] constexpr int L0_MAX_ROWS = 4096;   // (used by experiments builds only)
-template <int l>
-__device__ __forceinline__ void issue_level0_lds(const FinalLv &lv, const uint32_t *__restrict__ l0tab, const float (&x01)[3], float (&pos)[3],
-                                                 Corner<__half, 2> (&cv)[8]) {
-    static_assert(l == 0, "level 0 only");
-    const float rf = lv.res_f[0];
-    uint32_t cell[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        float p = __builtin_fmaf(x01[d], rf, -0.5f);
-        p = __builtin_amdgcn_fmed3f(p, 0.0f, lv.top_f[0]);
-        cell[d] = (uint32_t)p;
-        pos[d] = __builtin_amdgcn_fractf(p);
-    }
-    // vertex index in dwords: x + res * y + res^2 * z (the quad-row strides of FinalLv are 16 bytes per vertex: >> 4)
-    const uint32_t sy = lv.d_sy[0] >> 4, sz = lv.d_sz[0] >> 4, top = (uint32_t)lv.top_f[0];
-    const uint32_t X0 = cell[0], X1 = umin(X0 + 1u, top);
-    const uint32_t Y0 = __umul24(cell[1], sy), Y1 = umin(Y0 + sy, lv.d_ylim[0] >> 4);
-    const uint32_t Z0 = __umul24(cell[2], sz), Z1 = umin(Z0 + sz, lv.d_zlim[0] >> 4);
-#pragma unroll
-    for (uint32_t i = 0; i < 8; ++i) {
-        corner_set_half2(cv[i], l0tab[((i & 1u) ? X1 : X0) + ((i & 2u) ? Y1 : Y0) + ((i & 4u) ? Z1 : Z0)]);
-    }
-}
-
-// "Linear tail" form of the final stage (k_final_stage<..., LT = true>).  The third layer has no activation behind it and the
-// compositing is linear in what it produces, so for the 15 geometry channels
-//     sum_j w_j * (W3[1:16] relu(h2_j))  =  W3[1:16] * (sum_j w_j relu(h2_j)),
-// (renderer.py:332-336 composites `color`, network.py:175-186 forms it from grid_mlp's outputs 1..15): only the density row of
-// the third layer is needed per sample -- one 64-term dot product, in true fp32 on the vector ALU -- while the geometry rows are
-// applied ONCE per ray to the weight-accumulated hidden vector.  That takes the third layer off the matrix cores: 72 instead
-// of 96 MFMAs per wave-sample and 48 instead of 64 KiB of LDS weight reads, which matters because the kernel runs at the
-// clock the power management allows (the matrix-core MLP costs ~4 % in cycles and ~14 % in clock).
-// A documented re-association like SH(d) * sum_j w_j; fp32 round-off class, not bit-identical to the
-// per-sample form the other final-stage kernels (and per-sample geometry outputs) keep.
-//
-// layers 1 and 2 of ONE tile (32 samples): x[mt * 16 + r] = relu(h2) of hidden row mt*32 + (r&3) + 8*(r>>2) + 4*(lane>>5)
-template <bool SW = false, int NP = 3>
-__device__ __forceinline__ void grid_mlp_mfma16_l12(const uint4 *__restrict__ pk, const uint32_t *__restrict__ slab_hi,
-                                                    const uint32_t *__restrict__ slab_lo, int tile, float (&x)[32]) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t lo = lane & 31u, hi = lane >> 5;
-    const uint32_t srow = (uint32_t)tile * 32u + lo;
-    floatx16 h1[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        floatx16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            const uint32_t off = slab_dword<SW>(srow, 4u * hi + 8u * (uint32_t)st);
-            const uint4 bh = *reinterpret_cast<const uint4 *>(slab_hi + off);
-            uint4 bl = bh;
-            if constexpr (NP == 3) bl = *reinterpret_cast<const uint4 *>(slab_lo + off);
-            const int vec = mt * 2 + st;
-            const uint4 ah = pk[(vec * 2 + 0) * 64 + lane];
-            uint4 al = ah;
-            if constexpr (NP >= 2) al = pk[(vec * 2 + 1) * 64 + lane];
-            acc = mfma_np<NP>(ah, al, bh, bl, acc);
-        }
-        h1[mt] = acc;
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        floatx16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            uint4 bh, bl;
-            if constexpr (NP == 3) acc_to_b(h1[q >> 1], q & 1, bh, bl);
-            else { acc_to_b_hi(h1[q >> 1], q & 1, bh); bl = bh; }
-            const int vec = 4 + mt * 4 + q;
-            const uint4 ah = pk[(vec * 2 + 0) * 64 + lane];
-            uint4 al = ah;
-            if constexpr (NP >= 2) al = pk[(vec * 2 + 1) * 64 + lane];
-            acc = mfma_np<NP>(ah, al, bh, bl, acc);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) x[mt * 16 + r] = relu_ieee(acc[r]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// W3 re-ordered for the linear tail: w3p[half][o][i] = W3[o][mt*32 + (r&3) + 8*(r>>2) + 4*half], i = mt*16 + r -- the hidden
-// rows a lane of that half-wave holds, in its register order (o = 0: density row, 1..15: geometry rows)
-constexpr int W3P_FLOATS = 2 * 16 * 32;
-constexpr int W3P_OFFSET = (12 * 2) * 64 * 4;            // floats: the packed layer-3 operands' place in the LDS weight image (unused here)
-static_assert(W3P_OFFSET + W3P_FLOATS <= PACK_FLOATS, "the re-ordered W3 fits where the packed layer-3 operands were");
-__device__ __forceinline__ void stage_w3p(float *__restrict__ dst, const float *__restrict__ w3) {
-    for (uint32_t t = threadIdx.x; t < (uint32_t)W3P_FLOATS; t += blockDim.x) {
-        const uint32_t i = t & 31u, o = (t >> 5) & 15u, half = t >> 9;
-        const uint32_t mt = i >> 4, r = i & 15u;
-        dst[t] = w3[o * 64u + mt * 32u + (r & 3u) + 8u * (r >> 2) + 4u * half];
-    }
-}
-// sum_i w[i] * x[i] over the lane's 32 hidden rows: four interleaved ascending fmaf chains, combined (s0 + s1) + (s2 + s3)
-typedef float f2v __attribute__((ext_vector_type(2)));
-// (one step of the four chains and their closing sum stand alone: the spread matrix phase below issues them apart, in the same order)
-__device__ __forceinline__ void dot32_step(const float4 &ww, float x0, float x1, float x2, float x3, f2v &s01, f2v &s23) {
-    s01 = __builtin_elementwise_fma(f2v{ww.x, ww.y}, f2v{x0, x1}, s01);
-    s23 = __builtin_elementwise_fma(f2v{ww.z, ww.w}, f2v{x2, x3}, s23);
-}
-__device__ __forceinline__ float dot32_sum(const f2v &s01, const f2v &s23) { return (s01.x + s01.y) + (s23.x + s23.y); }
-__device__ __forceinline__ float dot32_lds(const float *__restrict__ w, const float (&x)[32]) {
-    f2v s01 = {0.0f, 0.0f}, s23 = {0.0f, 0.0f};
-#pragma unroll
-    for (int i4 = 0; i4 < 8; ++i4) {
-        const float4 ww = *reinterpret_cast<const float4 *>(w + 4 * i4);
-        dot32_step(ww, x[4 * i4 + 0], x[4 * i4 + 1], x[4 * i4 + 2], x[4 * i4 + 3], s01, s23);
-    }
-    return dot32_sum(s01, s23);
-}
-
-// The matrix phase of one wave-sample in the linear-tail kernel -- layers 1 and 2 of BOTH tiles and each tile's share of the density row --
-// with its vector work issued UNDER its MFMAs.  grid_mlp_mfma16_l12 + dot32_lds above issue the same instructions in clumps: the 12 layer-1
-// MFMAs of a tile back to back with empty gaps, then ReLU + split blocks with the matrix pipe idle, every weight fragment requested right
-// in front of the wait that consumes it.  An MFMA of this shape holds the SIMD's vector issue for 8 of its 32 cycles, so about five vector
-// instructions per gap are (nearly) free and a clump is paid in full.  Here every gap between two MFMAs is one scheduling region (closed
-// by a sched_barrier) that holds what the table below puts there, one "piece" of about six vector instructions at a time:
-//   W(s)      the (hi, lo) weight fragment of step s is requested under step s - 1: lo behind its first MFMA (the only one that reads a lo
-//             image), hi behind its last -- each into registers that have just died, so the prefetch costs none (the waits are counted:
-//             later requests are in flight behind it)
-//   S(q, p)   ReLU + split of one register pair of h1 -> dword p of the layer-2 B operand q:  q = 0, 1 under the layer-1 mt = 1 chain,
-//             q = 2, 3 under the first layer-2 steps; each is complete one gap before the MFMA that reads it
-//   X(i4)     ReLU of four h2 registers + their step of the density dot: the mt = 0 half under the layer-2 mt = 1 chain, the mt = 1 half
-//             of tile 0 under tile 1's layer-1 chain (tile 1's own is the tail of the phase)
-//   B(t + 1)  tile 1's slab rows are requested under tile 0's layer 2, when the registers of tile 0's rows are free again
-// Every accumulator receives the products of its chain in the order of grid_mlp_mfma16_l12 (Al Bh, Ah Bl, Ah Bh; k ascending) and the
-// dot keeps dot32_lds's four chains: the results are equal bit for bit (tests/test_gpu_final_matrix_phase.py holds the two orders together).
-template <bool SW>
-__device__ __forceinline__ void grid_mlp_mfma16_l12_spread(const uint4 *__restrict__ pk, const uint32_t *__restrict__ slab_hi,
-                                                           const uint32_t *__restrict__ slab_lo, const float *__restrict__ w3,
-                                                           float (&xh)[2][32], float (&part)[2]) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t lo = lane & 31u, hi = lane >> 5;
-    const floatx16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint4 W[2][2];                  // [step & 1][0 = hi image, 1 = lo image]
-    uint4 B[2][2];                  // layer-1 B operand: [st][hi, lo]
-    uint32_t bb[4][2][4];           // layer-2 B operands: [q][hi, lo][dword]
-    floatx16 h1[2], h2[2][2];       // h2[tile][mt]
-    float4 ww[2][8];                // [tile][i4]: rows of the density row, requested a gap or two ahead of their step
-    f2v s01[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}}, s23[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
-    // tile 1 reads the weights tile 0 read: behind an offset of its own, or the optimiser keeps all 24 fragments of tile 0 in registers for it
-    const uint32_t oz1 = opaque_zero();
-    const uint4 *const pkT[2] = {pk, pk + oz1};
-    const float *const w3T[2] = {w3, w3 + oz1};
-    auto rdW = [&](int S, int im) { W[S & 1][im] = pkT[S / 12][((S % 12) * 2 + im) * 64 + lane]; };
-    auto rdB = [&](int t, int st, int im) {
-        const uint32_t off = slab_dword<SW>((uint32_t)t * 32u + lo, 4u * hi + 8u * (uint32_t)st);
-        B[st][im] = *reinterpret_cast<const uint4 *>((im ? slab_lo : slab_hi) + off);
-    };
-    auto rdw3 = [&](int t, int i4) { ww[t][i4] = *reinterpret_cast<const float4 *>(w3T[t] + 4 * i4); };
-    auto S_ = [&](int q, int p) {
-        const floatx16 &v = h1[q >> 1];
-        const int i = 8 * (q & 1) + 2 * p;
-        split2(relu_ieee(v[i]), relu_ieee(v[i + 1]), bb[q][0][p], bb[q][1][p]);
-    };
-    auto X_ = [&](int t, int i4) {
-        const floatx16 &v = h2[t][i4 >> 2];
-        const int r = 4 * (i4 & 3);
-        float (&x)[32] = xh[t];
-        x[4 * i4 + 0] = relu_ieee(v[r + 0]); x[4 * i4 + 1] = relu_ieee(v[r + 1]);
-        x[4 * i4 + 2] = relu_ieee(v[r + 2]); x[4 * i4 + 3] = relu_ieee(v[r + 3]);
-        dot32_step(ww[t][i4], x[4 * i4 + 0], x[4 * i4 + 1], x[4 * i4 + 2], x[4 * i4 + 3], s01[t], s23[t]);
-    };
-    // head: what the first MFMA reads first
-    rdW(0, 1); rdB(0, 0, 0); rdW(0, 0); rdB(0, 0, 1); rdB(0, 1, 0); rdB(0, 1, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    static_for<0, 2>([&](auto tt) {
-        constexpr int t = decltype(tt)::value;
-        static_for<0, 36>([&](auto mm) {
-            constexpr int m = decltype(mm)::value, s = m / 3, k = m % 3, S = 12 * t + s;
-            // ---- MFMA m of the tile: product k of step s ----
-            uint4 bh, bl;
-            if constexpr (s < 4) { bh = B[s & 1][0]; bl = B[s & 1][1]; }
-            else {
-                constexpr int q = s & 3;
-                bh = uint4{bb[q][0][0], bb[q][0][1], bb[q][0][2], bb[q][0][3]};
-                bl = uint4{bb[q][1][0], bb[q][1][1], bb[q][1][2], bb[q][1][3]};
-            }
-            floatx16 &acc = s < 4 ? h1[(s >> 1) & 1] : h2[t][s < 4 ? 0 : (s - 4) >> 2];
-            if constexpr (k == 0 && (s == 0 || s == 2 || s == 4 || s == 8)) acc = zero16;
-            const half8_t Ah = __builtin_bit_cast(half8_t, W[S & 1][0]), Al = __builtin_bit_cast(half8_t, W[S & 1][1]);
-            const half8_t Bh = __builtin_bit_cast(half8_t, bh), Bl = __builtin_bit_cast(half8_t, bl);
-            if constexpr (k == 0) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh, acc, 0, 0, 0);   // small terms first (mfma3)
-            if constexpr (k == 1) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl, acc, 0, 0, 0);
-            if constexpr (k == 2) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh, acc, 0, 0, 0);
-            // ---- the gap behind it ----
-            if constexpr (k == 0 && S + 1 < 24) rdW(S + 1, 1);       // the lo image was read by product 0 only: its registers take the next step's
-            if constexpr (k == 2 && S + 1 < 24) rdW(S + 1, 0);       // and the hi image's behind the step's last product
-            if constexpr (t == 1) {           // tile 0's tail
-                if constexpr (m == 0) { X_(0, 4); rdw3(0, 5); }
-                if constexpr (m == 1) { rdw3(0, 6); rdw3(0, 7); }
-                if constexpr (m == 3) X_(0, 5);
-                if constexpr (m == 4) X_(0, 6);
-                if constexpr (m == 5) { X_(0, 7); part[0] = dot32_sum(s01[0], s23[0]); }
-            }
-            if constexpr (m >= 6 && m < 14) S_((m - 6) >> 2, (m - 6) & 3);
-            if constexpr (m == 14) S_(2, 0);
-            if constexpr (m == 15) S_(2, 1);
-            if constexpr (m == 16) { S_(2, 2); S_(2, 3); }
-            if constexpr (m == 17) S_(3, 0);
-            if constexpr (m == 18) S_(3, 1);
-            if constexpr (m == 19) { S_(3, 2); S_(3, 3); }
-            if constexpr (t == 0) {           // tile 1's slab rows, into the registers the layer-2 operands q = 0..2 leave behind
-                if constexpr (m == 30) rdB(1, 0, 0);
-                if constexpr (m == 32) rdB(1, 0, 1);
-                if constexpr (m == 33) rdB(1, 1, 0);
-                if constexpr (m == 34) rdB(1, 1, 1);
-            }
-            if constexpr (m == 24) rdw3(t, 0);
-            if constexpr (m == 26) rdw3(t, 1);
-            if constexpr (m == 28) rdw3(t, 2);
-            if constexpr (m == 30) rdw3(t, 3);
-            if constexpr (m == 32) rdw3(t, 4);
-            if constexpr (m == 26) X_(t, 0);
-            if constexpr (m == 28) X_(t, 1);
-            if constexpr (m == 30) X_(t, 2);
-            if constexpr (m == 32) X_(t, 3);
-            if constexpr (t == 1) {           // the rows of the tail, while the last MFMAs run (no tile follows: the slab-row registers are free)
-                if constexpr (m == 33) rdw3(1, 5);
-                if constexpr (m == 34) rdw3(1, 6);
-                if constexpr (m == 35) rdw3(1, 7);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        });
-    });
-    // tail: tile 1's mt = 1 half
-    X_(1, 4); X_(1, 5); X_(1, 6); X_(1, 7);
-    part[1] = dot32_sum(s01[1], s23[1]);
-}
-
-// hash-grid features of one position, split into f16 hi / lo and written to this lane's slab rows
-// (dword l = the level's two features as a half2).
-template <typename T, int L, int GROUP, int K>
-__device__ __forceinline__ void encode_levels_split(const T *__restrict__ table, const GridLevels &g, const float (&x01)[3],
-                                                    uint32_t *__restrict__ row_hi, uint32_t *__restrict__ row_lo) {
-    const bool oob = encode_grouped<T, L, 2, GROUP, K, false>(table, g, x01, [&](int l, const float (&acc)[2]) {
-        uint32_t ph, pl;
-        split2(acc[0], acc[1], ph, pl);
-        row_hi[l] = ph;
-        row_lo[l] = pl;
-    });
-    if (__builtin_expect(__any(oob), 0)) {
-        if (oob) for (int l = 0; l < L; ++l) { row_hi[l] = 0u; row_lo[l] = 0u; }
-    }
-}
-
-// Scalar-pipe fallback of the same MLP (SN_RENDER_MLP=valu): activations live in per-thread LDS
-// columns act[k][tid]; every neuron is one k-ascending fmaf chain (the oracle's order).
-template <int IN, int OUT, int ACT>
-__device__ __forceinline__ void dense_lds(const float *__restrict__ W, const float *__restrict__ xin, float *__restrict__ yout, uint32_t stride) {
-    float x[IN];
-#pragma unroll
-    for (int k = 0; k < IN; ++k) x[k] = xin[k * stride];
-#pragma unroll 1
-    for (int o = 0; o < OUT; ++o) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < IN; ++k) acc = __builtin_fmaf(W[o * IN + k], x[k], acc);
-        if (ACT == 1) acc = relu_ieee(acc);                  // ReLU as one v_maximum_f32 (a NaN stays NaN, as torch.relu)
-        yout[o * stride] = acc;
-    }
-}
-
-// hash-grid features of one position written to an LDS column fe[k * stride]
-template <typename T, int L, int C, int GROUP, int K, bool PAIRX = false>
-__device__ __forceinline__ void encode_levels_lds(const T *__restrict__ table, const GridLevels &g, const float (&x01)[3],
-                                                  float *__restrict__ fe, uint32_t stride) {
-    const bool oob = encode_grouped<T, L, C, GROUP, K, PAIRX>(table, g, x01, [&](int l, const float (&acc)[C]) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) fe[(l * C + c) * stride] = acc[c];
-    });
-    if (__builtin_expect(__any(oob), 0)) {
-        if (oob) for (int i = 0; i < L * C; ++i) fe[i * stride] = 0.0f;
-    }
-}
-
-enum { MLP_VALU = 0, MLP_F32 = 1, MLP_F16X3 = 2 };
-#ifndef SN_RS_SPANS_H
-#define SN_RS_SPANS_H 6      // role-split producers, fp16 tables: 6 spans like fp32 tables, or 4 spans of 4 levels
-#endif
-#ifndef SN_FINAL_WAVES
-#ifndef SN_FINAL_SP_MIN_BLOCKS
-#define SN_FINAL_SP_MIN_BLOCKS 256u    // the several-lanes-per-ray last stage takes fewer samples per lane until the launch has this many workgroups
-                                       // (round 6, same box: 512 / 1024 are 3-8 % slower from 4096 to 16 384 rays -- one workgroup per CU is this kernel's optimum)
-#endif
-#define SN_FINAL_WAVES 2     // waves per SIMD k_final_stage is compiled for (register budget); experiments only
-#endif
 
 // AUX: the instantiation that also serves the feature stage (weights -> scratch) and the opt-in early termination;
 // the plain one carries neither (one spilled register less in the march of the headline configuration)
@@ -4170,9 +2302,12 @@ static PropKern prop_kernel(const PropRoute &p) {
 }
 
 using FinalKern = void (*)(FinalArgs);
-// k_final_stage at the reference network's sizes
-template <typename TT, int MODE, int K, bool AUX = false, bool LT = false, bool L0L = false, bool EO = false, int NP = 3, bool PORD = false, bool CANON = false>
-static FinalKern fs() { return k_final_stage<TT, 16, 2, 64, 64, 16, 32, MODE, K, AUX, LT, L0L, EO, NP, PORD, CANON>; }
+// k_final_stage at the reference network's sizes; its boolean template parameters as one flag word (the names are k_final_stage's)
+enum : unsigned { FS_AUX = 1u, FS_LT = 2u, FS_L0L = 4u, FS_EO = 8u, FS_PORD = 16u, FS_CANON = 32u };
+template <typename TT, int MODE, int K, unsigned F = 0u, int NP = 3>
+static FinalKern fs() {
+    return k_final_stage<TT, 16, 2, 64, 64, 16, 32, MODE, K, (F & FS_AUX) != 0u, (F & FS_LT) != 0u, (F & FS_L0L) != 0u, (F & FS_EO) != 0u, NP, (F & FS_PORD) != 0u, (F & FS_CANON) != 0u>;
+}
 template <typename TT> static FinalKern final_kernel_of(const FinalRoute &f) {
     constexpr bool half = std::is_same<TT, __half>::value;
     switch (f.family) {
@@ -4184,36 +2319,36 @@ template <typename TT> static FinalKern final_kernel_of(const FinalRoute &f) {
 #ifdef SN_EXPERIMENTS
         case FinalRoute::RS: return k_final_stage_rs<TT, 5>;
         case FinalRoute::LT_L0:
-            if constexpr (half) return f.aux ? fs<__half, MLP_F16X3, 5, true, true, true>() : fs<__half, MLP_F16X3, 5, false, true, true>();
+            if constexpr (half) return f.aux ? fs<__half, MLP_F16X3, 5, FS_AUX | FS_LT | FS_L0L>() : fs<__half, MLP_F16X3, 5, FS_LT | FS_L0L>();
             return nullptr;
 #endif
         case FinalRoute::LT:
             if constexpr (half) {
-                if (f.np == 1) return f.K == 7 ? fs<__half, MLP_F16X3, 7, false, true, false, false, 1>() : fs<__half, MLP_F16X3, 5, false, true, false, false, 1>();
+                if (f.np == 1) return f.K == 7 ? fs<__half, MLP_F16X3, 7, FS_LT, 1>() : fs<__half, MLP_F16X3, 5, FS_LT, 1>();
             }
 #ifdef SN_EXPERIMENTS
             if (f.clumped) {
-                if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, false, true, false, true, 3, true>() : fs<TT, MLP_F16X3, 7, false, true, false, false, 3, true>();
-                if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, true, true, false, true, 3, true>() : fs<TT, MLP_F16X3, 5, true, true, false, false, 3, true>();
-                return f.eo ? fs<TT, MLP_F16X3, 5, false, true, false, true, 3, true>() : fs<TT, MLP_F16X3, 5, false, true, false, false, 3, true>();
+                if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, FS_LT | FS_EO | FS_PORD>() : fs<TT, MLP_F16X3, 7, FS_LT | FS_PORD>();
+                if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, FS_AUX | FS_LT | FS_EO | FS_PORD>() : fs<TT, MLP_F16X3, 5, FS_AUX | FS_LT | FS_PORD>();
+                return f.eo ? fs<TT, MLP_F16X3, 5, FS_LT | FS_EO | FS_PORD>() : fs<TT, MLP_F16X3, 5, FS_LT | FS_PORD>();
             }
             if (f.canon && f.np == 3) {
-                if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, false, true, false, true, 3, false, true>() : fs<TT, MLP_F16X3, 7, false, true, false, false, 3, false, true>();
-                if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, true, true, false, true, 3, false, true>() : fs<TT, MLP_F16X3, 5, true, true, false, false, 3, false, true>();
-                return f.eo ? fs<TT, MLP_F16X3, 5, false, true, false, true, 3, false, true>() : fs<TT, MLP_F16X3, 5, false, true, false, false, 3, false, true>();
+                if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, FS_LT | FS_EO | FS_CANON>() : fs<TT, MLP_F16X3, 7, FS_LT | FS_CANON>();
+                if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, FS_AUX | FS_LT | FS_EO | FS_CANON>() : fs<TT, MLP_F16X3, 5, FS_AUX | FS_LT | FS_CANON>();
+                return f.eo ? fs<TT, MLP_F16X3, 5, FS_LT | FS_EO | FS_CANON>() : fs<TT, MLP_F16X3, 5, FS_LT | FS_CANON>();
             }
 #endif
-            if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, false, true, false, true>() : fs<TT, MLP_F16X3, 7, false, true, false, false>();
-            if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, true, true, false, true>() : fs<TT, MLP_F16X3, 5, true, true, false, false>();
-            return f.eo ? fs<TT, MLP_F16X3, 5, false, true, false, true>() : fs<TT, MLP_F16X3, 5, false, true, false, false>();
+            if (f.K == 7) return f.eo ? fs<TT, MLP_F16X3, 7, FS_LT | FS_EO>() : fs<TT, MLP_F16X3, 7, FS_LT>();
+            if (f.aux) return f.eo ? fs<TT, MLP_F16X3, 5, FS_AUX | FS_LT | FS_EO>() : fs<TT, MLP_F16X3, 5, FS_AUX | FS_LT>();
+            return f.eo ? fs<TT, MLP_F16X3, 5, FS_LT | FS_EO>() : fs<TT, MLP_F16X3, 5, FS_LT>();
         case FinalRoute::PER_SAMPLE:      // the plain instantiation unless the extras are on
 #ifdef SN_EXPERIMENTS
-            if (f.canon && f.K == 5) return f.aux ? fs<TT, MLP_F16X3, 5, true, false, false, false, 3, false, true>() : fs<TT, MLP_F16X3, 5, false, false, false, false, 3, false, true>();
+            if (f.canon && f.K == 5) return f.aux ? fs<TT, MLP_F16X3, 5, FS_AUX | FS_CANON>() : fs<TT, MLP_F16X3, 5, FS_CANON>();
 #endif
-            if (f.K == 5) return f.aux ? fs<TT, MLP_F16X3, 5, true>() : fs<TT, MLP_F16X3, 5, false>();
-            return f.aux ? fs<TT, MLP_F16X3, -1, true>() : fs<TT, MLP_F16X3, -1, false>();
-        case FinalRoute::MFMA32: return fs<TT, MLP_F32, -1, true>();
-        case FinalRoute::VALU: return fs<TT, MLP_VALU, -1, true>();
+            if (f.K == 5) return f.aux ? fs<TT, MLP_F16X3, 5, FS_AUX>() : fs<TT, MLP_F16X3, 5>();
+            return f.aux ? fs<TT, MLP_F16X3, -1, FS_AUX>() : fs<TT, MLP_F16X3, -1>();
+        case FinalRoute::MFMA32: return fs<TT, MLP_F32, -1, FS_AUX>();
+        case FinalRoute::VALU: return fs<TT, MLP_VALU, -1, FS_AUX>();
         default: return nullptr;          // (ANY and SP take further arguments: launch_final names them)
     }
 }

@@ -1,4 +1,4 @@
-"""The fused renderer (render.hip):
+"""The fused renderer (render.hip: sn_rm_render_rays; its front part lives in csrc/render_*.h):
 
     render_rays          nerf/renderer.py:221-357 + nerf/network.py:146-186, fused
 """

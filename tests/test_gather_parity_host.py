@@ -1,4 +1,4 @@
-"""CPU tests of the parity order of the last stage's hashed-level gathers (render.hip: issue_level_lv<..., PY, PZ> / blend_level_par): a numpy
+"""CPU tests of the parity order of the last stage's hashed-level gathers (render_gather.h: issue_level_lv<..., PY, PZ> / blend_level_par): a numpy
 restatement of the slot permutation -- permute by cell parity, trade the x-pairs between the wave's halves, trade back, un-permute -- and the
 line model of tools/gather_parity_table.py, which the choice of levels rests on."""
 import os

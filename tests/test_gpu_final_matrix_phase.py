@@ -1,4 +1,4 @@
-"""GPU tests of the matrix phase of the linear-tail last stage (render.hip: grid_mlp_mfma16_l12_spread), whose vector work -- ReLU and
+"""GPU tests of the matrix phase of the linear-tail last stage (render_mfma.h: grid_mlp_mfma16_l12_spread), whose vector work -- ReLU and
 hi/lo splits, the density dot, the weight and slab reads -- is issued under its MFMAs: parity with the CPU oracle, bit equality with the
 order it replaces (tuning.experiment = EXP_MATRIX_CLUMPED, experiments builds) and equal bits from call to call, on images of one full
 workgroup and of a padded one, sample counts that hit the first, the last and an odd iteration of the march, both table precisions and

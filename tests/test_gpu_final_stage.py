@@ -262,7 +262,7 @@ def test_random_field_sizes_through_the_size_agnostic_stage(gpu):
                                             (9, 17, [128], True), (56, 72, [128, 64, 32], False), (200, 120, [32], True)])
 def test_wave_tile_workgroups_any_band_shape(gpu, orc, H, W, steps, f16, monkeypatch):
     """A workgroup of the fused stages is four CONSECUTIVE 8x8 wave tiles (pairs of wave-tile rows column-major, an odd last row left to
-    right: render.hip ray_of_lane), so that a band whose height is 8 mod 16 launches ceil(wave tiles / 4) workgroups.  Shapes with an odd
+    right: render_rays.h ray_of_lane), so that a band whose height is 8 mod 16 launches ceil(wave tiles / 4) workgroups.  Shapes with an odd
     number of wave-tile rows / columns, partial wave tiles and workgroups that straddle two row pairs: image, depth, weights and sample
     indices equal the linear-order launch bit for bit and the oracle within the fp32 contract."""
     from sanerf_hq_amd import raymarching as rm

@@ -1,4 +1,4 @@
-"""GPU tests of the parity order of the last stage's hashed-level gathers (render.hip: issue_level_lv<..., PY, PZ> / blend_level_par): a lane
+"""GPU tests of the parity order of the last stage's hashed-level gathers (render_gather.h: issue_level_lv<..., PY, PZ> / blend_level_par): a lane
 puts into instruction (a, b) of a level the corner whose absolute y / z has parity a / b, and trades the landed values back before the blend.
 A wrong slot is an error of order 1e-2 in the image.  Shapes: a block of the bench camera's 800x800 ray grid, where the lanes of a wave sit in
 equal and adjacent cells of the fine levels (merged lines, mixed parities inside one instruction), and a small wide-angle image whose rays each

@@ -1,5 +1,5 @@
 """CPU: which part of the image a workgroup of the render stages takes under each tuning.linear_tile_order, through
-sn_rm_tile_order_info -- the host twin of the kernels' own arithmetic (render.hip: xcd_tile_id, wave_tile_of), no device needed.
+sn_rm_tile_order_info -- the host twin of the kernels' own arithmetic (render_rays.h: xcd_tile_id, wave_tile_of), no device needed.
 
 Every order is a bijection between the wave-tile slots of the launch's workgroups and the wave tiles of the image, for whole images, odd
 wave-tile row counts (the 32x8-pixel workgroups of the last row), widths that are no multiple of 16, the row bands of dist.shard_rows

@@ -1,4 +1,4 @@
-"""CPU: the eight wave-tile queues of the persistent last stage (render.hip: tile_queue_range, k_final_stage_pt) through
+"""CPU: the eight wave-tile queues of the persistent last stage (render_rays.h: tile_queue_range; render.hip: k_final_stage_pt) through
 sn_rm_tile_queue_info -- the host twin of the kernel's own arithmetic, no device needed -- and the planner's choice of the launch form
 through sn_rm_render_route_info_cus (tests/test_render_route_host.py builds the descriptors).
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage (GPU box, repo root): tools/xswap_ab.sh [out-file]   -- which lanes trade the two x-corners of a hashed cell in the last stage (SN_XSWAP_MODE, render.hip):
+# usage (GPU box, repo root): tools/xswap_ab.sh [out-file]   -- which lanes trade the two x-corners of a hashed cell in the last stage (SN_XSWAP_MODE, render_knobs.h):
 # bench line (800x800, [128], fp16 tables; and fp32 tables) of the product library and of ab/xswap1.so (neighbour lanes) / ab/xswap2.so (16-lane rows), built
 # by tools/build_variant.sh, alternating, with a checksum of the image (the modes must agree bit for bit).
 out=${1:-$GRAFT_REPO_ROOT/gpurun_out/r06/xswap_ab.txt}; mkdir -p $(dirname $out); : > $out
