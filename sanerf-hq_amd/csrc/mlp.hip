@@ -556,11 +556,11 @@ __global__ __launch_bounds__(256, 1) void k_mlp_wide(WideArgs a) {
                             const uint32_t w = sw[mt >> 1] >> (16 * (mt & 1) + 4 * q);
                             h = make_float4((w & 1u) ? 1.0f : 0.0f, (w & 2u) ? 1.0f : 0.0f, (w & 4u) ? 1.0f : 0.0f, (w & 8u) ? 1.0f : 0.0f);
                         } else h = *reinterpret_cast<const float4 *>(mrow + m0);
-                        float4 v;
-                        v.x = acc[mt][4 * q + 0] * (h.x > 0.0f ? 1.0f : slope);
-                        v.y = acc[mt][4 * q + 1] * (h.y > 0.0f ? 1.0f : slope);
-                        v.z = acc[mt][4 * q + 2] * (h.z > 0.0f ? 1.0f : slope);
-                        v.w = acc[mt][4 * q + 3] * (h.w > 0.0f ? 1.0f : slope);
+                        float4 v;                             // fma(g, d, +0.0): a closed ReLU unit is +0.0 as in torch, never g * 0 = -0.0; the same value everywhere else
+                        v.x = __builtin_fmaf(acc[mt][4 * q + 0], h.x > 0.0f ? 1.0f : slope, 0.0f);
+                        v.y = __builtin_fmaf(acc[mt][4 * q + 1], h.y > 0.0f ? 1.0f : slope, 0.0f);
+                        v.z = __builtin_fmaf(acc[mt][4 * q + 2], h.z > 0.0f ? 1.0f : slope, 0.0f);
+                        v.w = __builtin_fmaf(acc[mt][4 * q + 3], h.w > 0.0f ? 1.0f : slope, 0.0f);
                         acc[mt][4 * q + 0] = v.x; acc[mt][4 * q + 1] = v.y; acc[mt][4 * q + 2] = v.z; acc[mt][4 * q + 3] = v.w;
                         if (ok) *reinterpret_cast<float4 *>(drow + m0) = make_float4(v.x * row_unscale, v.y * row_unscale, v.z * row_unscale, v.w * row_unscale);
                     }
@@ -971,7 +971,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_wide_j(WideArgs a) {
             const uint32_t w16 = sbits[t >> 1] >> (16 * (t & 1));
             static_for<16>([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
-                float v = acc[t][r] * ((!hid || ((w16 >> r) & 1u)) ? 1.0f : slope);
+                float v = __builtin_fmaf(acc[t][r], (!hid || ((w16 >> r) & 1u)) ? 1.0f : slope, 0.0f);   // (+0.0 for a closed ReLU unit: see k_mlp_wide<4>)
                 asm("" : "+v"(v));
                 prev[16 * t + r] = v;
             });

@@ -48,7 +48,8 @@ def mlp_forward(x: torch.Tensor, mlp, layer_norm: Optional[torch.nn.LayerNorm] =
     """SkipConnMLP / MLP forward [+ LayerNorm] in one matrix-core kernel (network.py:9-66, 115; the feature heads
     of renderer.py:359-385).  x [N, dim_in] -> [N, dim_out].  Inference only (no autograd graph); hidden width 256.
     check_range (default: environment SN_CHECK_RANGE=1): query the overflow flag after the call (one synchronisation) and
-    raise if an activation left the fp16 range -- the inputs are run-time data, so no static bound exists for this kernel."""
+    raise if an activation left the fp16 range -- the inputs are run-time data, so no static bound exists for this kernel.
+    Rows are not rescaled: an input or weight v is held to within max(2^-23 |v|, 2^-25), an ABSOLUTE floor below |v| = 1/4."""
     L = _lib.lib()
     x = _f32(x)
     layers = list(mlp.net)
