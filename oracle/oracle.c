@@ -670,6 +670,7 @@ static void sample_pdf_one(const float *bins, const float *weights, uint32_t T0,
     uint32_t i = 0; /* cdf and u are both non-decreasing: one merge pass == searchsorted(right=True) */
     for (uint32_t j = 0; j < T; j++) {
         const float uj = u[j];
+        if (j && uj < u[j - 1]) i = 0;  /* a row that steps back (a perturbed one may, by an ulp): searchsorted looks each element up on its own */
         while (i <= T0 && cdf[i] <= uj) i++;
         const int32_t ind = (int32_t)i;
         int32_t below = ind - 1; if (below < 0) below = 0; if (below > (int32_t)T0) below = (int32_t)T0;

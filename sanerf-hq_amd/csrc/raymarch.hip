@@ -138,8 +138,14 @@ __global__ __launch_bounds__(256) void k_sample_pdf(const float *__restrict__ bi
     float c_prev = 0.0f;     // cdf[i-1]
     float c_cur = 0.0f;      // cdf[i]   (cdf[0] = 0)
     float b_prev = b[0], b_cur = b[0];
+    float u_last = -__builtin_inff();
     for (uint32_t j = 0; j < T; ++j) {
         const float uj = u ? u[(size_t)n * u_stride + j] : linspace_at(ustart, uend, ustep, T, j);
+        if (uj < u_last) {                 // a row that steps back (a perturbed one may, by an ulp): searchsorted looks each element up on its
+            i = 0; acc = 0;                // own, as k_sample_pdf_wave does -- start the merge again
+            c_prev = c_cur = 0.0f; b_prev = b_cur = b[0];
+        }
+        u_last = uj;
         while (i <= T0 && c_cur <= uj) {   // advance: cdf[i] <= u
             c_prev = c_cur; b_prev = b_cur;
             ++i;
@@ -206,7 +212,7 @@ __global__ __launch_bounds__(256) void k_weights_wave(const float *__restrict__ 
         const bool live = j < T;
         float ds = live ? (rb[j + 1] - rb[j]) * sg[j] : 0.0f;
         if (live && last_opaque && j == T - 1u) ds = __builtin_inff();
-        const float add = (live && ds != __builtin_inff()) ? ds : 0.0f;      // +inf is the last sample: nothing follows it
+        const float add = live ? ds : 0.0f;      // +inf and NaN enter the running sum as in k_weights: every later sample gets weight 0
         double excl = 0.0;
 #pragma unroll
         for (uint32_t q = 0; q < 64u; ++q) {
@@ -309,7 +315,8 @@ __global__ __launch_bounds__(256) void k_weights_backward(const float *__restric
         double incl = (live && !opaque) ? (double)ds : 0.0;      // the opaque sample is last: nothing comes after it
 #pragma unroll
         for (uint32_t k = 1; k < 64u; k <<= 1) { const double v = __shfl_up(incl, k); if (lane >= k) incl += v; }
-        const double excl = carry + incl - ((live && !opaque) ? (double)ds : 0.0);
+        const double before = __shfl_up(incl, 1);                // the lane before's inclusive prefix.  (Not incl - ds: that is inf - inf at a mid-ray
+        const double excl = carry + (lane ? before : 0.0);       // +inf, and cancels to 0 at a huge finite ds, whose sample then got the full weight.)
         const double total = __shfl(incl, 63);
         if (opaque) ds = __builtin_inff();
         const float tr = expf_det(-(float)excl);
@@ -327,7 +334,8 @@ __global__ __launch_bounds__(256) void k_weights_backward(const float *__restric
         float incl = gwv;
 #pragma unroll
         for (uint32_t k = 1; k < 64u; k <<= 1) { const float v = __shfl_down(incl, k); if (lane + k < 64u) incl += v; }
-        const float after = tail + incl - gwv;          // strictly later samples
+        const float later = __shfl_down(incl, 1);       // the next lane's inclusive suffix: the strictly later samples of this segment
+        const float after = tail + (lane < 63u ? later : 0.0f);     // (not incl - gwv: where g w of the sample dwarfs what follows, that cancels)
         tail += __shfl(incl, 0);
         const uint32_t j = s * 64u + lane;
         if (j < T) gs[j] = delta * (dterm - after);
